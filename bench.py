@@ -15,9 +15,17 @@ encode with error feedback (HIP), RCCL all-gather of the packed payloads, fused 
 SGD (HIP).  Weak scaling: the per-GPU batch is fixed as N grows.  The byte fields report the
 payload per rank, the algorithmic wire bytes, and the reference-equivalent MiB/step.
 
-Extra measured fields (same K / W, after the headline run): ``value_fp32_no_ef`` (the same step
-without error feedback: its cost) and ``value_bf16`` / ``ms_per_step_bf16`` (bf16 autocast with bf16
-weight copies, error feedback on).  ``--no-extras`` skips them.
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds the
+extra measured fields (same K / W, after the headline run): ``value_fp32_no_ef`` (the same step
+without error feedback: its cost), ``value_bf16`` / ``ms_per_step_bf16`` (bf16 autocast with bf16
+weight copies, error feedback on), ``value_dense_fp32`` (dense fp32 all-reduce) and
+``value_method6`` (local SGD); ``--full --no-extras`` is the plain run again.
+
+``--dump-outputs DIR`` writes what the last timed step of the headline run returned and left
+behind as ``DIR/<name>.npy`` (float32): ``loss``, ``logits``, ``labels`` and ``params`` (the flat
+parameters after the step; a fixed seeded sample of them when they exceed the size cap).  The
+data, the initial weights and the codec's random stream are seeded, so the same arguments give the
+same inputs on every run.
 """
 import argparse
 import json
@@ -66,7 +74,13 @@ def parse(argv=None):
     p.add_argument("--fused-nn", default="on", choices=["on", "off"])
     p.add_argument("--no-overlap", action="store_true")
     p.add_argument("--error-feedback", default="on", choices=["on", "off"])
-    p.add_argument("--no-extras", action="store_true", help="headline run only")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run also measure the extra configurations (no error "
+                        "feedback, bf16, dense fp32, Method 6)")
+    p.add_argument("--no-extras", action="store_true",
+                   help="headline run only (the default; overrides --full)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the last timed step's outputs to DIR/<name>.npy")
     # auto: the one-graph step at N = 1 and for top-k payloads; per-bucket collectives overlapped
     # with backward (segmented graphs) for large dense collectives at N > 1 (plan_graph_mode)
     p.add_argument("--hip-graph", default="auto",
@@ -112,7 +126,7 @@ def _flags(a, world, amp, ef):
     return flags + a.extra.split(), gw
 
 
-def measure(a, world, amp, ef, extra=()):
+def measure(a, world, amp, ef, extra=(), dump=None):
     """Build a Trainer for this configuration, run W untimed warmup steps, then time exactly K
     steps bracketed by barrier + synchronize on both sides; returns (max-over-ranks seconds,
     trainer, final loss, host enqueue seconds, per-rank seconds [min, max], replica check).
@@ -130,7 +144,7 @@ def measure(a, world, amp, ef, extra=()):
     flags, gw = _flags(a, world, amp, ef)
     tr = Trainer(ewdml.parse_args(flags + list(extra), prog="bench.py"))
     try:
-        return _measure(a, tr, gw)
+        return _measure(a, tr, gw, dump)
     finally:
         tr.close()  # watchdog and own RCCL communicator (the next measure() builds its own)
 
@@ -160,7 +174,33 @@ def _pick_unroll(steps: int, umax: int) -> int:
     return best[1]
 
 
-def _measure(a, tr, gw):
+# --dump-outputs: most elements written per array (48 MB of float32; the whole dump stays under
+# 64 MB); a larger array is sampled at fixed seeded positions
+DUMP_MAX_ELEMS = 12 * 1024 * 1024
+
+
+def _dump_outputs(path, tr, loss, out):
+    """Write the last timed step's results (rank 0's) as float32 ``path/<name>.npy``."""
+    import numpy as np
+    import torch
+
+    if tr.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    logits, labels = out if out is not None else (None, None)
+    arrays = {"loss": loss, "logits": logits, "labels": labels, "params": tr.flat.data}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
+def _measure(a, tr, gw, dump=None):
     import torch
 
     def sync():
@@ -194,12 +234,14 @@ def _measure(a, tr, gw):
         time.sleep(0.25)
     t0 = time.perf_counter()
     loss = None
-    loss, _ = tr.train_steps(a.steps, unroll)
+    loss, out = tr.train_steps(a.steps, unroll)
     t_enq = time.perf_counter()  # host done enqueuing (the GPU may still be running)
     sync()
     t1 = time.perf_counter()
     if os.environ.get("EWDML_PROF_GAP") == "1":  # ... and after it (outside the clock)
         time.sleep(0.25)
+    if dump:
+        _dump_outputs(dump, tr, loss, out)
     tr.comm.barrier()
     sync()
     elapsed_max = tr.comm.all_reduce_scalars([t1 - t0], op="max")[0]
@@ -241,7 +283,8 @@ def main(argv=None):
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}; launch with torch.distributed.run")
     ef = a.error_feedback == "on"
-    elapsed_max, tr, final_loss, enq, span, rep = measure(a, world, a.amp, ef)
+    elapsed_max, tr, final_loss, enq, span, rep = measure(a, world, a.amp, ef,
+                                                          dump=a.dump_outputs)
     cuda = tr.cuda
     ms = elapsed_max * 1e3 / a.steps
     img_s = world * a.batch_size * a.steps / elapsed_max
@@ -329,7 +372,7 @@ def main(argv=None):
     if world == 1 and rec["predicted_ms_per_step"]:
         rec["model_error_n1"] = round(rec["predicted_ms_per_step"] / rec["ms_per_step"] - 1, 4)
     del tr
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         extras = []
         if ef:
             extras.append(("fp32_no_ef" if a.amp == "none" else f"{a.amp}_no_ef", a.amp, False,

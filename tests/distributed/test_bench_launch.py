@@ -22,12 +22,15 @@ def _free_port():
 
 
 @pytest.mark.parametrize("preset,batch", [("lenet", 32), ("vgg11", 4)])
-def test_bench_two_ranks_gloo(preset, batch):
+def test_bench_two_ranks_gloo(preset, batch, tmp_path):
+    import numpy as np
+
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--preset", preset,
-           "--batch-size", str(batch), "--hip-graph", "off"]
+           "--batch-size", str(batch), "--hip-graph", "off", "--full",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -55,6 +58,14 @@ def test_bench_two_ranks_gloo(preset, batch):
         assert rec[f"replicas_identical_{k}"] is True, k
     assert rec["comm"] == "process-group" and rec["rccl_world"] == 0
     assert rec["step_ms_min"] <= rec["step_ms_max"] == pytest.approx(rec["ms_per_step"], rel=1e-3)
+    # --dump-outputs: the headline run's last step (rank 0), float32, the loss as reported
+    dump = {n: np.load(tmp_path / "dump" / f"{n}.npy")
+            for n in ("loss", "logits", "labels", "params")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in dump.values())
+    assert dump["loss"].shape == (1,) and float(dump["loss"][0]) == rec["final_loss"]
+    classes = 10
+    assert dump["logits"].size == batch * classes and dump["labels"].size == batch
+    assert dump["params"].size > 0 and np.abs(dump["params"]).max() > 0
     if preset == "vgg11":
         assert rec["config"]["model"] == "vgg11_bn"
         assert rec["metric"].startswith("grad bytes/step on wire + images/sec, VGG-11")

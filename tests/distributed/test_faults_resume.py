@@ -83,16 +83,17 @@ def test_injected_fault_aborts_all_ranks_without_hang(tmp_path):
     assert codes[0] != 0  # the healthy rank aborts too instead of hanging
 
 
-REF_CKPT = "/root/reference/PyTorch-parameter-server/src/model_step_.zip"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_CKPT), reason="reference checkout not mounted")
 def test_reference_lenet_checkpoint_loads():
-    """The reference ships a LeNet state_dict (torch zip format); it loads into our LeNet with the
-    safe loader, and our evaluator path can score it."""
-    from ewdml.models import build_model
+    """The reference ships a LeNet state_dict (torch zip format; a copy is stored under
+    tests/golden/lenet_checkpoint); it loads into our LeNet with the safe loader, and our
+    evaluator path can score it."""
+    import io
 
-    sd = torch.load(REF_CKPT, map_location="cpu", weights_only=True)
+    from ewdml.models import build_model
+    from tests.golden_data import GOLDEN, read_parts
+
+    ckpt = read_parts(os.path.join(GOLDEN, "lenet_checkpoint", "model_step_.zip"))
+    sd = torch.load(io.BytesIO(ckpt), map_location="cpu", weights_only=True)
     m = build_model("LeNet")
     m.load_state_dict(sd)
     assert sum(v.numel() for v in sd.values()) == 431080

@@ -1,6 +1,6 @@
 """Accuracy of the GPU training path (HIP codecs, fused kernels, full HIP-graph steps).
 
-* LeNet on real MNIST: the reference ships only the 10K test images (``tests/fixtures/mnist``,
+* LeNet on real MNIST: the reference ships only the 10K test images (``tests/golden/mnist``,
   copied from its ``data/MNIST/raw/t10k-*``); train on 9K, score the held-out 1K.  Floors: the
   report's Method 5 LeNet figure, 96.5 % (``Report.zip:Top1 Accuracy.png``), for the
   dense exchange, for top-1 % + 8-bit QSGD with error feedback (the bench codec) and for the
@@ -10,18 +10,16 @@
   module-by-module fp32 path (MIOpen, PyTorch BN / head) over 300 steps.  Real CIFAR is absent from
   the reference checkout, so CIFAR accuracy parity stays unpinned.
 """
-import os
-
 import pytest
 import torch
 
 import ewdml
 from ewdml import ops
+from tests.golden_data import mnist_root
 
 pytestmark = pytest.mark.gpu
 
-MNIST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fixtures",
-                     "mnist")
+MNIST = mnist_root()
 
 
 def _train(flags, steps):

@@ -1,9 +1,7 @@
 """Accuracy on real data: the reference checkout ships the 10K MNIST *test* images
-(``data/MNIST/raw/t10k-images-idx3-ubyte.gz``).  LeNet is trained on 9K of them and scored on the
+(``data/MNIST/raw/t10k-images-idx3-ubyte.gz``, stored under ``tests/golden/mnist``).  LeNet is trained on 9K of them and scored on the
 held-out 1K, per codec.  The report's LeNet accuracies are 96.5-98 %; top-1 % without
 error feedback is expected a few points lower (the reference's Method 5 used K = 0.4, also tested)."""
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -15,11 +13,9 @@ from ewdml.models import build_model
 from ewdml.optim import FlatSGD
 from ewdml.parallel import Comm, FlatModel, GradientExchange
 
-ROOT = "/root/reference/data"
-pytestmark = [pytest.mark.slow,
-              pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "MNIST", "raw",
-                                                                 "t10k-images-idx3-ubyte.gz")),
-                                 reason="reference MNIST test images not mounted")]
+from tests.golden_data import mnist_root
+
+pytestmark = pytest.mark.slow
 
 
 # floors: the report's lowest LeNet accuracy (Method 5, 96.5 %) for every accuracy-preserving
@@ -31,7 +27,7 @@ pytestmark = [pytest.mark.slow,
                                                       ("qsgd", False, "l2", 0.01, 96.5)])
 def test_lenet_real_mnist_holdout(kind, ef, norm, ratio, floor):
     torch.manual_seed(0)
-    x, y = _mnist(ROOT, train=False)
+    x, y = _mnist(mnist_root(), train=False)
     info = {"mean": DATASETS["mnist"][2], "std": DATASETS["mnist"][3]}
     tr = DeviceLoader(x[:9000], y[:9000], info, 64, seed=1)
     te = DeviceLoader(x[9000:], y[9000:], info, 1000, shuffle=False, drop_last=False)

@@ -8,10 +8,12 @@ import torch
 from ewdml.data import DeviceLoader, augment_cifar, load_dataset
 from ewdml.data.datasets import DATASETS, _cifar_bin, read_idx
 
-REF_LABELS = "/root/reference/PyTorch-parameter-server/mnist_data/MNIST/raw/train-labels-idx1-ubyte"
+from tests.golden_data import MNIST_RAW
+
+# the reference's MNIST label files (tests/golden/mnist; gzip, which the reader opens itself)
+REF_LABELS = os.path.join(MNIST_RAW, "train-labels-idx1-ubyte")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LABELS), reason="reference checkout not mounted")
 def test_idx_reader_on_reference_labels():
     y = read_idx(REF_LABELS)
     assert y.shape == (60000,)

@@ -1,7 +1,7 @@
 """Measured reproduction of the report's Methods 1-6 (``Report.zip:main.tex:80-119``).
 
 Every method runs the real ``Trainer`` on the reference's own data (the MNIST t10k images shipped
-in its checkout, ``tests/fixtures/mnist``: 9K train / 1K held out) in its own setup: one parameter
+in its checkout, ``tests/golden/mnist``: 9K train / 1K held out) in its own setup: one parameter
 server + two workers over Gloo (``src/run_pytorch_single.sh``), batch 64 per worker, SGD with
 momentum 0.9.  Methods 1-5 use ``--topology ps`` (1, 2 pull weights; 3-5 pull gradients); Method 6 is
 Method 5 with local SGD, a sync every 20 steps and best-worker selection, over two ranks (it has no
@@ -35,7 +35,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MNIST = os.path.join(ROOT, "tests", "fixtures", "mnist")
+from tests.golden_data import mnist_root  # noqa: E402 - needs ROOT on the path
+
 MiB = float(1 << 20)
 PUBLISHED_MIB = [6.56, 4.1, 6.56, 1.64, 1.312, 0.066]  # LeNet, BASELINE.md / Comm Cost.png
 PUBLISHED_TOP1 = [98, 97, 97, 98, 96.5, 97]  # LeNet, Top1 Accuracy.png
@@ -56,7 +57,7 @@ def _free_port():
 
 
 def _flags(method, ratio, steps, device="cpu"):
-    f = ["--network", "LeNet", "--dataset", "MNIST", "--data-dir", MNIST,
+    f = ["--network", "LeNet", "--dataset", "MNIST", "--data-dir", mnist_root(),
          "--holdout-from-test", "1000", "--batch-size", "64", "--lr", "0.01", "--momentum", "0.9",
          "--eval-freq", "0", "--quiet", "--device", device, "--amp", "none", "--method",
          str(method), "--topk-ratio", str(ratio), "--qsgd-norm", "l2", "--test-batch-size",
@@ -233,7 +234,7 @@ def main(argv=None):
             "server + two workers (Methods 1-5, `--topology ps`), batch 64 per worker, SGD with "
             "momentum 0.9, lr 0.01; Method 6 = Method 5 + local SGD (sync every 20 steps) + "
             "best-worker selection on two ranks.  Data: the reference's MNIST t10k images "
-            "(`tests/fixtures/mnist`), 9,000 for training, the last 1,000 held out.  Top-k ratio "
+            "(`tests/golden/mnist`), 9,000 for training, the last 1,000 held out.  Top-k ratio "
             f"K = {a.ratio} (the report's).  Bytes are the exchanges' measured wire counters: per "
             "iteration, summed over the two workers, push + pull (the report's metric); the "
             "static column is `tools/methods_table.py` from the packed layouts.  The report trained "
