@@ -7,6 +7,8 @@
   * ``qsgd``  -- dense stochastic quantisation to int8/int4 (Method 4)
   * ``topk``  -- top-k sparsification, fp32 values (``TopKCompressor``)
   * ``topk_qsgd`` -- top-k then QSGD (Method 5); the flagship codec
+  * ``sign``  -- scaled sign, 1 bit per element plus one fp32 scale per 8192-element chunk
+    (1-bit SGD / EF-signSGD); meant to run with error feedback, which the all-gather exchange keeps
 
 Device tensors go through the HIP kernels (``ops``); CPU tensors through the torch oracle.  On a
 GPU box a missing extension raises instead of silently falling back.
@@ -24,7 +26,7 @@ from . import oracle
 from .plan import BucketPlan, Layout
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd")
+KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign")
 
 
 class Codec:
@@ -32,7 +34,7 @@ class Codec:
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
-        if bits not in (4, 8):
+        if kind != "sign" and bits not in (4, 8):  # the sign codec has neither bits nor levels
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -65,6 +67,8 @@ class Codec:
             return f"qsgd{self.bits}b(s={self.levels},{self.norm})"
         if self.kind == "topk":
             return f"topk{self.ratio:g}"
+        if self.kind == "sign":
+            return "sign1b"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -132,6 +136,8 @@ class Codec:
         (``ops.topk_encode``), so no decode launch follows."""
         if dgc is not None and (resid is None or self.kind not in ("topk", "topk_qsgd")):
             raise ValueError("momentum correction needs a top-k codec and a residual")
+        if self.kind == "sign" and apply is not None:
+            raise ValueError("the sign codec has no encode-side apply")
         plan, lay = self.plans[b], self.layouts[b]
         key = self.key(step, rank)
         on_dev = (grad[0] if isinstance(grad, (list, tuple)) else grad).is_cuda
@@ -140,7 +146,9 @@ class Codec:
         if on_dev and not _FORCE_ORACLE:
             if ef21:
                 raise NotImplementedError("EF21 encode on the GPU: run with EWDML_ORACLE=1")
-            if self.kind == "qsgd":
+            if self.kind == "sign":
+                ops.sign_encode(self.dplans[b], grad, payload, lay, resid)
+            elif self.kind == "qsgd":
                 ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
                                 resid, key_tensor)
             else:
@@ -151,7 +159,9 @@ class Codec:
             raise ValueError("the encode-side apply runs on the GPU codec only")
         if isinstance(grad, (list, tuple)):
             raise TypeError("CPU encode takes the bucket's flat gradient view")
-        if self.kind == "qsgd":
+        if self.kind == "sign":
+            out = oracle.encode_sign(grad, plan, lay, resid)
+        elif self.kind == "qsgd":
             out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
         else:
             out = oracle.encode_topk(grad, plan, lay, self.levels, self.norm, key, resid, dgc,
@@ -162,6 +172,9 @@ class Codec:
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
+            if self.kind == "sign":
+                ops.sign_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
+                return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, grad_out=out, grad_scale=scale)
             return
@@ -178,12 +191,16 @@ class Codec:
             raise ValueError("a momentum step needs the momentum buffer")
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
+            kw = dict(param=param, mom=mom, grad_out=grad_out, lr=hp["lr"],
+                      momentum=hp["momentum"], dampening=hp["dampening"],
+                      weight_decay=hp["weight_decay"], grad_scale=scale, nesterov=hp["nesterov"],
+                      first=first, shadow=shadow, key_state=key_state, key_seed=self.seed,
+                      key_rank=rank, lr_tensor=hp.get("lr_t"))
+            if self.kind == "sign":
+                ops.sign_decode_apply(self.dplans[b], recv, lay, **kw)
+                return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
-            fn(self.dplans[b], recv, lay, self.levels, param=param, mom=mom, grad_out=grad_out,
-               lr=hp["lr"], momentum=hp["momentum"], dampening=hp["dampening"],
-               weight_decay=hp["weight_decay"], grad_scale=scale, nesterov=hp["nesterov"],
-               first=first, shadow=shadow, key_state=key_state, key_seed=self.seed,
-               key_rank=rank, lr_tensor=hp.get("lr_t"))
+            fn(self.dplans[b], recv, lay, self.levels, **kw)
             return
         g = oracle.decode_sum(recv, plan, lay, self.levels, scale)
         if grad_out is not None:

@@ -15,6 +15,10 @@ Reference semantics being reproduced:
   * Top-k (``Compresssor/TopK.py:5-35``): k = max(1, int(numel*ratio)) largest |g| per tensor.  Ties
     at the threshold are broken by lowest index (torch.topk leaves them unspecified), entries are
     stored sorted by index.
+  * Scaled sign with error feedback (no reference counterpart; 1-bit SGD, Seide et al. 2014, and
+    EF-signSGD, Karimireddy et al. 2019): per 8192-element chunk the mean |g + residual| and one
+    bit per element.  The chunk sum is written in the kernel's own order (``_sign_chunk_sums``),
+    so scales, bits and residuals are bitwise the kernel's.
 """
 import numpy as np
 import torch
@@ -235,6 +239,91 @@ def encode_qsgd(g: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int, 
 
 
 # ---------------------------------------------------------------------------------------------
+# scaled sign with error feedback (1-bit SGD / EF-signSGD), one scale per chunk
+# ---------------------------------------------------------------------------------------------
+_SIGN_THREADS = 256  # the kernel's block: thread t owns elements 4t .. 4t + 3 of each 1024-slab
+
+
+def _sign_chunk_sums(a: torch.Tensor) -> torch.Tensor:
+    """fp32 sums of the rows of ``a`` (fp32 [C, CHUNK], non-negative, padding 0) in the order of
+    ``ops/csrc/sign_codec.hip``, every add rounded to fp32:
+
+    * thread t (0..255) adds, from 0, the elements ``u * 1024 + 4 t + j`` for u = 0..7 outer and
+      j = 0..3 inner;
+    * per wave of 64 threads the shuffle-down tree: ``x[:32] += x[32:]``, ``x[:16] += x[16:32]``,
+      ..., ``x[:1] += x[1:2]``;
+    * then ``(((0 + w0) + w1) + w2) + w3`` over the four waves."""
+    C = a.shape[0]
+    x = a.reshape(C, CHUNK // (4 * _SIGN_THREADS), _SIGN_THREADS, 4)
+    s = torch.zeros(C, _SIGN_THREADS, dtype=torch.float32, device=a.device)
+    for u in range(x.shape[1]):
+        for j in range(4):
+            s = s + x[:, u, :, j]
+    w = s.reshape(C, _SIGN_THREADS // 64, 64)
+    d = 32
+    while d:
+        w = w[:, :, :d] + w[:, :, d:2 * d]
+        d >>= 1
+    tot = torch.zeros(C, dtype=torch.float32, device=a.device)
+    for i in range(w.shape[1]):
+        tot = tot + w[:, i, 0]
+    return tot
+
+
+def _sign_gather(plan: BucketPlan, device):
+    """(index [C, CHUNK] into the bucket, valid mask, fp32 chunk lengths)."""
+    start = torch.tensor(plan.chunk_start, dtype=torch.int64, device=device)
+    ln = torch.tensor(plan.chunk_len, dtype=torch.int64, device=device)
+    ar = torch.arange(CHUNK, dtype=torch.int64, device=device)
+    valid = ar[None, :] < ln[:, None]
+    pos = torch.where(valid, start[:, None] + ar[None, :], torch.zeros_like(ar)[None, :])
+    return pos, valid, ln.to(torch.float32)
+
+
+def encode_sign(g: torch.Tensor, plan: BucketPlan, layout: Layout,
+                residual: torch.Tensor = None) -> torch.Tensor:
+    """Scaled sign of one bucket -> uint8 payload (``scales f32[C] | bits u32[256 C]``).
+
+    Per chunk: ``e = g + residual`` (``e = g`` without error feedback), ``scale = sum|e| / len``
+    (the fixed-order fp32 sum of :func:`_sign_chunk_sums`, one fp32 divide), ``bit = e < 0``
+    (+0, -0 and NaN give 0), decoded value ``d = -scale if bit else scale``, and ``residual = e -
+    d``.  Bits past the chunk's length are 0."""
+    if layout.kind != "sign":
+        raise ValueError(f"encode_sign given a {layout.kind!r} layout")
+    g = g.to(torch.float32)
+    e = g + residual if residual is not None else g
+    C = plan.num_chunks
+    pos, valid, lens = _sign_gather(plan, g.device)
+    E = torch.where(valid, e[pos], torch.zeros((), dtype=torch.float32, device=g.device))
+    scale = _sign_chunk_sums(E.abs()) / lens
+    neg = E < 0
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=g.device)
+    _section(out, layout.scales, C, torch.float32).copy_(scale)
+    sh = torch.arange(32, dtype=torch.int64, device=g.device)
+    words = (neg.reshape(C, CHUNK // 32, 32).to(torch.int64) << sh).sum(-1)
+    words = ((words + (1 << 31)) % (1 << 32)) - (1 << 31)  # uint32 bits as int32
+    _section(out, layout.codes, C * (CHUNK // 32), torch.int32).copy_(
+        words.to(torch.int32).flatten())
+    if residual is not None:
+        d = torch.where(neg, -scale[:, None], scale[:, None])
+        residual[pos[valid]] = (E - d)[valid]
+    return out
+
+
+def _sign_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    C = plan.num_chunks
+    scale = _section(pay, layout.scales, C, torch.float32)
+    words = _section(pay, layout.codes, C * (CHUNK // 32), torch.int32).to(torch.int64)
+    sh = torch.arange(32, dtype=torch.int64, device=pay.device)
+    neg = ((words[:, None] >> sh) & 1).reshape(C, CHUNK).bool()
+    d = torch.where(neg, -scale[:, None], scale[:, None])
+    pos, valid, _ = _sign_gather(plan, pay.device)
+    out = torch.zeros(plan.length, dtype=torch.float32, device=pay.device)
+    out[pos[valid]] = d[valid]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # decode: sum over ranks (in rank order) of the dequantised payloads, times ``scale``
 # ---------------------------------------------------------------------------------------------
 def _decoded_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int):
@@ -281,6 +370,8 @@ def decode_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int
         if layout.kind in ("topk", "topk_qsgd"):
             pos, vals = _decoded_entries(recv[r], plan, layout, levels)
             acc.index_add_(0, pos, vals)
+        elif layout.kind == "sign":
+            acc += _sign_decoded(recv[r], plan, layout)
         else:
             acc += _dense_decoded(recv[r], plan, layout, levels)
     return acc * torch.tensor(scale, dtype=torch.float32)

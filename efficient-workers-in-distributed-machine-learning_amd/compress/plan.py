@@ -22,6 +22,8 @@ exchange is a fixed-size all-gather with no size handshake):
 ``topk_qsgd``: scales f32[T] | counts u16[C] | idx u16[K] | codes i8[K] (bits=8) or nibbles[K/2]
 ``topk``     : scales f32[T] (unused, kept for a uniform header) | counts | idx | values f32[K]
 ``qsgd``     : scales f32[T] | codes i8[D'] or nibbles  (dense; D' = numels padded to 16 per tensor)
+``sign``     : scales f32[C] | bits u32[256 C]  (one scale per chunk; chunk c owns words [256 c,
+               256 c + 256), element i of the chunk is bit i & 31 of word i >> 5, padding bits 0)
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -202,6 +204,12 @@ class Layout:
             counts = idx = off
             codes = off
             off += plan.total_codes if bits == 8 else plan.total_codes // 2
+        elif kind == "sign":
+            # one scale per chunk, then the chunks' bit words (`codes` is their byte offset)
+            bits = 1
+            off = _align(4 * C)
+            counts = idx = codes = off
+            off += 4 * BM_WORDS * C
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)

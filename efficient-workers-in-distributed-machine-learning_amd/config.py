@@ -58,7 +58,7 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    compress: str = "topk_qsgd"  # none | fp16 | bf16 | qsgd | topk | topk_qsgd
+    compress: str = "topk_qsgd"  # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
     qsgd_levels: int = 127
@@ -73,7 +73,8 @@ class Config:
     sync_mode_default: bool = True  # --sync-mode not given (--method 6 then selects 'model')
     select_best: bool = False  # method 6: adopt the weights of the best-accuracy rank at sync
     # None (auto): on for the top-k codecs -- top-k at 1 % without error feedback trains 10-80x
-    # slower than dense (profiles/validation/ef_stability_r03.md) -- off otherwise;
+    # slower than dense (profiles/validation/ef_stability_r03.md) -- and for the sign codec
+    # (scaled sign is biased without its residual), off otherwise;
     # --no-error-feedback gives the reference's Methods 5/6 as published (no residual)
     error_feedback: Optional[bool] = None
     # dgc: momentum correction + momentum factor masking (the sender runs the momentum before
@@ -179,8 +180,14 @@ class Config:
             # only the all-gather exchange keeps a residual (parallel/engine.py
             # GradientExchange); the parameter-server / sharded exchanges have none, so their
             # top-k runs keep the reference's schedule (no EF warm-up) and record no EF
-            c.error_feedback = (c.compress in ("topk", "topk_qsgd")
+            c.error_feedback = (c.compress in ("topk", "topk_qsgd", "sign")
                                 and c.topology == "allgather")
+        if c.compress == "sign" and (c.topology != "allgather" or c.sync_every > 1
+                                     or c.select_best):
+            # scaled sign is biased without error feedback, and only GradientExchange keeps one
+            raise ValueError("--compress sign needs the all-gather exchange's residual: it does "
+                             "not run with --topology ps / sharded, --sync-every > 1 or "
+                             "--select-best (those exchanges keep no error feedback)")
         if c.ef_mode == "ef21" and c.error_feedback and c.device != "cpu" and not c.no_cuda:
             import os
 
@@ -242,7 +249,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # exchange
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
-      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd"])
+      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign"])
     a("--topk-ratio", type=float, default=d.topk_ratio)
     a("--topk-dense-below", type=int, default=d.topk_dense_below)
     a("--qsgd-levels", type=int, default=d.qsgd_levels)

@@ -390,6 +390,62 @@ def qsgd_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
 
 
+def _check_sign_layout(dp, layout):
+    C = dp.plan.num_chunks
+    if layout.kind != "sign":
+        raise ValueError(f"sign codec given a {layout.kind!r} layout")
+    if (layout.scales % 16 or layout.codes % 16 or layout.codes < layout.scales + 4 * C
+            or layout.nbytes < layout.codes + 1024 * C):
+        raise ValueError("sign layout does not match the bucket plan")
+
+
+def sign_encode(dp: DevicePlan, grad, payload, layout, resid=None):
+    """Scaled sign of one bucket (``csrc/sign_codec.hip``): per chunk the mean ``|e|`` and one bit
+    per element, ``e = grad + resid`` with ``resid`` (error feedback) overwritten by what was not
+    sent.  One launch, no scratch; bitwise ``compress/oracle.py encode_sign``."""
+    C = require()
+    ptrs, mask = grad_pointers(dp, grad)
+    _check_sign_layout(dp, layout)
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+    if resid is not None:
+        _check_bucket(dp, resid, "resid")
+    C.sign_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
+                  dp.plan.num_tensors, dp.plan.num_chunks, layout.scales, layout.codes, _stream())
+
+
+def sign_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
+                      momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
+                      nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
+                      key_rank=0, lr_tensor=None):
+    """``grad_out = grad_scale * sum over the rows of recv (rank order) of +/- scale`` and / or the
+    fused SGD step on ``param`` (``mom`` None: a step without momentum)."""
+    C = require()
+    _check_sign_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or recv.shape[0] < 1:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+    apply = param is not None
+    if apply:
+        _check_bucket(dp, param, "param")
+        if mom is not None:
+            _check_bucket(dp, mom, "mom")
+        elif momentum != 0.0 or nesterov:
+            raise ValueError("a momentum step needs the momentum buffer")
+    if grad_out is not None:
+        _check_bucket(dp, grad_out, "grad_out")
+    if not apply and grad_out is None:
+        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    _check_shadow(dp, shadow)
+    C.sign_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
+                        dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param), _ptr(mom),
+                        _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
+                        grad_scale, int(nesterov), int(first), int(apply), _stream(),
+                        _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
+                        _lrp(lr_tensor))
+
+
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 

@@ -90,6 +90,30 @@ struct QsgdDecodeArgs {
   uintptr_t lr_ptr;
 };
 
+// scaled sign with error feedback (sign_codec.hip): scales f32[C] | bits u32[256 * C]
+struct SignEncodeArgs {
+  const uintptr_t* grad_ptrs;
+  int n_grad_ptrs;
+  const uint32_t* bf16_mask;
+  int n_bf16_mask;
+  uintptr_t resid, chunks, payload, stream;  // resid 0: no error feedback
+  long long payload_bytes;
+  int num_tensors, num_chunks;
+  int scales_off, bits_off;
+};
+
+struct SignDecodeArgs {
+  uintptr_t recv, chunks, param, mom, grad_out, shadow, stream;  // mom 0: a step without momentum
+  long long stride;
+  int nranks, num_chunks;
+  int scales_off, bits_off;
+  float lr, momentum, dampening, weight_decay, grad_scale;
+  int nesterov, first, apply;
+  uintptr_t key_state;  // see TopkDecodeArgs
+  uint32_t key_seed, key_rank;
+  uintptr_t lr_ptr;
+};
+
 struct SgdFlatArgs {
   uintptr_t param, mom, grad, shadow, stream;
   long long n;
@@ -127,6 +151,9 @@ void ew_topk_decode_apply(const TopkDecodeArgs& a);
 size_t ew_qsgd_scratch_bytes(int num_tensors, int num_chunks);
 void ew_qsgd_encode(const QsgdEncodeArgs& a);
 void ew_qsgd_decode_apply(const QsgdDecodeArgs& a);
+
+void ew_sign_encode(const SignEncodeArgs& a);
+void ew_sign_decode_apply(const SignDecodeArgs& a);
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

@@ -731,7 +731,8 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
     Returns ``{"mode", "splits", "bucket_bytes", "wire_bytes", "reason"}`` (+ ``predicted_ms``)."""
     from .step_model import overlap_splits, predict, profile_for
 
-    per_elem = {"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0}.get(codec_kind)
+    per_elem = {"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
+                "sign": 1.0 / 8.0}.get(codec_kind)
     payload = grad_numel * (per_elem or 0.0)
     # top-k payload per rank (estimate): k entries of one code byte (4-bit: half) + a 2-byte index
     pb = payload if per_elem is not None else grad_numel * topk_ratio * (2.0 + max(bits, 4) / 8.0)

@@ -147,6 +147,11 @@ class Compression:
     def topk_qsgd(ratio: float = 0.01, levels: int = 127, bits: int = 8, norm: str = "max"):
         return Codec("topk_qsgd", ratio=ratio, levels=levels, bits=bits, norm=norm)
 
+    @staticmethod
+    def sign():
+        """Scaled sign, 1 bit per element; the optimizer wrapper keeps its error feedback."""
+        return Codec("sign")
+
 
 def _as_codec(compression) -> Codec:
     if isinstance(compression, Codec):
@@ -245,6 +250,8 @@ class _DistributedOptimizer:
         codec = Codec("none") if op == Adasum else _as_codec(compression)
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
+                                         # scaled sign is biased without its residual
+                                         error_feedback=codec.kind == "sign",
                                          predivide=gradient_predivide_factor)
         self._synced = False
         self.exchange.begin()
