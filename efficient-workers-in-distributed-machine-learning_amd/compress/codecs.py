@@ -168,6 +168,48 @@ class Codec:
                                      ef21)
         payload[:lay.nbytes].copy_(out)
 
+    def encode_momentum(self, b: int, grad, payload: torch.Tensor, resid: torch.Tensor,
+                        exp_avg: torch.Tensor, beta1: float, weight_decay: float = 0.0,
+                        param: torch.Tensor = None):
+        """1-bit Adam's compressed stage: the sign encode (error feedback always on) of ``exp_avg *
+        beta1 + (1 - beta1) * (grad + weight_decay * param)`` of bucket ``b``; ``exp_avg`` and
+        ``param`` are that bucket's views and are only read."""
+        if self.kind != "sign":
+            raise ValueError("the momentum encode needs the sign codec")
+        if resid is None:
+            raise ValueError("the momentum encode needs the residual (error feedback)")
+        plan, lay = self.plans[b], self.layouts[b]
+        on_dev = (grad[0] if isinstance(grad, (list, tuple)) else grad).is_cuda
+        if on_dev and not _FORCE_ORACLE:
+            ops.sign_encode_momentum(self.dplans[b], grad, payload, lay, resid, exp_avg, beta1,
+                                     weight_decay, param)
+            return
+        if isinstance(grad, (list, tuple)):
+            raise TypeError("CPU encode takes the bucket's flat gradient view")
+        out = oracle.encode_sign_momentum(grad, plan, lay, resid, exp_avg, beta1, weight_decay,
+                                          param)
+        payload[:lay.nbytes].copy_(out)
+
+    def decode_apply_onebit(self, b: int, recv: torch.Tensor, inv_n: float, param: torch.Tensor,
+                            exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,
+                            shadow=None, key_state=None, rank: int = 0):
+        """1-bit Adam's fused decode -> ``exp_avg = mean`` -> frozen-variance step of bucket ``b``
+        (one kernel on the GPU).  ``hp``: ``FlatOnebitAdam.hparams()`` (``lr_step`` of this step;
+        on the GPU ``step_t`` / ``lr_t`` make the kernel derive it)."""
+        if self.kind != "sign":
+            raise ValueError("the 1-bit Adam step needs the sign codec")
+        plan, lay = self.plans[b], self.layouts[b]
+        if recv.is_cuda and not _FORCE_ORACLE:
+            b1, b2 = hp["betas"]
+            ops.sign_decode_onebit(self.dplans[b], recv, lay, param, exp_avg, exp_avg_sq, inv_n,
+                                   hp["lr_step"], hp["eps"], b1, b2, hp["freeze_step"],
+                                   shadow=shadow, step=hp.get("step_t"), lr=hp["lr"],
+                                   lr_tensor=hp.get("lr_t"), key_state=key_state,
+                                   key_seed=self.seed, key_rank=rank)
+            return
+        oracle.onebit_adam_apply(recv, plan, lay, param, exp_avg, exp_avg_sq, inv_n,
+                                 hp["lr_step"], hp["eps"])
+
     def decode(self, b: int, recv: torch.Tensor, out: torch.Tensor, scale: float):
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""
         plan, lay = self.plans[b], self.layouts[b]

@@ -19,6 +19,9 @@ Reference semantics being reproduced:
     EF-signSGD, Karimireddy et al. 2019): per 8192-element chunk the mean |g + residual| and one
     bit per element.  The chunk sum is written in the kernel's own order (``_sign_chunk_sums``),
     so scales, bits and residuals are bitwise the kernel's.
+  * 1-bit Adam's compressed stage (no reference counterpart; Tang et al., ICML 2021):
+    ``encode_sign_momentum`` (the sign encode of the error-compensated momentum candidate) and
+    ``onebit_adam_apply`` (averaged momentum, frozen-variance step), bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -308,6 +311,63 @@ def encode_sign(g: torch.Tensor, plan: BucketPlan, layout: Layout,
         d = torch.where(neg, -scale[:, None], scale[:, None])
         residual[pos[valid]] = (E - d)[valid]
     return out
+
+
+def encode_sign_momentum(g: torch.Tensor, plan: BucketPlan, layout: Layout,
+                         residual: torch.Tensor, exp_avg: torch.Tensor, beta1: float,
+                         weight_decay: float = 0.0, param: torch.Tensor = None) -> torch.Tensor:
+    """1-bit Adam's compressed stage (Tang et al., ICML 2021), sender side: :func:`encode_sign`
+    with error feedback of the momentum candidate (every product and sum rounded to fp32
+    separately, ``1 - beta1`` formed in fp32, as the kernel does)::
+
+        g' = g + wd * p                     (only when wd != 0)
+        u  = m * beta1 + (1 - beta1) * g'
+        e  = u + residual
+
+    ``exp_avg`` (m, the same on every rank), ``param`` and ``g`` are only read."""
+    if residual is None:
+        raise ValueError("the momentum encode always runs with error feedback")
+    f32 = np.float32
+    g = g.to(torch.float32)
+    if weight_decay != 0.0:
+        g = g + param * float(f32(weight_decay))
+    b1 = f32(beta1)
+    u = exp_avg * float(b1) + g * float(f32(1.0) - b1)
+    return encode_sign(u, plan, layout, residual)
+
+
+def onebit_adam_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, param: torch.Tensor,
+                      exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, inv_n: float,
+                      lr_step: float, eps: float) -> None:
+    """1-bit Adam's compressed stage, receiver side, on the bucket views ``param`` / ``exp_avg`` /
+    ``exp_avg_sq``: ``m = inv_n * sum_r decode(r)`` (rank order, from 0) for every element of
+    every tensor, then ``p -= lr_step * (m / (sqrt(v) + eps))`` where the frozen ``v > 0`` -- a
+    coordinate that never saw a gradient keeps its parameter.  ``exp_avg_sq`` is only read, and
+    positions between tensors are not touched."""
+    f32 = np.float32
+    m_all = decode_sum(recv, plan, layout, 0, inv_n)
+    for off, n in zip(plan.offsets, plan.numels):
+        sl = slice(off, off + n)
+        m, v, p = m_all[sl], exp_avg_sq[sl], param[sl]
+        exp_avg[sl] = m
+        # the correctly rounded fp32 square root (the kernel's sqrtf): through fp64, whose 53
+        # bits make the second rounding harmless -- torch's vectorised CPU fp32 sqrt is not
+        # correctly rounded on every build (1 ulp low on ~0.5 % of inputs with AVX-512)
+        root = v.to(torch.float64).sqrt().to(torch.float32)
+        step = (m / (root + float(f32(eps)))) * float(f32(lr_step))
+        param[sl] = torch.where(v > 0, p - step, p)
+
+
+def onebit_lr_step(lr: float, beta1: float, beta2: float, step: int, freeze_step: int) -> float:
+    """``lr * sqrt(1 - beta2^freeze_step) / (1 - beta1^step)``: the variance's bias correction
+    stays at its value of the freeze step, the momentum's follows the 1-based ``step``.  In
+    double precision with the betas rounded to fp32 first, as the kernel holds them (at a small
+    ``freeze_step`` 1 - beta2^freeze_step magnifies beta2's rounding a thousandfold), so the
+    host value and the one the kernel derives from the device step counter agree to fp32."""
+    import math
+
+    b1, b2 = float(np.float32(beta1)), float(np.float32(beta2))
+    return lr * math.sqrt(1 - b2 ** freeze_step) / (1 - b1 ** step)
 
 
 def _sign_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:

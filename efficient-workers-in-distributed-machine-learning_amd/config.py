@@ -96,7 +96,11 @@ class Config:
     predivide: float = 1.0  # Horovod gradient_predivide_factor
     sync_bn: bool = False  # broadcast BN running stats from rank 0 at every checkpoint/eval
     # ---- optimizer -------------------------------------------------------------------------------
-    optimizer: str = "sgd"
+    optimizer: str = "sgd"  # sgd | adam | amsgrad | onebit_adam (1-bit Adam: optim/flat.py)
+    adam_eps: float = 1e-8  # epsilon of adam / amsgrad / onebit_adam
+    # onebit_adam: dense Adam steps before the variance is frozen and the sign-compressed
+    # momentum exchange starts (required, >= 1)
+    onebit_warmup_steps: Optional[int] = None
     weight_decay: float = 0.0
     dampening: float = 0.0
     nesterov: bool = False
@@ -188,6 +192,24 @@ class Config:
             raise ValueError("--compress sign needs the all-gather exchange's residual: it does "
                              "not run with --topology ps / sharded, --sync-every > 1 or "
                              "--select-best (those exchanges keep no error feedback)")
+        if c.optimizer == "onebit_adam":
+            # the compressed stage is the sign codec's all-gather with its residual; every option
+            # that changes what is exchanged, or that scales it, breaks the momentum's linearity
+            why = None
+            if c.onebit_warmup_steps is None or int(c.onebit_warmup_steps) < 1:
+                why = "needs --onebit-warmup-steps N >= 1 (the dense Adam steps before the freeze)"
+            elif c.compress != "sign":
+                why = "exchanges sign-compressed momentum: it needs --compress sign"
+            elif not c.error_feedback:
+                why = ("compresses the error-compensated momentum: it does not run with "
+                       "--no-error-feedback")
+            elif c.predivide != 1.0:
+                why = ("averages decoded momenta with 1/N: it does not run with --predivide "
+                       "other than 1")
+            if why is not None:
+                raise ValueError("--optimizer onebit_adam " + why)
+        elif c.onebit_warmup_steps is not None:
+            raise ValueError("--onebit-warmup-steps belongs to --optimizer onebit_adam")
         if c.ef_mode == "ef21" and c.error_feedback and c.device != "cpu" and not c.no_cuda:
             import os
 
@@ -274,7 +296,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--predivide", type=float, default=d.predivide)
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
-    a("--optimizer", type=str, default=d.optimizer, choices=["sgd", "adam", "amsgrad"])
+    a("--optimizer", type=str, default=d.optimizer,
+      choices=["sgd", "adam", "amsgrad", "onebit_adam"])
+    a("--adam-eps", type=float, default=d.adam_eps)
+    a("--onebit-warmup-steps", type=int, default=None)
     a("--weight-decay", type=float, default=d.weight_decay)
     a("--dampening", type=float, default=d.dampening)
     a("--nesterov", action="store_true", default=False)

@@ -446,6 +446,63 @@ def sign_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_o
                         _lrp(lr_tensor))
 
 
+def sign_encode_momentum(dp: DevicePlan, grad, payload, layout, resid, exp_avg, beta1,
+                         weight_decay=0.0, param=None):
+    """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad
+    + weight_decay * param) + resid``.  ``exp_avg``, ``param`` and the gradients are only read;
+    ``resid`` (required) is overwritten.  Bitwise ``compress/oracle.py encode_sign_momentum``."""
+    C = require()
+    ptrs, mask = grad_pointers(dp, grad)
+    _check_sign_layout(dp, layout)
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+    if resid is None or exp_avg is None:
+        raise ValueError("the momentum encode needs the residual and exp_avg")
+    _check_bucket(dp, resid, "resid")
+    _check_bucket(dp, exp_avg, "exp_avg")
+    if weight_decay != 0.0:
+        if param is None:
+            raise ValueError("weight decay needs the parameters")
+        _check_bucket(dp, param, "param")
+    else:
+        param = None
+    C.sign_encode_momentum(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
+                           dp.plan.num_tensors, dp.plan.num_chunks, layout.scales, layout.codes,
+                           _ptr(exp_avg), _ptr(param), float(beta1), float(weight_decay),
+                           _stream())
+
+
+def sign_decode_onebit(dp: DevicePlan, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_step,
+                       eps, beta1=0.9, beta2=0.999, freeze_step=1, shadow=None, step=None, lr=0.0,
+                       lr_tensor=None, key_state=None, key_seed=0, key_rank=0):
+    """1-bit Adam's fused receive side: ``exp_avg = inv_n * sum over the rows of recv (rank order)
+    of +/- scale``, then ``param -= lr_step * exp_avg / (sqrt(exp_avg_sq) + eps)`` where
+    ``exp_avg_sq > 0`` (read only).  ``step`` (int32 device tensor, optional): the kernel reads t =
+    step + 1 and derives ``lr_step = lr * sqrt(1 - beta2^freeze_step) / (1 - beta1^t)`` on the
+    device (``lr_step`` is then ignored)."""
+    C = require()
+    _check_sign_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or recv.shape[0] < 1:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+    for t, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if t is None:
+            raise ValueError(f"the 1-bit Adam step needs {nm}")
+        _check_bucket(dp, t, nm)
+    if int(freeze_step) < 1:
+        raise ValueError("freeze_step must be >= 1")
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    _check_shadow(dp, shadow)
+    C.sign_decode_onebit(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
+                         dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param),
+                         _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(shadow), float(lr_step),
+                         float(inv_n), float(eps), float(beta1), float(beta2), int(freeze_step),
+                         _ptr(step), float(lr), _lrp(lr_tensor), _stream(), _keyp(key_state),
+                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF)
+
+
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 

@@ -229,6 +229,67 @@ PYBIND11_MODULE(_C, m) {
           ew_sign_encode(a);
         });
 
+  m.def("sign_encode_momentum",
+        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
+           uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
+           int bits_off, uintptr_t exp_avg, uintptr_t param, float beta1, float weight_decay,
+           uintptr_t stream) {
+          SignEncodeArgs a{};
+          a.grad_ptrs = grads.data();
+          a.n_grad_ptrs = (int)grads.size();
+          a.bf16_mask = mask.data();
+          a.n_bf16_mask = (int)mask.size();
+          a.resid = resid;
+          a.chunks = chunks;
+          a.payload = payload;
+          a.stream = stream;
+          a.payload_bytes = payload_bytes;
+          a.num_tensors = T;
+          a.num_chunks = C;
+          a.scales_off = scales_off;
+          a.bits_off = bits_off;
+          if (!exp_avg) throw std::runtime_error("ewdml sign: the momentum encode needs exp_avg");
+          a.mom_exp_avg = exp_avg;
+          a.mom_param = param;
+          a.mom_beta1 = beta1;
+          a.mom_wd = weight_decay;
+          ew_sign_encode(a);
+        });
+
+  m.def("sign_decode_onebit",
+        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
+           int bits_off, uintptr_t param, uintptr_t exp_avg, uintptr_t exp_avg_sq,
+           uintptr_t shadow, float lr_step, float inv_n, float eps, float beta1, float beta2,
+           int freeze_step, uintptr_t step, double lr, uintptr_t lr_ptr, uintptr_t stream,
+           uintptr_t key_state, uint32_t key_seed, uint32_t key_rank) {
+          SignOnebitArgs a{};
+          a.recv = recv;
+          a.chunks = chunks;
+          a.param = param;
+          a.exp_avg = exp_avg;
+          a.exp_avg_sq = exp_avg_sq;
+          a.shadow = shadow;
+          a.stream = stream;
+          a.stride = stride;
+          a.nranks = nranks;
+          a.num_chunks = C;
+          a.scales_off = scales_off;
+          a.bits_off = bits_off;
+          a.lr_step = lr_step;
+          a.inv_n = inv_n;
+          a.eps = eps;
+          a.beta1 = beta1;
+          a.beta2 = beta2;
+          a.freeze_step = freeze_step;
+          a.step = step;
+          a.lr = lr;
+          a.lr_ptr = lr_ptr;
+          a.key_state = key_state;
+          a.key_seed = key_seed;
+          a.key_rank = key_rank;
+          ew_sign_decode_onebit(a);
+        });
+
   m.def("sign_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
            int bits_off, uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,

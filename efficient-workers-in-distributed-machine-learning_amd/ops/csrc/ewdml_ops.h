@@ -100,6 +100,25 @@ struct SignEncodeArgs {
   long long payload_bytes;
   int num_tensors, num_chunks;
   int scales_off, bits_off;
+  // 1-bit Adam's momentum encode (mom_exp_avg != 0; needs resid): the compressed vector is
+  // exp_avg * beta1 + (1 - beta1) * (g + wd * param) + resid; exp_avg and param are only read
+  uintptr_t mom_exp_avg, mom_param;
+  float mom_beta1, mom_wd;
+};
+
+// 1-bit Adam's fused decode -> exp_avg = mean -> frozen-variance step (sign_codec.hip)
+struct SignOnebitArgs {
+  uintptr_t recv, chunks, param, exp_avg, exp_avg_sq, shadow, stream;  // exp_avg_sq is read only
+  long long stride;
+  int nranks, num_chunks;
+  int scales_off, bits_off;
+  float lr_step, inv_n, eps, beta1, beta2;
+  int freeze_step;
+  uintptr_t step;    // nullable int32 device step counter: lr_step derived on the device
+  double lr;         // base lr for the device-side lr_step
+  uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
+  uintptr_t key_state;  // see TopkDecodeArgs
+  uint32_t key_seed, key_rank;
 };
 
 struct SignDecodeArgs {
@@ -154,6 +173,7 @@ void ew_qsgd_decode_apply(const QsgdDecodeArgs& a);
 
 void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
+void ew_sign_decode_onebit(const SignOnebitArgs& a);
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

@@ -13,21 +13,52 @@
 // The summation order is part of the contract (compress/oracle.py _sign_chunk_sums reproduces it,
 // so scales, bits and residuals match the oracle bit for bit): thread t adds, from 0.0f, elements
 // u * 1024 + 4 t + j for u = 0..7 outer, j = 0..3 inner; then ew_block_sum.
+//
+// 1-bit Adam's compressed stage (Tang et al. 2021; optim/flat.py FlatOnebitAdam) reuses both sides:
+// k_sign_encode<true, true> forms the momentum candidate in front of the same encode, and
+// k_sign_decode_onebit writes the averaged momentum and takes the frozen-variance step
+// (compress/oracle.py encode_sign_momentum / onebit_adam_apply, bit for bit).
 #include "common.h"
 #include "ewdml_ops.h"
 
 namespace {
 
-template <bool EF>
+// 1-bit Adam's compressed stage (MOM): what is compressed is the momentum candidate
+// u = m * beta1 + (1 - beta1) * (g + wd * p), formed here from the shared exp_avg m (read only)
+struct SignMom {
+  const float* m;  // the bucket's exp_avg
+  const float* p;  // the bucket's fp32 parameters (read when wd != 0)
+  float beta1, wd;
+};
+
+template <bool EF, bool MOM>
 __global__ __launch_bounds__(EW_BLOCK) void k_sign_encode(GradPtrs gp, float* __restrict__ resid,
                                                           const ChunkRow* __restrict__ chunks,
                                                           uint8_t* __restrict__ payload,
-                                                          int scales_off, int bits_off) {
+                                                          int scales_off, int bits_off,
+                                                          SignMom mo) {
   __shared__ float wsf[EW_WAVES];
   __shared__ float s_scale;
   const ChunkRow c = chunks[blockIdx.x];
   float4 e[EW_CU];
   ew_ld_chunk(gp, nullptr, c, e);  // positions past c.len read as 0: |e| = 0, bit = 0
+  if (MOM) {  // m and p read as 0 past c.len too: u = 0 there
+    float4 m[EW_CU];
+    ew_ld_chunk(gp, mo.m, c, m);
+    if (mo.wd != 0.0f) {
+      float4 p[EW_CU];
+      ew_ld_chunk(gp, mo.p, c, p);
+#pragma unroll
+      for (int u = 0; u < EW_CU; ++u)
+        e[u] = make_float4(e[u].x + mo.wd * p[u].x, e[u].y + mo.wd * p[u].y,
+                           e[u].z + mo.wd * p[u].z, e[u].w + mo.wd * p[u].w);
+    }
+    const float b1 = mo.beta1, c1 = 1.0f - mo.beta1;
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u)
+      e[u] = make_float4(m[u].x * b1 + c1 * e[u].x, m[u].y * b1 + c1 * e[u].y,
+                         m[u].z * b1 + c1 * e[u].z, m[u].w * b1 + c1 * e[u].w);
+  }
   if (EF) {
     float4 r[EW_CU];
     ew_ld_chunk(gp, resid, c, r);
@@ -154,6 +185,90 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
   }
 }
 
+// 1-bit Adam's receive side: m = (sum over ranks of +/- scale, rank order, from 0) * inv_n for
+// every element, then p -= lr_step * (m / (sqrtf(v) + eps)) where the frozen v > 0 (a coordinate
+// whose variance is still 0 never saw a gradient: it keeps its parameter).  v is only read.
+struct OnebitArgs {
+  float lr_step, inv_n, eps, beta1, beta2;
+  int freeze_step;
+  // device step counter (nullable): t = *step + 1, and lr_step = lr * sqrt(1 - beta2^freeze_step)
+  // / (1 - beta1^t) is formed here, so a captured graph follows the step count and the lr
+  const int* step;
+  double lr;
+  const float* lr_ptr;
+};
+
+__device__ __forceinline__ void ew_onebit(float& p, float m, float v, const OnebitArgs& a) {
+  if (v > 0.0f) p = p - a.lr_step * (m / (sqrtf(v) + a.eps));
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_onebit(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
+    float* __restrict__ mom, const float* __restrict__ var, uint16_t* __restrict__ shadow,
+    OnebitArgs oa, SgdArgs key) {
+  const ChunkRow c = chunks[blockIdx.x];
+  if (oa.step) {
+    const double t = (double)(*oa.step + 1);
+    const double lr = oa.lr_ptr ? (double)*oa.lr_ptr : oa.lr;
+    oa.lr_step = (float)(lr * sqrt(1.0 - pow((double)oa.beta2, (double)oa.freeze_step)) /
+                         (1.0 - pow((double)oa.beta1, t)));
+  }
+  ew_key_advance(key);
+  const int shift = 4 * (threadIdx.x & 7);
+  const size_t word0 = (size_t)blockIdx.x * EW_BM_WORDS + (threadIdx.x >> 3);
+  float acc[EW_CU][4];
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[u][j] = 0.0f;
+  for (int r = 0; r < nranks; ++r) {
+    const uint8_t* pay = recv + r * stride;
+    const float scale = reinterpret_cast<const float*>(pay + scales_off)[blockIdx.x];
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(pay + bits_off) + word0;
+    uint32_t w[EW_CU];
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u) w[u] = words[u * (EW_BLOCK / 8)];
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u) {
+      const uint32_t nib = w[u] >> shift;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[u][j] = acc[u][j] + (((nib >> j) & 1u) ? -scale : scale);
+    }
+  }
+  float* p = param + c.start;
+  float* b = mom + c.start;
+  const float* vq = var + c.start;
+  uint16_t* sh = shadow ? shadow + c.start : nullptr;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const int i = ew_chunk_idx(u);
+    if (i >= c.len) continue;
+    float mv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mv[j] = acc[u][j] * oa.inv_n;
+    if (i + 3 < c.len) {
+      const float4 p4 = *reinterpret_cast<const float4*>(p + i);
+      const float4 v4 = *reinterpret_cast<const float4*>(vq + i);
+      float pv[4] = {p4.x, p4.y, p4.z, p4.w};
+      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ew_onebit(pv[j], mv[j], vv[j], oa);
+      *reinterpret_cast<float4*>(b + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+      if (sh) ew_st4_bf16(sh + i, 4, pv);
+    } else {  // the last elements of a tensor
+      for (int j = 0; j < 4 && i + j < c.len; ++j) {
+        float pv = p[i + j];
+        ew_onebit(pv, mv[j], vq[i + j], oa);
+        b[i + j] = mv[j];
+        p[i + j] = pv;
+        if (sh) sh[i + j] = ew_f2bf(pv);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 #define EW_LAUNCH(kern, grid, stream, ...) \
@@ -170,10 +285,45 @@ void ew_sign_encode(const SignEncodeArgs& a) {
   ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
   float* resid = reinterpret_cast<float*>(a.resid);
   auto* pay = reinterpret_cast<uint8_t*>(a.payload);
-  if (resid)
-    EW_LAUNCH(k_sign_encode<true>, C, a.stream, g, resid, chunks, pay, a.scales_off, a.bits_off);
-  else
-    EW_LAUNCH(k_sign_encode<false>, C, a.stream, g, resid, chunks, pay, a.scales_off, a.bits_off);
+  const SignMom mo{reinterpret_cast<const float*>(a.mom_exp_avg),
+                   reinterpret_cast<const float*>(a.mom_param), a.mom_beta1, a.mom_wd};
+  if (mo.m) {  // 1-bit Adam's momentum encode: error feedback always on
+    if (!resid) throw std::runtime_error("ewdml sign: the momentum encode needs the residual");
+    if (mo.wd != 0.0f && !mo.p)
+      throw std::runtime_error("ewdml sign: weight decay needs the parameters");
+    EW_LAUNCH((k_sign_encode<true, true>), C, a.stream, g, resid, chunks, pay, a.scales_off,
+              a.bits_off, mo);
+  } else if (resid) {
+    EW_LAUNCH((k_sign_encode<true, false>), C, a.stream, g, resid, chunks, pay, a.scales_off,
+              a.bits_off, mo);
+  } else {
+    EW_LAUNCH((k_sign_encode<false, false>), C, a.stream, g, resid, chunks, pay, a.scales_off,
+              a.bits_off, mo);
+  }
+  EW_CHECK_LAUNCH();
+}
+
+void ew_sign_decode_onebit(const SignOnebitArgs& a) {
+  const int C = a.num_chunks;
+  if (C <= 0 || a.nranks <= 0) throw std::runtime_error("ewdml 1-bit Adam: nothing to decode");
+  if (a.scales_off % 16 || a.bits_off % 16 || a.bits_off < a.scales_off + 4LL * C ||
+      a.stride < a.bits_off + 4LL * EW_BM_WORDS * C)
+    throw std::runtime_error("ewdml 1-bit Adam: payload sections do not fit the payload");
+  if (!a.param || !a.exp_avg || !a.exp_avg_sq)
+    throw std::runtime_error("ewdml 1-bit Adam: the step needs param, exp_avg and exp_avg_sq");
+  if (a.freeze_step < 1) throw std::runtime_error("ewdml 1-bit Adam: freeze_step must be >= 1");
+  OnebitArgs oa{a.lr_step, a.inv_n, a.eps, a.beta1, a.beta2, a.freeze_step,
+                reinterpret_cast<const int*>(a.step), a.lr,
+                reinterpret_cast<const float*>(a.lr_ptr)};
+  SgdArgs key{};
+  key.key_state = reinterpret_cast<uint32_t*>(a.key_state);
+  key.key_seed = a.key_seed;
+  key.key_rank = a.key_rank;
+  EW_LAUNCH(k_sign_decode_onebit, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv), a.nranks,
+            a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
+            reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.exp_avg),
+            reinterpret_cast<const float*>(a.exp_avg_sq), reinterpret_cast<uint16_t*>(a.shadow),
+            oa, key);
   EW_CHECK_LAUNCH();
 }
 

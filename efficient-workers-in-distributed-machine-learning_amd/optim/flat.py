@@ -187,6 +187,55 @@ class FlatAdam(_LrMixin):
         self.lr = sd.get("lr", self.lr)
 
 
+class FlatOnebitAdam(FlatAdam):
+    """1-bit Adam (Tang et al., ICML 2021; DeepSpeed ``OnebitAdam``).  Steps 1..``freeze_step`` are
+    :class:`FlatAdam` on the dense averaged gradient.  From then on (``frozen``) ``exp_avg_sq`` is
+    never written again and the exchange, not :meth:`step_range`, runs the step: every rank
+    sign-compresses its error-compensated momentum candidate, and the decode writes the average
+    into ``exp_avg`` and applies ``p -= lr_step * exp_avg / (sqrt(exp_avg_sq) + eps)``
+    (``Codec.encode_momentum`` / ``decode_apply_onebit``).  The error-feedback residual is per-rank
+    state and lives in the exchange; this optimizer's state is the same on every rank."""
+    onebit = True
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 amsgrad=False, freeze_step=None):
+        if amsgrad:
+            raise ValueError("1-bit Adam freezes exp_avg_sq: AMSGrad's running maximum has no "
+                             "place in it")
+        if freeze_step is None or int(freeze_step) < 1:
+            raise ValueError("1-bit Adam needs freeze_step >= 1 (the dense warm-up's length)")
+        super().__init__(flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.freeze_step = int(freeze_step)
+
+    @property
+    def frozen(self) -> bool:
+        """The next step is a compressed-stage step."""
+        return self.steps >= self.freeze_step
+
+    def lr_step(self) -> float:
+        """Host ``lr_step`` of the next (compressed-stage) step."""
+        b1, b2 = self.betas
+        return oracle.onebit_lr_step(self.lr, b1, b2, self.steps + 1, self.freeze_step)
+
+    def hparams(self) -> dict:
+        return dict(lr=self.lr, lr_step=self.lr_step(), betas=self.betas, eps=self.eps,
+                    weight_decay=self.weight_decay, freeze_step=self.freeze_step,
+                    step_t=self.step_t, lr_t=self.lr_t)
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        if self.frozen:
+            raise RuntimeError("1-bit Adam is past its freeze step: the sign exchange runs the "
+                               "step (a dense step would write exp_avg_sq)")
+        super().step_range(start, length, grad, grad_scale)
+
+    def state_dict(self):
+        return dict(super().state_dict(), kind="onebit_adam", freeze_step=self.freeze_step)
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
     if name == "sgd":
@@ -195,5 +244,11 @@ def make_optimizer(name, flat, **kw):
                                          "nesterov")})
     if name in ("adam", "amsgrad"):
         return FlatAdam(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
+                        eps=kw.get("eps", 1e-8),
                         amsgrad=(name == "amsgrad") or kw.get("amsgrad", False))
+    if name == "onebit_adam":
+        return FlatOnebitAdam(flat, lr=kw.get("lr", 1e-3),
+                              weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),
+                              amsgrad=kw.get("amsgrad", False),
+                              freeze_step=kw.get("freeze_step"))
     raise ValueError(f"unknown optimizer {name!r}")

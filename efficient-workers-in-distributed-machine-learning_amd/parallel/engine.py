@@ -87,6 +87,14 @@ class GradientExchange:
         self.ef_mode = None if self.resid is None else (
             ef_mode if (self.dgc or self.ef21) else "plain")
         self.vel = torch.zeros_like(flat.grad) if self.dgc else None
+        # 1-bit Adam's compressed stage (optim/flat.py FlatOnebitAdam): the encode compresses the
+        # error-compensated momentum candidate, the decode writes the averaged momentum and takes
+        # the frozen-variance step.  The optimizer's dense warm-up runs through an all-reduce
+        # exchange of its own (runtime/trainer.py switches between the two)
+        self.onebit = bool(getattr(optimizer, "onebit", False)) and not codec.allreduce
+        if self.onebit and (codec.kind != "sign" or self.resid is None or predivide != 1.0):
+            raise ValueError("1-bit Adam's compressed stage needs the sign codec with error "
+                             "feedback and predivide 1")
         self.gest = torch.zeros_like(flat.grad) if self.ef21 else None  # EF21's global G
         self.local_apply = False  # enable_local_apply
         self.local_apply_dense = False
@@ -319,6 +327,12 @@ class GradientExchange:
                 self.send[bi].copy_(g * (1.0 / self.predivide))
             return
         resid = None if self.resid is None else self.resid[b.start:b.start + b.length]
+        if self.onebit:  # sign(exp_avg * beta1 + (1 - beta1) * (g + wd * p) + residual)
+            o = self.opt
+            self.codec.encode_momentum(bi, g, self.payload[bi], resid,
+                                       o.exp_avg[b.start:b.start + b.length], o.betas[0],
+                                       o.weight_decay, self.flat.data_view(b))
+            return
         dgc = None
         if self.dgc:
             o = self.opt
@@ -441,6 +455,15 @@ class GradientExchange:
                     opt.step_range(b.start, b.length, G, 1.0)
                 elif self.local_apply:
                     continue  # applied by the encode's write pass (enable_local_apply)
+                elif self.onebit:  # exp_avg = mean of the decoded momenta; frozen-variance step
+                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
+                    sl = slice(b.start, b.start + b.length)
+                    self.codec.decode_apply_onebit(b.index, recv, scale, self.flat.data_view(b),
+                                                   opt.exp_avg[sl], opt.exp_avg_sq[sl],
+                                                   opt.hparams(),
+                                                   shadow=self.flat.shadow_view(b),
+                                                   key_state=self.key_state if adv else None,
+                                                   rank=self.comm.rank)
                 elif getattr(opt, "fusable", False):
                     adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     hp, mom = opt.hparams(), opt.mom[b.start:b.start + b.length]

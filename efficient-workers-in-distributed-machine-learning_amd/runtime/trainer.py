@@ -182,13 +182,15 @@ class Trainer:
         self.n_workers = n_workers
         self.opt = make_optimizer(cfg.optimizer, self.flat, lr=lr, momentum=cfg.momentum,
                                   dampening=cfg.dampening, weight_decay=cfg.weight_decay,
-                                  nesterov=cfg.nesterov)
+                                  nesterov=cfg.nesterov, eps=cfg.adam_eps,
+                                  freeze_step=cfg.onebit_warmup_steps)
 
         # exchange ---------------------------------------------------------------------------------
         ckw = dict(ratio=cfg.topk_ratio, levels=cfg.qsgd_levels, bits=cfg.qsgd_bits,
                    norm=cfg.qsgd_norm, seed=cfg.seed, dense_below=cfg.topk_dense_below)
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
+        self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
         if cfg.topology == "ps":
             self.exchange = PSExchange(self.flat, self.comm, make_codec(cfg.compress, **ckw),
                                        make_codec(cfg.pull_compress or cfg.compress, **ckw),
@@ -198,6 +200,20 @@ class Trainer:
                                        else None)
         elif cfg.topology == "sharded":
             self.exchange = ShardedPSExchange(self.flat, self.comm, cfg.compress, self.opt, **ckw)
+        elif cfg.optimizer == "onebit_adam":
+            # 1-bit Adam: two exchanges over the same flat model and optimizer -- the dense fp32
+            # all-reduce of the warm-up (steps 1..T_w: FlatAdam's step) and the sign exchange of
+            # the compressed stage (momentum encode, fused decode + frozen-variance step).  An
+            # exchange's hooks are inert unless its begin() ran; _select_stage picks the one of
+            # the next step
+            side = (self.cuda and not cfg.phase_timing
+                    and (cfg.hip_graph == "off" or os.environ.get("EWDML_SIDE_STREAM") == "1"))
+            self._stages = tuple(
+                GradientExchange(self.flat, self.comm, make_codec(kind, **ckw), self.opt,
+                                 overlap=cfg.overlap, error_feedback=ef, predivide=1.0,
+                                 side_stream=side, ef_mode="plain")
+                for kind, ef in (("none", False), ("sign", True)))
+            self.exchange = self._stages[1 if self.opt.frozen else 0]
         else:
             # captured steps keep the encode + collectives on the step's own stream: a side-stream
             # fork makes the graph a DAG, which ROCm 7.2 replays node by node from the host (~7.9
@@ -275,14 +291,16 @@ class Trainer:
             self.exchange.enable_local_apply()
         # --phase-timing: the step's phase clock, shared with the exchange (engine.Stopwatch)
         self.clock = Stopwatch(self.cuda) if cfg.phase_timing else None
-        for e in (self.exchange, getattr(self.exchange, "inner", None)):
-            if e is not None and hasattr(e, "clock"):
+        for e in self._exchanges():
+            if hasattr(e, "clock"):
                 e.clock = self.clock
         self.overlap_splits = (self.graph_plan["splits"] if (self.graph_plan is not None and
                                                              self.graph_mode == "segmented")
                                else cfg.overlap_splits)
         if self.graph_mode == "segmented":  # collectives on their own stream, beside backward
-            self.exchange.comm_stream = torch.cuda.Stream(device=self.device)
+            cs = torch.cuda.Stream(device=self.device)
+            for e in (self.exchange,) + self._stages:
+                e.comm_stream = cs
         self._graphs = None
         # (U, graph, loss, out): U consecutive steps captured as one graph (train_steps)
         self._ugraph = None
@@ -389,6 +407,24 @@ class Trainer:
             return contextlib.nullcontext()
         return torch.cuda.stream(self.gstream)
 
+    def _exchanges(self):
+        """Every exchange object of this trainer: the current one, local SGD's wrapped one, and
+        both stages of 1-bit Adam."""
+        out = [self.exchange, getattr(self.exchange, "inner", None), *self._stages]
+        return [e for i, e in enumerate(out) if e is not None and e not in out[:i]]
+
+    def _select_stage(self):
+        """1-bit Adam: make the exchange of the next step current -- the dense all-reduce through
+        step T_w, the sign exchange from step T_w + 1 on.  Every rank switches at the same step
+        (the optimizer's step count is the same everywhere) and drops its captured graphs once."""
+        if not self._stages:
+            return
+        ex = self._stages[1 if self.opt.frozen else 0]
+        if ex is not self.exchange:
+            ex.step_idx = self.exchange.step_idx
+            self.exchange = ex
+            self._drop_graphs()
+
     def _drop_graphs(self):
         """Forget every captured step (the next graphed step re-captures)."""
         self._graphs = None
@@ -493,6 +529,10 @@ class Trainer:
 
     def _unroll_ok(self, unroll: int, pos: bool = True) -> bool:
         cfg = self.cfg
+        if self._stages and not (self.opt.frozen and self.exchange is self._stages[1]):
+            # 1-bit Adam: no unrolled run spans the stage switch (the warm-up is running, or its
+            # last step just ran and the next train_step moves to the sign exchange)
+            return False
         ok = (self.graph_mode == "full" and self._graphs is not None and len(self._graphs) == 1
               and self._in_graph_batch and self.loader is not None and self.loader.fused
               and self.clock is None and not self.local_sgd and not self.is_server
@@ -561,7 +601,8 @@ class Trainer:
     def close(self):
         """Release the exchange hooks, the watchdog and the own RCCL communicator (collective:
         every rank calls it).  The process group stays up."""
-        self.exchange.close()
+        for e in {id(e): e for e in (self.exchange,) + self._stages}.values():
+            e.close()
         if self.cuda and getattr(self, "_loss_seed", None) is not None:
             from ..ops.nn import set_unit_grad
 
@@ -610,6 +651,7 @@ class Trainer:
         if self.fault is not None and self.fault == (self.rank, self.step):
             raise FaultInjected(f"injected fault on rank {self.rank} at step {self.step}")
         self._apply_ratio_schedule()
+        self._select_stage()
         if self.cfg.lr_warmup_epochs > 0 or self.cfg.lr_decay_epochs:
             lr = self.lr_at(self.step)
             if lr != self.opt.lr:
@@ -668,9 +710,8 @@ class Trainer:
             ex = self.exchange
             self._drop_graphs()
             self.graph_mode = "off"
-            for e in (ex, getattr(ex, "inner", None)):
-                if e is not None:
-                    e.use_dev_key = e.defer_comm = e._active = e.dev_key_advance = False
+            for e in self._exchanges():
+                e.use_dev_key = e.defer_comm = e._active = e.dev_key_advance = False
             # a stream forked into an aborted capture (the encode side stream, a backend's
             # internal stream) can stay in capture mode: continue on fresh streams
             self.gstream = None
@@ -971,6 +1012,7 @@ class Trainer:
                                   for k, v in st["optimizer"].items()})
         self.step = int(st["step"])
         self.epoch = int(st["epoch"])
+        self._select_stage()  # 1-bit Adam past its freeze step: the residual's exchange
         inner = getattr(self.exchange, "inner", self.exchange)
         for name, attr in (("ef_residual", "resid"), ("ef_velocity", "vel"),
                            ("ef_global", "gest")):
