@@ -190,6 +190,132 @@ class Codec:
                                           param)
         payload[:lay.nbytes].copy_(out)
 
+    # -- two-stage sign all-reduce (parallel/twostage.py): three launches per bucket ------------
+    def bind_twostage(self, ts_plans, device):
+        """Bind the buckets' :class:`TwoStagePlan` s.  On the GPU every bucket gets its slot
+        tables and every non-empty shard its chunk table (any rank may be asked to own any shard:
+        the kernel tests drive all of them from one process)."""
+        if self.kind != "sign":
+            raise ValueError("the two-stage exchange needs the sign codec")
+        self.device = torch.device(device)
+        self.ts = list(ts_plans)
+        self.ts_dev = self.ts_shard_dev = None
+        if self.device.type == "cuda" and not _FORCE_ORACLE:
+            if ops.hip_required():
+                ops.require()
+            self.ts_dev = [ops.SignSlots(t, self.device) for t in self.ts]
+            self.ts_shard_dev = [[None if sp is None else ops.SignTables(sp, self.device)
+                                  for _, _, sp, _, _ in t.shards] for t in self.ts]
+        return self
+
+    def _ts_kernel(self, t: torch.Tensor) -> bool:
+        return t.is_cuda and not _FORCE_ORACLE
+
+    def ts_encode(self, b: int, grad: torch.Tensor, rows: torch.Tensor, resid: torch.Tensor,
+                  mom: dict = None):
+        """Push: sign-encode (error feedback through the worker residual ``resid``) every shard
+        of bucket ``b`` of the flat gradient view ``grad`` into its row of ``rows`` (``[N, P]``).
+        ``mom`` (``exp_avg``, ``beta1``, ``weight_decay``, ``param``): 1-bit Adam's momentum
+        encode instead.  One launch on the GPU."""
+        ts = self.ts[b]
+        if resid is None:
+            raise ValueError("the two-stage push always runs with error feedback")
+        if self._ts_kernel(grad):
+            sl = self.ts_dev[b]
+            if mom is None:
+                ops.sign_encode(sl, grad, rows, None, resid, slots=sl)
+            else:
+                ops.sign_encode_momentum(sl, grad, rows, None, resid, mom["exp_avg"],
+                                         mom["beta1"], mom.get("weight_decay", 0.0),
+                                         mom.get("param"), slots=sl)
+            return
+        for r, (s0, ln, sp, lay, _) in enumerate(ts.shards):
+            if sp is None:
+                continue
+            sl = slice(s0, s0 + ln)
+            if mom is None:
+                out = oracle.encode_sign(grad[sl], sp, lay, resid[sl])
+            else:
+                out = oracle.encode_sign_momentum(grad[sl], sp, lay, resid[sl], mom["exp_avg"][sl],
+                                                  mom["beta1"], mom.get("weight_decay", 0.0),
+                                                  None if mom.get("param") is None
+                                                  else mom["param"][sl])
+            rows[r, :lay.nbytes].copy_(out)
+
+    def ts_reduce_encode(self, b: int, r: int, recv: torch.Tensor, out: torch.Tensor, inv_n: float,
+                         sresid: torch.Tensor):
+        """Owner step of shard ``r`` of bucket ``b``: average the N received rows ``recv`` (``[N,
+        P]``), add the server residual ``sresid`` (shard-relative, updated in place) and
+        sign-encode again into the row ``out``.  One launch on the GPU."""
+        _, ln, sp, lay, _ = self.ts[b].shards[r]
+        if sp is None:
+            raise ValueError("an empty shard has no owner step")
+        if self._ts_kernel(recv):
+            ops.sign_reduce_encode(self.ts_shard_dev[b][r], recv, lay, inv_n, sresid, out)
+            return
+        out[:lay.nbytes].copy_(oracle.sign_reduce_encode(recv, sp, lay, inv_n, sresid[:ln]))
+
+    def _ts_decoded(self, b: int, rows: torch.Tensor) -> torch.Tensor:
+        """Oracle pull: every shard's row decoded into a bucket-length fp32 vector."""
+        ts = self.ts[b]
+        g = torch.zeros(ts.plan.length, dtype=torch.float32, device=rows.device)
+        for r, (s0, ln, sp, lay, _) in enumerate(ts.shards):
+            if sp is not None:
+                g[s0:s0 + ln] = oracle.decode_sum(rows[r:r + 1, :lay.nbytes], sp, lay, 0, 1.0)
+        return g
+
+    def ts_decode_apply_sgd(self, b: int, rows: torch.Tensor, param: torch.Tensor,
+                            mom: torch.Tensor, hp: dict, first: bool, grad_out=None, shadow=None,
+                            key_state=None, rank: int = 0):
+        """Pull: decode every owner's row of the gathered ``rows`` (``[N, P]``, already averaged:
+        scale 1) and take the fused SGD step of bucket ``b``; ``param`` None: write the decoded
+        mean to ``grad_out`` only.  One launch on the GPU."""
+        if param is not None and mom is None and hp["momentum"] != 0:
+            raise ValueError("a momentum step needs the momentum buffer")
+        ts = self.ts[b]
+        if self._ts_kernel(rows):
+            sl = self.ts_dev[b]
+            kw = dict(grad_out=grad_out, grad_scale=1.0, key_state=key_state, key_seed=self.seed,
+                      key_rank=rank, slots=sl)
+            if param is not None:
+                kw.update(param=param, mom=mom, lr=hp["lr"], momentum=hp["momentum"],
+                          dampening=hp["dampening"], weight_decay=hp["weight_decay"],
+                          nesterov=hp["nesterov"], first=first, shadow=shadow,
+                          lr_tensor=hp.get("lr_t"))
+            ops.sign_decode_apply(sl, rows, None, **kw)
+            return
+        g = self._ts_decoded(b, rows)
+        if grad_out is not None:
+            grad_out[:ts.plan.length].copy_(g)
+        if param is None:
+            return
+        for off, n in zip(ts.plan.offsets, ts.plan.numels):
+            oracle.sgd_apply(param[off:off + n], None if mom is None else mom[off:off + n],
+                             g[off:off + n], hp["lr"], hp["momentum"], hp["dampening"],
+                             hp["weight_decay"], hp["nesterov"], first)
+
+    def ts_decode_apply_onebit(self, b: int, rows: torch.Tensor, param: torch.Tensor,
+                               exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,
+                               shadow=None, key_state=None, rank: int = 0):
+        """Pull of 1-bit Adam: ``exp_avg`` = the decoded rows (``inv_n`` = 1, the owners
+        averaged), then the frozen-variance step of bucket ``b``.  One launch on the GPU."""
+        ts = self.ts[b]
+        if self._ts_kernel(rows):
+            sl = self.ts_dev[b]
+            b1, b2 = hp["betas"]
+            ops.sign_decode_onebit(sl, rows, None, param, exp_avg, exp_avg_sq, 1.0,
+                                   hp["lr_step"], hp["eps"], b1, b2, hp["freeze_step"],
+                                   shadow=shadow, step=hp.get("step_t"), lr=hp["lr"],
+                                   lr_tensor=hp.get("lr_t"), key_state=key_state,
+                                   key_seed=self.seed, key_rank=rank, slots=sl)
+            return
+        for r, (s0, ln, sp, lay, _) in enumerate(ts.shards):
+            if sp is not None:
+                sl = slice(s0, s0 + ln)
+                oracle.onebit_adam_apply(rows[r:r + 1, :lay.nbytes], sp, lay, param[sl],
+                                         exp_avg[sl], exp_avg_sq[sl], 1.0, hp["lr_step"],
+                                         hp["eps"])
+
     def decode_apply_onebit(self, b: int, recv: torch.Tensor, inv_n: float, param: torch.Tensor,
                             exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,
                             shadow=None, key_state=None, rank: int = 0):

@@ -358,6 +358,17 @@ def onebit_adam_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, para
         param[sl] = torch.where(v > 0, p - step, p)
 
 
+def sign_reduce_encode(recv: torch.Tensor, plan: BucketPlan, layout: Layout, inv_n: float,
+                       server_resid: torch.Tensor) -> torch.Tensor:
+    """The two-stage sign all-reduce's owner step (``parallel/twostage.py``) for one shard:
+    ``recv`` (uint8 ``[N, >= layout.nbytes]``) holds the N workers' payloads of the shard; their
+    rank-ordered sum from 0 times ``inv_n`` is sign-compressed again with the *server* residual
+    (updated in place).  By definition ``encode_sign(decode_sum(recv, plan, layout, 0, inv_n),
+    plan, layout, server_resid)``: no numerics of its own."""
+    mean = decode_sum(recv[:, :layout.nbytes], plan, layout, 0, inv_n)
+    return encode_sign(mean, plan, layout, server_resid)
+
+
 def onebit_lr_step(lr: float, beta1: float, beta2: float, step: int, freeze_step: int) -> float:
     """``lr * sqrt(1 - beta2^freeze_step) / (1 - beta1^step)``: the variance's bias correction
     stays at its value of the freeze step, the momentum's follows the 1-based ``step``.  In

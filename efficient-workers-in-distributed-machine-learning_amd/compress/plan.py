@@ -213,3 +213,57 @@ class Layout:
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)
+
+
+MAX_SEGMENTS = 128  # EW_MAX_T in ops/csrc/common.h: the kernels' pointer-table capacity
+
+
+class TwoStagePlan:
+    """One bucket of the two-stage sign all-reduce (``parallel/twostage.py``), cut into one shard
+    per rank by ``parallel.sharded.shard_plans``.
+
+    ``plan``: the bucket's *shard-major* plan -- one "tensor" per segment (a tensor crossing a cut
+    is two segments, each chunked from its own start), so its chunk list is the shards' chunk
+    lists one after the other and one launch covers every shard.  ``shards[r] = (start, length,
+    BucketPlan | None, Layout | None, chunk0)``: shard r's own plan (offsets relative to its
+    start), its sign layout and its first chunk in ``plan``.
+
+    The exchange's buffers are ``[N, P]`` byte rows, ``P`` the largest shard payload; row r holds
+    shard r's payload ``scales f32[C_r] | bits u32[256 C_r]`` from byte 0.  ``slots[c] = (byte
+    offset of chunk c's scale, byte offset of its 256 words)`` inside such a buffer -- the same
+    table addresses the push rows (row r goes to rank r) and the all-gathered pull rows (row r
+    came from owner r).  Row padding and alignment pads are never written."""
+
+    def __init__(self, bucket_plan: BucketPlan, shards):
+        self.N = len(shards)
+        numels, offsets = [], []
+        self.shards = []
+        c0 = 0
+        for s0, ln, sp in shards:
+            lay = Layout.build("sign", sp) if sp is not None else None
+            self.shards.append((s0, ln, sp, lay, c0))
+            if sp is not None:
+                numels += sp.numels
+                offsets += [s0 + o for o in sp.offsets]
+                c0 += sp.num_chunks
+        if len(numels) > MAX_SEGMENTS:
+            raise ValueError(f"bucket has {len(numels)} tensor segments after sharding (max "
+                             f"{MAX_SEGMENTS}): use smaller buckets (--bucket-mb)")
+        self.plan = BucketPlan(numels, offsets, 1.0, bucket_plan.bucket_offset,
+                               bucket_plan.length)
+        assert self.plan.num_chunks == c0
+        self.P = max([lay.nbytes for _, _, _, lay, _ in self.shards if lay is not None])
+        if self.N * self.P >= 1 << 31:
+            raise ValueError("two-stage row buffer of 2 GiB or more: use smaller buckets")
+        self.max_shard = max(ln for _, ln, _, _, _ in self.shards)
+        self.slots = []
+        for r, (_, _, sp, lay, _) in enumerate(self.shards):
+            if sp is not None:
+                self.slots += [(r * self.P + lay.scales + 4 * c,
+                                r * self.P + lay.codes + 4 * BM_WORDS * c)
+                               for c in range(sp.num_chunks)]
+        self.slot_end = max(w for _, w in self.slots) + 4 * BM_WORDS
+
+    def slot_table(self, device) -> torch.Tensor:
+        """int32 [C, 2]: byte offsets of every chunk's scale and words (csrc int2 slots)."""
+        return torch.tensor(self.slots, dtype=torch.int32, device=device)

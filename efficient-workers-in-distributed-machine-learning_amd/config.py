@@ -66,6 +66,8 @@ class Config:
     qsgd_norm: str = "max"  # max | l2 (the reference's L2 norm)
     topology: str = "allgather"  # allgather (all-to-all) | ps (rank-0 parameter server) |
     #                               sharded (every rank owns 1/N of each bucket: parallel/sharded.py)
+    #                               | twostage (sign codec: sharded owners with worker and server
+    #                               error feedback, parallel/twostage.py)
     pull: str = "grad"  # ps topology: pull averaged 'grad' or server 'weights'
     pull_compress: Optional[str] = None  # ps topology: codec of the pull (default = push codec)
     sync_every: int = 1  # local SGD: exchange every H steps (method 6)
@@ -184,14 +186,38 @@ class Config:
             # only the all-gather exchange keeps a residual (parallel/engine.py
             # GradientExchange); the parameter-server / sharded exchanges have none, so their
             # top-k runs keep the reference's schedule (no EF warm-up) and record no EF
-            c.error_feedback = (c.compress in ("topk", "topk_qsgd", "sign")
-                                and c.topology == "allgather")
-        if c.compress == "sign" and (c.topology != "allgather" or c.sync_every > 1
-                                     or c.select_best):
+            c.error_feedback = ((c.compress in ("topk", "topk_qsgd", "sign")
+                                 and c.topology == "allgather")
+                                or (c.compress == "sign" and c.topology == "twostage"))
+        if c.topology == "twostage":
+            # the two-stage sign all-reduce (parallel/twostage.py): both of its quantisations
+            # are error-compensated, and the owners average with 1/N
+            why = None
+            if c.compress != "sign":
+                why = (f"is the sign codec's exchange: it needs --compress sign, not "
+                       f"{c.compress!r}")
+            elif not c.error_feedback:
+                why = ("compensates both of its quantisations with a residual: it does not run "
+                       "with --no-error-feedback")
+            elif c.sync_every > 1:
+                why = "exchanges every step: it does not run with --sync-every > 1"
+            elif c.select_best:
+                why = "averages all workers: it does not run with --select-best"
+            elif c.predivide != 1.0:
+                why = ("averages on the shard owners with 1/N: it does not run with --predivide "
+                       "other than 1")
+            elif c.hip_graph in ("full", "segmented"):
+                why = (f"issues its two collectives and the owner step between two graphs: "
+                       f"--hip-graph {c.hip_graph} is not supported (auto resolves to split)")
+            if why is not None:
+                raise ValueError("--topology twostage " + why)
+        elif c.compress == "sign" and (c.topology != "allgather" or c.sync_every > 1
+                                       or c.select_best):
             # scaled sign is biased without error feedback, and only GradientExchange keeps one
             raise ValueError("--compress sign needs the all-gather exchange's residual: it does "
                              "not run with --topology ps / sharded, --sync-every > 1 or "
-                             "--select-best (those exchanges keep no error feedback)")
+                             "--select-best (those exchanges keep no error feedback); "
+                             "--topology twostage is the sign codec's sharded exchange")
         if c.optimizer == "onebit_adam":
             # the compressed stage is the sign codec's all-gather with its residual; every option
             # that changes what is exchanged, or that scales it, breaks the momentum's linearity
@@ -230,8 +256,8 @@ class Config:
                 c.lr_warmup_epochs = 2.0
                 if c.lr_warmup_start is None:
                     c.lr_warmup_start = 0.1
-        if c.topology not in ("allgather", "ps", "sharded"):
-            raise ValueError("--topology must be allgather, ps or sharded")
+        if c.topology not in ("allgather", "ps", "sharded", "twostage"):
+            raise ValueError("--topology must be allgather, ps, sharded or twostage")
         if c.graph_warmup < 1:
             raise ValueError("--graph-warmup must be >= 1 (one eager step initialises the stream)")
         if c.ckpt_dir is None:
@@ -277,7 +303,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--qsgd-levels", type=int, default=d.qsgd_levels)
     a("--qsgd-bits", type=int, default=d.qsgd_bits, choices=[4, 8])
     a("--qsgd-norm", type=str, default=d.qsgd_norm, choices=["max", "l2"])
-    a("--topology", type=str, default=d.topology, choices=["allgather", "ps", "sharded"])
+    a("--topology", type=str, default=d.topology, choices=["allgather", "ps", "sharded", "twostage"])
     a("--pull", type=str, default=d.pull, choices=["grad", "weights"])
     a("--pull-compress", type=str, default=None,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd"])

@@ -390,6 +390,44 @@ def qsgd_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
 
 
+class SignTables:
+    """Device chunk table of a sign-codec plan without the top-k / QSGD scratch of
+    :class:`DevicePlan` (the two-stage exchange's per-shard plans)."""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        self.chunks = plan.chunk_table(device)
+
+
+class SignSlots(SignTables):
+    """Device tables of one bucket of the two-stage sign exchange (``compress/plan.py
+    TwoStagePlan``): the shard-major chunk table and the per-chunk slot table of the ``[N, P]``
+    row buffers.  Pass it as both ``dp`` and ``slots`` of the sign wrappers."""
+
+    def __init__(self, ts, device):
+        super().__init__(ts.plan, device)
+        self.ts = ts
+        self.table = ts.slot_table(device)
+        self.nbytes = ts.N * ts.P  # bytes of a row buffer
+        # the host copy of the table decides whether a buffer holds every slot (the kernels
+        # cannot): scales 4-byte, words 16-byte aligned, nothing past slot_end
+        if (len(ts.slots) != ts.plan.num_chunks or ts.slot_end > self.nbytes
+                or any(a < 0 or a % 4 or w % 16 or a + 4 > self.nbytes
+                       or w + 4 * 256 > self.nbytes for a, w in ts.slots)):
+            raise ValueError("two-stage slot table does not fit its row buffer")
+
+
+def _check_slots(dp, slots, buf, name):
+    """``buf`` is the ``[N, P]`` row buffer the slot table of ``slots`` addresses."""
+    if not isinstance(slots, SignSlots) or slots.plan is not dp.plan:
+        raise ValueError("slots must be the SignSlots of the same bucket as dp")
+    _check(buf, torch.uint8, name)
+    if buf.numel() < slots.nbytes:
+        raise ValueError(f"{name} has {buf.numel()} bytes, the slot table addresses "
+                         f"{slots.nbytes}")
+    return _ptr(slots.table), slots.ts.slot_end
+
+
 def _check_sign_layout(dp, layout):
     C = dp.plan.num_chunks
     if layout.kind != "sign":
@@ -399,33 +437,81 @@ def _check_sign_layout(dp, layout):
         raise ValueError("sign layout does not match the bucket plan")
 
 
-def sign_encode(dp: DevicePlan, grad, payload, layout, resid=None):
-    """Scaled sign of one bucket (``csrc/sign_codec.hip``): per chunk the mean ``|e|`` and one bit
-    per element, ``e = grad + resid`` with ``resid`` (error feedback) overwritten by what was not
-    sent.  One launch, no scratch; bitwise ``compress/oracle.py encode_sign``."""
-    C = require()
-    ptrs, mask = grad_pointers(dp, grad)
+def _sign_payload(dp, payload, layout, slots):
+    """Checks of an encode's destination; returns (bytes, scales_off, bits_off, slots, slot_end)."""
+    if slots is not None:  # the [N, P] row buffer: every chunk goes to its slot
+        sp, end = _check_slots(dp, slots, payload, "payload")
+        return payload.numel(), 0, 0, sp, end
     _check_sign_layout(dp, layout)
     _check(payload, torch.uint8, "payload")
     if payload.numel() < layout.nbytes:
         raise ValueError("payload too small")
+    return layout.nbytes, layout.scales, layout.codes, 0, 0
+
+
+def sign_encode(dp, grad, payload, layout, resid=None, slots=None):
+    """Scaled sign of one bucket (``csrc/sign_codec.hip``): per chunk the mean ``|e|`` and one bit
+    per element, ``e = grad + resid`` with ``resid`` (error feedback) overwritten by what was not
+    sent.  One launch, no scratch; bitwise ``compress/oracle.py encode_sign``.  ``slots``
+    (:class:`SignSlots`, also ``dp``): ``payload`` is the two-stage exchange's ``[N, P]`` row
+    buffer and every chunk is written to its slot (``layout`` unused; pads are not written)."""
+    C = require()
+    ptrs, mask = grad_pointers(dp, grad)
+    nbytes, so, bo, sp, end = _sign_payload(dp, payload, layout, slots)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
-    C.sign_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
-                  dp.plan.num_tensors, dp.plan.num_chunks, layout.scales, layout.codes, _stream())
+    C.sign_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), nbytes,
+                  dp.plan.num_tensors, dp.plan.num_chunks, so, bo, _stream(), sp, end)
 
 
-def sign_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
-                      momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
-                      nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
-                      key_rank=0, lr_tensor=None):
-    """``grad_out = grad_scale * sum over the rows of recv (rank order) of +/- scale`` and / or the
-    fused SGD step on ``param`` (``mom`` None: a step without momentum)."""
+def sign_reduce_encode(dp, recv, layout, inv_n, sresid, out):
+    """The two-stage exchange's owner step for one shard (``dp``: :class:`SignTables` of the
+    shard's plan): ``e = inv_n * sum over the rows of recv (rank order) of +/- scale + sresid``,
+    formed in registers and encoded into ``out``; ``sresid`` (shard-relative) is overwritten with
+    what was not sent.  ``recv`` is ``[N, P]`` with ``P >= layout.nbytes``; only the scales and
+    words of ``out`` are written.  Bitwise ``compress/oracle.py sign_reduce_encode``."""
     C = require()
+    _check_sign_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[0] < 1 or recv.shape[0] > 64:
+        raise ValueError("recv must be [nranks, P] with 1 <= nranks <= 64")
+    if recv.shape[1] < layout.nbytes or recv.shape[1] % 16:
+        raise ValueError(f"recv rows must be 16-byte multiples of at least {layout.nbytes} bytes "
+                         "(row stride >= payload)")
+    _check(out, torch.uint8, "out")
+    if out.numel() < layout.nbytes:
+        raise ValueError("out too small")
+    if sresid is None:
+        raise ValueError("the owner step needs the server residual")
+    _check_bucket(dp, sresid, "sresid")
+    C.sign_reduce_encode(_ptr(recv), recv.shape[0], recv.shape[1], _ptr(dp.chunks),
+                         dp.plan.num_chunks, layout.scales, layout.codes, float(inv_n),
+                         _ptr(sresid), _ptr(out), out.numel(), _stream())
+
+
+def _sign_recv(dp, recv, layout, slots):
+    """Checks of a decode's source; returns (nranks, stride, scales_off, bits_off, slots,
+    slot_end)."""
+    if slots is not None:  # the gathered [N, P] row buffer, read as one slot-addressed payload
+        sp, end = _check_slots(dp, slots, recv, "recv")
+        return 1, recv.numel(), 0, 0, sp, end
     _check_sign_layout(dp, layout)
     _check(recv, torch.uint8, "recv")
     if recv.dim() != 2 or recv.shape[1] != layout.nbytes or recv.shape[0] < 1:
         raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+    return recv.shape[0], layout.nbytes, layout.scales, layout.codes, 0, 0
+
+
+def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
+                      momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
+                      nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
+                      key_rank=0, lr_tensor=None, slots=None):
+    """``grad_out = grad_scale * sum over the rows of recv (rank order) of +/- scale`` and / or the
+    fused SGD step on ``param`` (``mom`` None: a step without momentum).  ``slots``
+    (:class:`SignSlots`, also ``dp``): ``recv`` is the two-stage exchange's gathered ``[N, P]``
+    buffer, every chunk read once from its slot (``layout`` unused)."""
+    C = require()
+    nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
     apply = param is not None
     if apply:
         _check_bucket(dp, param, "param")
@@ -438,25 +524,23 @@ def sign_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_o
     if not apply and grad_out is None:
         raise ValueError("nothing to do: pass param/mom and/or grad_out")
     _check_shadow(dp, shadow)
-    C.sign_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
-                        dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param), _ptr(mom),
+    C.sign_decode_apply(_ptr(recv), nranks, stride, _ptr(dp.chunks),
+                        dp.plan.num_chunks, so, bo, _ptr(param), _ptr(mom),
                         _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
                         grad_scale, int(nesterov), int(first), int(apply), _stream(),
                         _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
-                        _lrp(lr_tensor))
+                        _lrp(lr_tensor), sp, end)
 
 
-def sign_encode_momentum(dp: DevicePlan, grad, payload, layout, resid, exp_avg, beta1,
-                         weight_decay=0.0, param=None):
+def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
+                         weight_decay=0.0, param=None, slots=None):
     """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad
     + weight_decay * param) + resid``.  ``exp_avg``, ``param`` and the gradients are only read;
-    ``resid`` (required) is overwritten.  Bitwise ``compress/oracle.py encode_sign_momentum``."""
+    ``resid`` (required) is overwritten.  Bitwise ``compress/oracle.py encode_sign_momentum``.
+    ``slots``: as in :func:`sign_encode`."""
     C = require()
     ptrs, mask = grad_pointers(dp, grad)
-    _check_sign_layout(dp, layout)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    nbytes, so, bo, sp, end = _sign_payload(dp, payload, layout, slots)
     if resid is None or exp_avg is None:
         raise ValueError("the momentum encode needs the residual and exp_avg")
     _check_bucket(dp, resid, "resid")
@@ -467,25 +551,22 @@ def sign_encode_momentum(dp: DevicePlan, grad, payload, layout, resid, exp_avg, 
         _check_bucket(dp, param, "param")
     else:
         param = None
-    C.sign_encode_momentum(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
-                           dp.plan.num_tensors, dp.plan.num_chunks, layout.scales, layout.codes,
+    C.sign_encode_momentum(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), nbytes,
+                           dp.plan.num_tensors, dp.plan.num_chunks, so, bo,
                            _ptr(exp_avg), _ptr(param), float(beta1), float(weight_decay),
-                           _stream())
+                           _stream(), sp, end)
 
 
-def sign_decode_onebit(dp: DevicePlan, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_step,
+def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_step,
                        eps, beta1=0.9, beta2=0.999, freeze_step=1, shadow=None, step=None, lr=0.0,
-                       lr_tensor=None, key_state=None, key_seed=0, key_rank=0):
+                       lr_tensor=None, key_state=None, key_seed=0, key_rank=0, slots=None):
     """1-bit Adam's fused receive side: ``exp_avg = inv_n * sum over the rows of recv (rank order)
     of +/- scale``, then ``param -= lr_step * exp_avg / (sqrt(exp_avg_sq) + eps)`` where
     ``exp_avg_sq > 0`` (read only).  ``step`` (int32 device tensor, optional): the kernel reads t =
     step + 1 and derives ``lr_step = lr * sqrt(1 - beta2^freeze_step) / (1 - beta1^t)`` on the
-    device (``lr_step`` is then ignored)."""
+    device (``lr_step`` is then ignored).  ``slots``: as in :func:`sign_decode_apply`."""
     C = require()
-    _check_sign_layout(dp, layout)
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or recv.shape[0] < 1:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+    nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
     for t, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         if t is None:
             raise ValueError(f"the 1-bit Adam step needs {nm}")
@@ -495,12 +576,12 @@ def sign_decode_onebit(dp: DevicePlan, recv, layout, param, exp_avg, exp_avg_sq,
     if step is not None:
         _check(step, torch.int32, "step", align=4)
     _check_shadow(dp, shadow)
-    C.sign_decode_onebit(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
-                         dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param),
+    C.sign_decode_onebit(_ptr(recv), nranks, stride, _ptr(dp.chunks),
+                         dp.plan.num_chunks, so, bo, _ptr(param),
                          _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(shadow), float(lr_step),
                          float(inv_n), float(eps), float(beta1), float(beta2), int(freeze_step),
                          _ptr(step), float(lr), _lrp(lr_tensor), _stream(), _keyp(key_state),
-                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF)
+                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, sp, end)
 
 
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}

@@ -211,8 +211,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("sign_encode",
         [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
            uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
-           int bits_off, uintptr_t stream) {
+           int bits_off, uintptr_t stream, uintptr_t slots, long long slot_end) {
           SignEncodeArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.grad_ptrs = grads.data();
           a.n_grad_ptrs = (int)grads.size();
           a.bf16_mask = mask.data();
@@ -233,8 +235,10 @@ PYBIND11_MODULE(_C, m) {
         [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
            uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
            int bits_off, uintptr_t exp_avg, uintptr_t param, float beta1, float weight_decay,
-           uintptr_t stream) {
+           uintptr_t stream, uintptr_t slots, long long slot_end) {
           SignEncodeArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.grad_ptrs = grads.data();
           a.n_grad_ptrs = (int)grads.size();
           a.bf16_mask = mask.data();
@@ -256,13 +260,36 @@ PYBIND11_MODULE(_C, m) {
           ew_sign_encode(a);
         });
 
+  m.def("sign_reduce_encode",
+        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
+           int bits_off, float inv_n, uintptr_t sresid, uintptr_t out, long long out_bytes,
+           uintptr_t stream) {
+          SignReduceArgs a{};
+          a.recv = recv;
+          a.chunks = chunks;
+          a.sresid = sresid;
+          a.out = out;
+          a.stream = stream;
+          a.stride = stride;
+          a.out_bytes = out_bytes;
+          a.nranks = nranks;
+          a.num_chunks = C;
+          a.scales_off = scales_off;
+          a.bits_off = bits_off;
+          a.inv_n = inv_n;
+          ew_sign_reduce_encode(a);
+        });
+
   m.def("sign_decode_onebit",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
            int bits_off, uintptr_t param, uintptr_t exp_avg, uintptr_t exp_avg_sq,
            uintptr_t shadow, float lr_step, float inv_n, float eps, float beta1, float beta2,
            int freeze_step, uintptr_t step, double lr, uintptr_t lr_ptr, uintptr_t stream,
-           uintptr_t key_state, uint32_t key_seed, uint32_t key_rank) {
+           uintptr_t key_state, uint32_t key_seed, uint32_t key_rank, uintptr_t slots,
+           long long slot_end) {
           SignOnebitArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.recv = recv;
           a.chunks = chunks;
           a.param = param;
@@ -295,8 +322,11 @@ PYBIND11_MODULE(_C, m) {
            int bits_off, uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
            float lr, float momentum, float dampening, float weight_decay, float grad_scale,
            int nesterov, int first, int apply, uintptr_t stream, uintptr_t key_state,
-           uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr) {
+           uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr, uintptr_t slots,
+           long long slot_end) {
           SignDecodeArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.lr_ptr = lr_ptr;
           a.key_state = key_state;
           a.key_seed = key_seed;

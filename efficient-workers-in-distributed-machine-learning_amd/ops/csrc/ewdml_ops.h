@@ -104,6 +104,22 @@ struct SignEncodeArgs {
   // exp_avg * beta1 + (1 - beta1) * (g + wd * param) + resid; exp_avg and param are only read
   uintptr_t mom_exp_avg, mom_param;
   float mom_beta1, mom_wd;
+  // slot-addressed form (slots != 0; the two-stage exchange): int2 per chunk = byte offsets of its
+  // scale and of its 256 words in `payload`, an [N, P] row buffer of payload_bytes bytes; slot_end
+  // = the largest offset a slot reaches.  scales_off / bits_off are unused and no pad is written
+  uintptr_t slots;
+  long long slot_end;
+};
+
+// the two-stage exchange's owner step (sign_codec.hip k_sign_reduce_encode): the rows of recv
+// (stride bytes apart, the shard's layout in each) summed in rank order, times inv_n, plus the
+// server residual, re-encoded into `out` (same layout); sresid is updated in place
+struct SignReduceArgs {
+  uintptr_t recv, chunks, sresid, out, stream;
+  long long stride, out_bytes;
+  int nranks, num_chunks;
+  int scales_off, bits_off;
+  float inv_n;
 };
 
 // 1-bit Adam's fused decode -> exp_avg = mean -> frozen-variance step (sign_codec.hip)
@@ -119,6 +135,8 @@ struct SignOnebitArgs {
   uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
   uintptr_t key_state;  // see TopkDecodeArgs
   uint32_t key_seed, key_rank;
+  uintptr_t slots;  // see SignEncodeArgs: recv is the gathered row buffer (stride = its bytes),
+  long long slot_end;  // nranks must be 1
 };
 
 struct SignDecodeArgs {
@@ -131,6 +149,8 @@ struct SignDecodeArgs {
   uintptr_t key_state;  // see TopkDecodeArgs
   uint32_t key_seed, key_rank;
   uintptr_t lr_ptr;
+  uintptr_t slots;  // see SignOnebitArgs
+  long long slot_end;
 };
 
 struct SgdFlatArgs {
@@ -174,6 +194,7 @@ void ew_qsgd_decode_apply(const QsgdDecodeArgs& a);
 void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
+void ew_sign_reduce_encode(const SignReduceArgs& a);
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

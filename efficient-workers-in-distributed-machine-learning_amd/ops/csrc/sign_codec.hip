@@ -18,6 +18,13 @@
 // k_sign_encode<true, true> forms the momentum candidate in front of the same encode, and
 // k_sign_decode_onebit writes the averaged momentum and takes the frozen-variance step
 // (compress/oracle.py encode_sign_momentum / onebit_adam_apply, bit for bit).
+//
+// The two-stage sign all-reduce (parallel/twostage.py) adds a slot-addressed form of all three:
+// `slots` (nullable int2 per chunk) holds the byte offsets of the chunk's scale and of its 256
+// words inside an [N, P] row buffer (row r = shard r's scales | bits), so one launch covers every
+// shard of a bucket.  Pads of that buffer are zero at allocation and never written.  Its owner
+// step, k_sign_reduce_encode, decodes the N received rows of a shard straight into the encode's
+// register layout (compress/oracle.py sign_reduce_encode, bit for bit).
 #include "common.h"
 #include "ewdml_ops.h"
 
@@ -31,12 +38,73 @@ struct SignMom {
   float beta1, wd;
 };
 
+// Byte offsets of a chunk's scale and of its first word: the bucket's own layout, or the slot table
+__device__ __forceinline__ void ew_sign_where(const int2* __restrict__ slots, int scales_off,
+                                              int bits_off, size_t& scale_at, size_t& words_at) {
+  if (slots) {
+    const int2 sl = slots[blockIdx.x];
+    scale_at = (size_t)sl.x;
+    words_at = (size_t)sl.y;
+  } else {
+    scale_at = (size_t)scales_off + 4 * (size_t)blockIdx.x;
+    words_at = (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS;
+  }
+}
+
+// The encode of the chunk held in e (0 past len): the fixed-order sum of |e|, the scale, the
+// packed words, and e left as the residual e -/+ scale.  wsf / s_scale: the block's LDS.
+__device__ __forceinline__ void ew_sign_pack(float4 (&e)[EW_CU], int len, float* scale_out,
+                                             uint32_t* words, float* wsf, float* s_scale) {
+  float s = 0.0f;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    s = s + fabsf(e[u].x);
+    s = s + fabsf(e[u].y);
+    s = s + fabsf(e[u].z);
+    s = s + fabsf(e[u].w);
+  }
+  const float total = ew_block_sum(s, wsf);
+  if (threadIdx.x == 0) {
+    const float sc = total / (float)len;
+    *s_scale = sc;
+    *scale_out = sc;
+  }
+  __syncthreads();
+  const float scale = *s_scale;
+
+  // thread t holds elements 4t .. 4t + 3 of each slab: a nibble of word u * 32 + (t >> 3).  The 8
+  // lanes of a word OR their nibbles together (all 8 end up with the word); lane k of the group
+  // then stores slab k's word, so the block's 256 words go out as one dword store per thread.
+  const int k = threadIdx.x & 7;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    uint32_t w = (uint32_t)(e[u].x < 0.0f) | ((uint32_t)(e[u].y < 0.0f) << 1) |
+                 ((uint32_t)(e[u].z < 0.0f) << 2) | ((uint32_t)(e[u].w < 0.0f) << 3);
+    w <<= 4 * k;
+    w |= __shfl_xor(w, 1, 64);
+    w |= __shfl_xor(w, 2, 64);
+    w |= __shfl_xor(w, 4, 64);
+    mine = (u == k) ? w : mine;
+  }
+  words[k * (EW_BLOCK / 8) + (threadIdx.x >> 3)] = mine;
+
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    e[u].x = e[u].x - (e[u].x < 0.0f ? -scale : scale);
+    e[u].y = e[u].y - (e[u].y < 0.0f ? -scale : scale);
+    e[u].z = e[u].z - (e[u].z < 0.0f ? -scale : scale);
+    e[u].w = e[u].w - (e[u].w < 0.0f ? -scale : scale);
+  }
+}
+
 template <bool EF, bool MOM>
 __global__ __launch_bounds__(EW_BLOCK) void k_sign_encode(GradPtrs gp, float* __restrict__ resid,
                                                           const ChunkRow* __restrict__ chunks,
                                                           uint8_t* __restrict__ payload,
                                                           int scales_off, int bits_off,
-                                                          SignMom mo) {
+                                                          SignMom mo,
+                                                          const int2* __restrict__ slots) {
   __shared__ float wsf[EW_WAVES];
   __shared__ float s_scale;
   const ChunkRow c = chunks[blockIdx.x];
@@ -66,77 +134,32 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_encode(GradPtrs gp, float* __
     for (int u = 0; u < EW_CU; ++u)
       e[u] = make_float4(e[u].x + r[u].x, e[u].y + r[u].y, e[u].z + r[u].z, e[u].w + r[u].w);
   }
-  float s = 0.0f;
-#pragma unroll
-  for (int u = 0; u < EW_CU; ++u) {
-    s = s + fabsf(e[u].x);
-    s = s + fabsf(e[u].y);
-    s = s + fabsf(e[u].z);
-    s = s + fabsf(e[u].w);
-  }
-  const float total = ew_block_sum(s, wsf);
-  if (threadIdx.x == 0) {
-    const float sc = total / (float)c.len;
-    s_scale = sc;
-    reinterpret_cast<float*>(payload + scales_off)[blockIdx.x] = sc;
-  }
-  if (blockIdx.x == 0) {  // the scales section's alignment pad: payloads compare bytewise
-    const int slots = (bits_off - scales_off) >> 2;
-    for (int i = (int)gridDim.x + (int)threadIdx.x; i < slots; i += EW_BLOCK)
+  if (!slots && blockIdx.x == 0) {  // the scales section's alignment pad: payloads compare bytewise
+    const int nslots = (bits_off - scales_off) >> 2;
+    for (int i = (int)gridDim.x + (int)threadIdx.x; i < nslots; i += EW_BLOCK)
       reinterpret_cast<float*>(payload + scales_off)[i] = 0.0f;
   }
-  __syncthreads();
-  const float scale = s_scale;
-
-  // thread t holds elements 4t .. 4t + 3 of each slab: a nibble of word u * 32 + (t >> 3).  The 8
-  // lanes of a word OR their nibbles together (all 8 end up with the word); lane k of the group
-  // then stores slab k's word, so the block's 256 words go out as one dword store per thread.
-  const int k = threadIdx.x & 7;
-  uint32_t mine = 0;
-#pragma unroll
-  for (int u = 0; u < EW_CU; ++u) {
-    uint32_t w = (uint32_t)(e[u].x < 0.0f) | ((uint32_t)(e[u].y < 0.0f) << 1) |
-                 ((uint32_t)(e[u].z < 0.0f) << 2) | ((uint32_t)(e[u].w < 0.0f) << 3);
-    w <<= 4 * k;
-    w |= __shfl_xor(w, 1, 64);
-    w |= __shfl_xor(w, 2, 64);
-    w |= __shfl_xor(w, 4, 64);
-    mine = (u == k) ? w : mine;
-  }
-  uint32_t* words = reinterpret_cast<uint32_t*>(payload + bits_off) + (size_t)blockIdx.x * EW_BM_WORDS;
-  words[k * (EW_BLOCK / 8) + (threadIdx.x >> 3)] = mine;
-
-  if (EF) {
-#pragma unroll
-    for (int u = 0; u < EW_CU; ++u) {
-      e[u].x = e[u].x - (e[u].x < 0.0f ? -scale : scale);
-      e[u].y = e[u].y - (e[u].y < 0.0f ? -scale : scale);
-      e[u].z = e[u].z - (e[u].z < 0.0f ? -scale : scale);
-      e[u].w = e[u].w - (e[u].w < 0.0f ? -scale : scale);
-    }
-    ew_st_chunk(resid + c.start, c.len, e);
-  }
+  size_t scale_at, words_at;
+  ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
+  ew_sign_pack(e, c.len, reinterpret_cast<float*>(payload + scale_at),
+               reinterpret_cast<uint32_t*>(payload + words_at), wsf, &s_scale);
+  if (EF) ew_st_chunk(resid + c.start, c.len, e);
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
-    const uint8_t* __restrict__ recv, int nranks, long long stride,
-    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
-    float* __restrict__ mom, float* __restrict__ grad_out, uint16_t* __restrict__ shadow,
-    SgdArgs sa, int apply) {
-  const ChunkRow c = chunks[blockIdx.x];
-  ew_sgd_resolve(sa);
-  ew_key_advance(sa);
+// The rank-ordered sum, from 0.0f, of +/- scale_r over the rows of recv for this block's chunk:
+// acc[u][j] is element ew_chunk_idx(u) + j, which is the encode's e[u] layout.
+__device__ __forceinline__ void ew_sign_acc(const uint8_t* __restrict__ recv, int nranks,
+                                            long long stride, size_t scale_at, size_t words_at,
+                                            float (&acc)[EW_CU][4]) {
   const int shift = 4 * (threadIdx.x & 7);
-  const size_t word0 = (size_t)blockIdx.x * EW_BM_WORDS + (threadIdx.x >> 3);
-  float acc[EW_CU][4];
 #pragma unroll
   for (int u = 0; u < EW_CU; ++u)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[u][j] = 0.0f;
   for (int r = 0; r < nranks; ++r) {
     const uint8_t* pay = recv + r * stride;
-    const float scale = reinterpret_cast<const float*>(pay + scales_off)[blockIdx.x];
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(pay + bits_off) + word0;
+    const float scale = *reinterpret_cast<const float*>(pay + scale_at);
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(pay + words_at) + (threadIdx.x >> 3);
     uint32_t w[EW_CU];
 #pragma unroll
     for (int u = 0; u < EW_CU; ++u) w[u] = words[u * (EW_BLOCK / 8)];
@@ -147,6 +170,60 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
       for (int j = 0; j < 4; ++j) acc[u][j] = acc[u][j] + (((nib >> j) & 1u) ? -scale : scale);
     }
   }
+}
+
+// The two-stage exchange's owner step for one shard: e = (sum over the N received rows) * inv_n +
+// server residual, formed in registers, then the encode of e into the owner's row.  Reads the
+// received rows and the server residual; writes the owner's row (scales and words only: its pads
+// stay as allocated) and the server residual.  chunks / sresid are relative to the shard's start.
+__global__ __launch_bounds__(EW_BLOCK) void k_sign_reduce_encode(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float inv_n,
+    float* __restrict__ sresid, uint8_t* __restrict__ out) {
+  __shared__ float wsf[EW_WAVES];
+  __shared__ float s_scale;
+  const ChunkRow c = chunks[blockIdx.x];
+  size_t scale_at, words_at;
+  ew_sign_where(nullptr, scales_off, bits_off, scale_at, words_at);
+  float acc[EW_CU][4];
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
+  float4 e[EW_CU];
+  const float* sr = sresid + c.start;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const int i = ew_chunk_idx(u);
+    float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (i + 3 < c.len) {
+      const float4 r4 = *reinterpret_cast<const float4*>(sr + i);
+      r[0] = r4.x; r[1] = r4.y; r[2] = r4.z; r[3] = r4.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i + j < c.len) r[j] = sr[i + j];
+    }
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)  // padding bits decode to +scale: positions past c.len are 0
+      v[j] = (i + j < c.len) ? (acc[u][j] * inv_n + r[j]) : 0.0f;
+    e[u] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  ew_sign_pack(e, c.len, reinterpret_cast<float*>(out + scale_at),
+               reinterpret_cast<uint32_t*>(out + words_at), wsf, &s_scale);
+  ew_st_chunk(sresid + c.start, c.len, e);
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
+    float* __restrict__ mom, float* __restrict__ grad_out, uint16_t* __restrict__ shadow,
+    SgdArgs sa, int apply, const int2* __restrict__ slots) {
+  const ChunkRow c = chunks[blockIdx.x];
+  ew_sgd_resolve(sa);
+  ew_key_advance(sa);
+  size_t scale_at, words_at;
+  ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
+  float acc[EW_CU][4];
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
   float* p = param + c.start;
   float* b = mom ? mom + c.start : nullptr;
   float* go = grad_out ? grad_out + c.start : nullptr;
@@ -206,7 +283,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_onebit(
     const uint8_t* __restrict__ recv, int nranks, long long stride,
     const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
     float* __restrict__ mom, const float* __restrict__ var, uint16_t* __restrict__ shadow,
-    OnebitArgs oa, SgdArgs key) {
+    OnebitArgs oa, SgdArgs key, const int2* __restrict__ slots) {
   const ChunkRow c = chunks[blockIdx.x];
   if (oa.step) {
     const double t = (double)(*oa.step + 1);
@@ -215,27 +292,10 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_onebit(
                          (1.0 - pow((double)oa.beta1, t)));
   }
   ew_key_advance(key);
-  const int shift = 4 * (threadIdx.x & 7);
-  const size_t word0 = (size_t)blockIdx.x * EW_BM_WORDS + (threadIdx.x >> 3);
+  size_t scale_at, words_at;
+  ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
   float acc[EW_CU][4];
-#pragma unroll
-  for (int u = 0; u < EW_CU; ++u)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[u][j] = 0.0f;
-  for (int r = 0; r < nranks; ++r) {
-    const uint8_t* pay = recv + r * stride;
-    const float scale = reinterpret_cast<const float*>(pay + scales_off)[blockIdx.x];
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(pay + bits_off) + word0;
-    uint32_t w[EW_CU];
-#pragma unroll
-    for (int u = 0; u < EW_CU; ++u) w[u] = words[u * (EW_BLOCK / 8)];
-#pragma unroll
-    for (int u = 0; u < EW_CU; ++u) {
-      const uint32_t nib = w[u] >> shift;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[u][j] = acc[u][j] + (((nib >> j) & 1u) ? -scale : scale);
-    }
-  }
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
   float* p = param + c.start;
   float* b = mom + c.start;
   const float* vq = var + c.start;
@@ -274,13 +334,26 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_onebit(
 #define EW_LAUNCH(kern, grid, stream, ...) \
   hipLaunchKernelGGL(kern, dim3(grid), dim3(EW_BLOCK), 0, (hipStream_t)(stream), __VA_ARGS__)
 
+// The payload sections (or, slot-addressed, every slot of the table: slot_end is the largest byte
+// offset any of them reaches, from the host copy of the table) must lie inside `bytes`.
+static void ew_sign_fit(const std::string& who, uintptr_t slots, long long slot_end, int scales_off,
+                        int bits_off, int C, long long bytes) {
+  if (slots) {
+    if (slot_end < 4LL * EW_BM_WORDS + 4 || slot_end > bytes || slot_end > 0x7fffffffLL)
+      throw std::runtime_error(who + ": the slot table does not fit the row buffer");
+    return;
+  }
+  if (scales_off < 0 || scales_off % 16 || bits_off % 16 || bits_off < scales_off + 4LL * C ||
+      bytes < bits_off + 4LL * EW_BM_WORDS * C)
+    throw std::runtime_error(who + ": payload sections do not fit the payload");
+}
+
 void ew_sign_encode(const SignEncodeArgs& a) {
   const int C = a.num_chunks;
   if (C <= 0) throw std::runtime_error("ewdml sign: empty bucket");
-  if (a.scales_off % 16 || a.bits_off % 16 || a.bits_off < a.scales_off + 4LL * C ||
-      a.payload_bytes < a.bits_off + 4LL * EW_BM_WORDS * C)
-    throw std::runtime_error("ewdml sign: payload sections do not fit the payload");
+  ew_sign_fit("ewdml sign", a.slots, a.slot_end, a.scales_off, a.bits_off, C, a.payload_bytes);
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
+  auto* slots = reinterpret_cast<const int2*>(a.slots);
   GradPtrs g;
   ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
   float* resid = reinterpret_cast<float*>(a.resid);
@@ -292,23 +365,38 @@ void ew_sign_encode(const SignEncodeArgs& a) {
     if (mo.wd != 0.0f && !mo.p)
       throw std::runtime_error("ewdml sign: weight decay needs the parameters");
     EW_LAUNCH((k_sign_encode<true, true>), C, a.stream, g, resid, chunks, pay, a.scales_off,
-              a.bits_off, mo);
+              a.bits_off, mo, slots);
   } else if (resid) {
     EW_LAUNCH((k_sign_encode<true, false>), C, a.stream, g, resid, chunks, pay, a.scales_off,
-              a.bits_off, mo);
+              a.bits_off, mo, slots);
   } else {
     EW_LAUNCH((k_sign_encode<false, false>), C, a.stream, g, resid, chunks, pay, a.scales_off,
-              a.bits_off, mo);
+              a.bits_off, mo, slots);
   }
+  EW_CHECK_LAUNCH();
+}
+
+void ew_sign_reduce_encode(const SignReduceArgs& a) {
+  const int C = a.num_chunks;
+  if (C <= 0 || a.nranks <= 0 || a.nranks > EW_MAX_RANKS)
+    throw std::runtime_error("ewdml sign reduce: nothing to reduce, or too many ranks");
+  ew_sign_fit("ewdml sign reduce", 0, 0, a.scales_off, a.bits_off, C, a.stride);
+  ew_sign_fit("ewdml sign reduce", 0, 0, a.scales_off, a.bits_off, C, a.out_bytes);
+  if (!a.recv || !a.out || !a.sresid || !a.chunks)
+    throw std::runtime_error("ewdml sign reduce: needs the received rows, the server residual "
+                             "and the owner's row");
+  EW_LAUNCH(k_sign_reduce_encode, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv), a.nranks,
+            a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
+            a.inv_n, reinterpret_cast<float*>(a.sresid), reinterpret_cast<uint8_t*>(a.out));
   EW_CHECK_LAUNCH();
 }
 
 void ew_sign_decode_onebit(const SignOnebitArgs& a) {
   const int C = a.num_chunks;
   if (C <= 0 || a.nranks <= 0) throw std::runtime_error("ewdml 1-bit Adam: nothing to decode");
-  if (a.scales_off % 16 || a.bits_off % 16 || a.bits_off < a.scales_off + 4LL * C ||
-      a.stride < a.bits_off + 4LL * EW_BM_WORDS * C)
-    throw std::runtime_error("ewdml 1-bit Adam: payload sections do not fit the payload");
+  if (a.slots && a.nranks != 1)
+    throw std::runtime_error("ewdml 1-bit Adam: the slot-addressed decode reads one row buffer");
+  ew_sign_fit("ewdml 1-bit Adam", a.slots, a.slot_end, a.scales_off, a.bits_off, C, a.stride);
   if (!a.param || !a.exp_avg || !a.exp_avg_sq)
     throw std::runtime_error("ewdml 1-bit Adam: the step needs param, exp_avg and exp_avg_sq");
   if (a.freeze_step < 1) throw std::runtime_error("ewdml 1-bit Adam: freeze_step must be >= 1");
@@ -323,16 +411,16 @@ void ew_sign_decode_onebit(const SignOnebitArgs& a) {
             a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
             reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.exp_avg),
             reinterpret_cast<const float*>(a.exp_avg_sq), reinterpret_cast<uint16_t*>(a.shadow),
-            oa, key);
+            oa, key, reinterpret_cast<const int2*>(a.slots));
   EW_CHECK_LAUNCH();
 }
 
 void ew_sign_decode_apply(const SignDecodeArgs& a) {
   const int C = a.num_chunks;
   if (C <= 0 || a.nranks <= 0) throw std::runtime_error("ewdml sign decode: nothing to decode");
-  if (a.scales_off % 16 || a.bits_off % 16 || a.bits_off < a.scales_off + 4LL * C ||
-      a.stride < a.bits_off + 4LL * EW_BM_WORDS * C)
-    throw std::runtime_error("ewdml sign decode: payload sections do not fit the payload");
+  if (a.slots && a.nranks != 1)
+    throw std::runtime_error("ewdml sign decode: the slot-addressed decode reads one row buffer");
+  ew_sign_fit("ewdml sign decode", a.slots, a.slot_end, a.scales_off, a.bits_off, C, a.stride);
   if (a.apply && !a.param) throw std::runtime_error("ewdml sign decode: apply needs the parameters");
   if (!a.apply && !a.grad_out) throw std::runtime_error("ewdml sign decode: nothing to write");
   if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
@@ -344,6 +432,6 @@ void ew_sign_decode_apply(const SignDecodeArgs& a) {
             a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
             reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
             reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
-            a.apply);
+            a.apply, reinterpret_cast<const int2*>(a.slots));
   EW_CHECK_LAUNCH();
 }

@@ -29,6 +29,7 @@ from ..parallel.flat import FlatModel
 from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
 from ..parallel.sharded import ShardedPSExchange
+from ..parallel.twostage import TwoStageSignExchange
 from ..utils import checkpoint as ckpt
 from ..utils.metrics import MetricsLogger, accuracy, byte_summary
 
@@ -200,6 +201,9 @@ class Trainer:
                                        else None)
         elif cfg.topology == "sharded":
             self.exchange = ShardedPSExchange(self.flat, self.comm, cfg.compress, self.opt, **ckw)
+        elif cfg.topology == "twostage" and cfg.optimizer != "onebit_adam":
+            self.exchange = TwoStageSignExchange(self.flat, self.comm,
+                                                 make_codec(cfg.compress, **ckw), self.opt)
         elif cfg.optimizer == "onebit_adam":
             # 1-bit Adam: two exchanges over the same flat model and optimizer -- the dense fp32
             # all-reduce of the warm-up (steps 1..T_w: FlatAdam's step) and the sign exchange of
@@ -212,7 +216,13 @@ class Trainer:
                 GradientExchange(self.flat, self.comm, make_codec(kind, **ckw), self.opt,
                                  overlap=cfg.overlap, error_feedback=ef, predivide=1.0,
                                  side_stream=side, ef_mode="plain")
-                for kind, ef in (("none", False), ("sign", True)))
+                for kind, ef in (("none", False), ("sign", True))[:1 if cfg.topology == "twostage"
+                                                                  else 2])
+            if cfg.topology == "twostage":
+                # the warm-up is unchanged; the compressed stage runs the two-stage exchange
+                # (momentum push, owner average + re-encode, 1-bit pull with inv_n = 1)
+                self._stages += (TwoStageSignExchange(self.flat, self.comm,
+                                                      make_codec("sign", **ckw), self.opt),)
             self.exchange = self._stages[1 if self.opt.frozen else 0]
         else:
             # captured steps keep the encode + collectives on the step's own stream: a side-stream
@@ -250,7 +260,9 @@ class Trainer:
         # and the sharded exchange (graph A: forward, backward, push encodes -> eager all-to-all,
         # owner average + re-encode, all-gather -> graph B: decode + update)
         ps_split = ((isinstance(self.exchange, PSExchange) and self.exchange.k == self.world - 1)
-                    or isinstance(self.exchange, ShardedPSExchange))
+                    or isinstance(self.exchange, ShardedPSExchange)
+                    # 1-bit Adam's dense warm-up runs split too: one graph mode for both stages
+                    or cfg.topology == "twostage")
         self.ps_graph = ps_split
         if self.graph_mode == "auto":
             # graphs wherever the step can be captured: the all-to-all exchange, local SGD's
@@ -260,6 +272,8 @@ class Trainer:
             # update); the k-of-n arrival polling stays eager
             if self.graph_plan is not None:
                 self.graph_mode = self.graph_plan["mode"]
+            elif cfg.topology == "twostage":
+                self.graph_mode = "split"
             elif isinstance(self.exchange, GradientExchange) or self.local_sgd:
                 self.graph_mode = "full"
             else:
@@ -956,8 +970,8 @@ class Trainer:
         extra = {"config": {k: v for k, v in vars(self.cfg).items()
                             if isinstance(v, (int, float, str, bool)) or v is None},
                  "world": self.world}
-        for name, attr in (("ef_residual", "resid"), ("ef_velocity", "vel"),
-                           ("ef_global", "gest")):
+        for name, attr in (("ef_residual", "resid"), ("ef_server_residual", "sresid"),
+                           ("ef_velocity", "vel"), ("ef_global", "gest")):
             r = getattr(inner, attr, None)
             if r is not None:
                 # error-feedback residual / DGC velocity are per-rank state: keep every rank's row
@@ -1014,8 +1028,8 @@ class Trainer:
         self.epoch = int(st["epoch"])
         self._select_stage()  # 1-bit Adam past its freeze step: the residual's exchange
         inner = getattr(self.exchange, "inner", self.exchange)
-        for name, attr in (("ef_residual", "resid"), ("ef_velocity", "vel"),
-                           ("ef_global", "gest")):
+        for name, attr in (("ef_residual", "resid"), ("ef_server_residual", "sresid"),
+                           ("ef_velocity", "vel"), ("ef_global", "gest")):
             r = st["extra"].get(name)
             mine = getattr(inner, attr, None)
             if r is not None and mine is not None:
