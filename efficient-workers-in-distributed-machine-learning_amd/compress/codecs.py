@@ -9,6 +9,9 @@
   * ``topk_qsgd`` -- top-k then QSGD (Method 5); the flagship codec
   * ``sign``  -- scaled sign, 1 bit per element plus one fp32 scale per 8192-element chunk
     (1-bit SGD / EF-signSGD); meant to run with error feedback, which the all-gather exchange keeps
+  * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
+    al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
+    methods below)
 
 Device tensors go through the HIP kernels (``ops``); CPU tensors through the torch oracle.  On a
 GPU box a missing extension raises instead of silently falling back.
@@ -23,18 +26,23 @@ from .. import ops
 # variants before they have kernels; needs flat gradient views, EWDML_GRAD_VIEWS=1)
 _FORCE_ORACLE = os.environ.get("EWDML_ORACLE") == "1"
 from . import oracle
-from .plan import BucketPlan, Layout
+from .plan import POWERSGD_RANKS, BucketPlan, Layout
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign")
+KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd")
 
 
 class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
-                 bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0):
+                 bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
+                 rank: int = 4):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
-        if kind != "sign" and bits not in (4, 8):  # the sign codec has neither bits nor levels
+        if kind == "powersgd" and rank not in POWERSGD_RANKS:
+            raise ValueError(f"PowerSGD rank must be one of {POWERSGD_RANKS}, not {rank!r}")
+        self.rank = int(rank)
+        # the sign and low-rank codecs have neither bits nor levels
+        if kind not in ("sign", "powersgd") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -69,6 +77,8 @@ class Codec:
             return f"topk{self.ratio:g}"
         if self.kind == "sign":
             return "sign1b"
+        if self.kind == "powersgd":
+            return f"powersgd-r{self.rank}"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -76,6 +86,9 @@ class Codec:
         self.device = torch.device(device)
         self.plans = list(plans)
         self._bound = {}  # ratio -> (plans, layouts, device plans): see set_ratio
+        if self.kind == "powersgd":
+            raise ValueError("the PowerSGD codec is bound by its own exchange (bind_powersgd; "
+                             "--compress powersgd on the trainer)")
         if self.allreduce:
             self.layouts = [None] * len(self.plans)
             return self
@@ -315,6 +328,69 @@ class Codec:
                 oracle.onebit_adam_apply(rows[r:r + 1, :lay.nbytes], sp, lay, param[sl],
                                          exp_avg[sl], exp_avg_sq[sl], 1.0, hp["lr_step"],
                                          hp["eps"])
+
+    # -- PowerSGD (parallel/powersgd.py): four launches per bucket --------------------------------
+    def bind_powersgd(self, lr_plans, device):
+        """Bind the buckets' :class:`LowRankPlan` s (and, on the GPU, their device tables)."""
+        if self.kind != "powersgd":
+            raise ValueError("the PowerSGD exchange needs the powersgd codec")
+        if any(p.rank != self.rank for p in lr_plans):
+            raise ValueError("plans of another rank than the codec's")
+        self.device = torch.device(device)
+        self.lr_plans = list(lr_plans)
+        self.lr_dev = None
+        if self.device.type == "cuda" and not _FORCE_ORACLE:
+            if ops.hip_required():
+                ops.require()
+            self.lr_dev = [ops.LowRankTables(p, self.device) for p in self.lr_plans]
+        return self
+
+    def ps_project(self, b: int, grad: torch.Tensor, resid: torch.Tensor, q: torch.Tensor,
+                   p: torch.Tensor):
+        """``resid <- M = grad + resid`` (compressed tensors) and ``p`` = the ``M Q`` factors of
+        bucket ``b`` followed by its dense gradients.  One launch on the GPU."""
+        if self._ts_kernel(grad):
+            ops.psgd_project(self.lr_dev[b], grad, resid, q, p)
+            return
+        lrp = self.lr_plans[b]
+        p[:lrp.p_floats].copy_(oracle.powersgd_project(grad, resid, q, lrp))
+
+    def ps_orthogonalize(self, b: int, p: torch.Tensor, inv_n: float):
+        """The summed P factors of bucket ``b`` averaged and orthogonalised in place."""
+        if self._ts_kernel(p):
+            ops.psgd_orth(self.lr_dev[b], p, inv_n)
+            return
+        oracle.powersgd_orthogonalize(p, self.lr_plans[b], inv_n)
+
+    def ps_backproject(self, b: int, resid: torch.Tensor, p: torch.Tensor, q: torch.Tensor):
+        """``q`` = the ``M^T P`` factors of bucket ``b``.  One launch on the GPU."""
+        if self._ts_kernel(p):
+            ops.psgd_backproject(self.lr_dev[b], resid, p, q)
+            return
+        lrp = self.lr_plans[b]
+        q[:lrp.q_floats].copy_(oracle.powersgd_backproject(resid, p, lrp))
+
+    def ps_decode_apply_sgd(self, b: int, resid: torch.Tensor, p: torch.Tensor, q: torch.Tensor,
+                            q_out: torch.Tensor, inv_n: float, param: torch.Tensor,
+                            mom: torch.Tensor, hp: dict, first: bool, grad_out=None, shadow=None):
+        """Reconstruct ``g^`` of bucket ``b`` from ``p`` and the summed ``q`` (``q_out = q *
+        inv_n``, the next warm start), ``resid <- M - g^`` and the fused SGD step; ``param`` None:
+        write ``g^`` to ``grad_out`` only.  One launch on the GPU."""
+        if param is not None and mom is None and hp["momentum"] != 0:
+            raise ValueError("a momentum step needs the momentum buffer")
+        if self._ts_kernel(p):
+            kw = dict(grad_out=grad_out)
+            if param is not None:
+                kw.update(param=param, mom=mom, lr=hp["lr"], momentum=hp["momentum"],
+                          dampening=hp["dampening"], weight_decay=hp["weight_decay"],
+                          nesterov=hp["nesterov"], first=first, shadow=shadow,
+                          lr_tensor=hp.get("lr_t"))
+            ops.psgd_decode_apply(self.lr_dev[b], resid, p, q, q_out, inv_n, **kw)
+            return
+        lrp = self.lr_plans[b]
+        qa = oracle.powersgd_reconstruct_apply(resid, p, q, lrp, inv_n, param, mom, hp, first,
+                                               grad_out)
+        q_out[:lrp.q_floats].copy_(qa)
 
     def decode_apply_onebit(self, b: int, recv: torch.Tensor, inv_n: float, param: torch.Tensor,
                             exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,

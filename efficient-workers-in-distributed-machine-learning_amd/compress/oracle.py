@@ -493,3 +493,107 @@ def adam_apply(p, m, v, vmax, g, lr, beta1, beta2, eps, weight_decay, step, amsg
     bc1 = 1 - beta1 ** step
     bc2 = 1 - beta2 ** step
     p.addcdiv_(m, denom, value=-lr * math.sqrt(bc2) / bc1)
+
+
+# ---------------------------------------------------------------------------------------------
+# PowerSGD (Vogels et al., NeurIPS 2019; torch's ``powerSGD_hook``): rank-r factors of the
+# error-compensated gradient matrices of one bucket (``plan.LowRankPlan``).  The CPU path and the
+# definition of the arithmetic of ``ops/csrc/powersgd.hip``.  Every function works in ``dtype``
+# on buffers of that dtype (fp32; the tests run the same code in fp64).
+# ---------------------------------------------------------------------------------------------
+POWERSGD_EPS = 1e-8  # torch's _orthogonalize_gram_schmidt epsilon
+
+
+def _psgd_block(buf, off, rows, r):
+    return buf[off:off + rows * r].view(rows, r)
+
+
+def powersgd_project(grad, resid, q, lrp, dtype=torch.float32):
+    """``resid <- M = grad + resid`` on the compressed tensors (in place; dense tensors keep no
+    residual) and the P buffer: ``P_t = M_t Q_t`` per matrix, the dense gradients in the tail."""
+    r = lrp.rank
+    p = torch.zeros(lrp.p_floats, dtype=dtype, device=grad.device)
+    for off, n, m, po, qo, _ in lrp.mats:
+        M = resid[off:off + n * m].view(n, m)
+        M.add_(grad[off:off + n * m].view(n, m).to(dtype))
+        _psgd_block(p, po, n, r).copy_(M @ _psgd_block(q, qo, m, r).to(dtype))
+    for off, numel, tail, _ in lrp.dense:
+        p[tail:tail + numel] = grad[off:off + numel].to(dtype)
+    return p
+
+
+def powersgd_orthogonalize(p, lrp, inv_n=1.0, dtype=torch.float32):
+    """In place: every P block times ``inv_n`` (the all-reduce's average), then modified
+    Gram-Schmidt over its columns in order, ``col /= (|col| + 1e-8)`` (torch's
+    ``_orthogonalize_gram_schmidt`` with its non-zero epsilon).  The dense tail is not touched."""
+    r = lrp.rank
+    inv = torch.tensor(inv_n, dtype=torch.float32).to(dtype)
+    for _, n, _, po, _, _ in lrp.mats:
+        P = _psgd_block(p, po, n, r)
+        P.mul_(inv)
+        for c in range(r):
+            col = P[:, c:c + 1]
+            col.div_(torch.sqrt((col * col).sum()) + POWERSGD_EPS)
+            if c + 1 < r:
+                rest = P[:, c + 1:]
+                rest.sub_((col * rest).sum(dim=0, keepdim=True) * col)
+    return p
+
+
+def powersgd_backproject(resid, p, lrp, dtype=torch.float32):
+    """The Q buffer: ``Q_t = M_t^T P_t`` per matrix (``resid`` holds M)."""
+    r = lrp.rank
+    q = torch.zeros(lrp.q_floats, dtype=dtype, device=p.device)
+    for off, n, m, po, qo, _ in lrp.mats:
+        M = resid[off:off + n * m].view(n, m)
+        _psgd_block(q, qo, m, r).copy_(M.t() @ _psgd_block(p, po, n, r))
+    return q
+
+
+def powersgd_reconstruct_apply(resid, p, q, lrp, inv_n=1.0, param=None, mom=None, hp=None,
+                               first=False, grad_out=None, dtype=torch.float32):
+    """``Qa = q * inv_n``; per matrix ``g^ = P Qa^T`` with ``g^[i, j] = ((P[i,0] Qa[j,0] + P[i,1]
+    Qa[j,1]) + ...)`` in ascending k, every multiply and add rounded on its own, and ``resid <- M
+    - g^``; a dense tensor's ``g^`` is its tail times ``inv_n``.  ``grad_out`` (bucket view)
+    receives ``g^``; ``param`` / ``mom`` / ``hp``: the SGD step with ``g^`` (``sgd_apply``).
+    Returns ``Qa``, the next step's warm start.  The kernel reproduces all of it bit for bit."""
+    r = lrp.rank
+    inv = torch.tensor(inv_n, dtype=torch.float32).to(dtype)
+    qa = q[:lrp.q_floats] * inv
+    pieces = []
+    for off, n, m, po, qo, _ in lrp.mats:
+        P, Q = _psgd_block(p, po, n, r), _psgd_block(qa, qo, m, r)
+        g = P[:, 0:1] * Q[:, 0][None, :]
+        for k in range(1, r):
+            g = g + P[:, k:k + 1] * Q[:, k][None, :]
+        M = resid[off:off + n * m].view(n, m)
+        M.sub_(g)
+        pieces.append((off, n * m, g.reshape(-1)))
+    for off, numel, tail, _ in lrp.dense:
+        pieces.append((off, numel, p[tail:tail + numel] * inv))
+    for off, numel, g in pieces:
+        if grad_out is not None:
+            grad_out[off:off + numel].copy_(g)
+        if param is not None:
+            sgd_apply(param[off:off + numel], None if mom is None else mom[off:off + numel], g,
+                      hp["lr"], hp["momentum"], hp["dampening"], hp["weight_decay"],
+                      hp["nesterov"], first)
+    return qa
+
+
+def powersgd_init_q(lrp, seed: int, bucket: int, dtype=torch.float32):
+    """The initial Q buffer: per matrix, counter-RNG uniforms (``rng.uniform``, key of (seed,
+    bucket, tensor)) mapped to [-1, 1), orthogonalised once.  The same on every rank."""
+    r = lrp.rank
+    q = torch.zeros(lrp.q_floats, dtype=dtype)
+    for _, _, m, _, qo, t in lrp.mats:
+        u = rng.uniform(torch.arange(m * r, dtype=torch.int64), rng.stream_key(seed, bucket, t))
+        Q = _psgd_block(q, qo, m, r)
+        Q.copy_((u * 2.0 - 1.0).to(dtype).view(m, r))
+        for c in range(r):
+            col = Q[:, c:c + 1]
+            col.div_(torch.sqrt((col * col).sum()) + POWERSGD_EPS)
+            if c + 1 < r:
+                rest = Q[:, c + 1:]
+                rest.sub_((col * rest).sum(dim=0, keepdim=True) * col)
+    return q

@@ -267,3 +267,110 @@ class TwoStagePlan:
     def slot_table(self, device) -> torch.Tensor:
         """int32 [C, 2]: byte offsets of every chunk's scale and words (csrc int2 slots)."""
         return torch.tensor(self.slots, dtype=torch.int32, device=device)
+
+
+POWERSGD_RANKS = (1, 2, 4, 8)
+# torch's powerSGD_hook min_compression_rate: a tensor viewed as [n, m] is compressed when
+# n * m >= this * r * (n + m); fixed, decided at plan time
+POWERSGD_MIN_COMPRESSION_RATE = 2
+PSGD_ROWS = 8192  # elements a project block aims at (its rows: PSGD_ROWS // m, 4..64)
+PSGD_COLS = 256  # columns of a back-project / reconstruct tile: one per thread
+PSGD_SPLIT_ROWS = 64  # fewest rows of a tile's row split ...
+PSGD_MAX_SPLITS = 16  # ... and the most splits per matrix
+
+
+class LowRankPlan:
+    """One bucket of PowerSGD (Vogels et al., NeurIPS 2019; ``parallel/powersgd.py``).
+
+    A tensor of shape ``s`` with ``len(s) >= 2`` is the matrix ``[n, m] = [s[0], numel / s[0]]``
+    and is compressed at rank r when ``n * m >= 2 r (n + m)`` (then ``min(n, m) > 2 r``: the
+    effective rank is always r); every other tensor is *dense* and travels whole.
+
+    ``mats[t] = (offset in the bucket, n, m, p_off, q_off, index in the bucket)``: the matrix's
+    ``[n, r]`` block of the P buffer and its ``[m, r]`` block of the Q buffer, row-major, packed
+    one after the other without padding.  ``dense[d] = (offset, numel, tail_off, index)``: the
+    dense tensors follow the P blocks in the P buffer (``tail_off`` is an offset into that
+    buffer), so they share its all-reduce.  ``p_floats`` = P blocks + dense tail, ``q_floats`` =
+    Q blocks.
+
+    Kernel work lists (``ops/csrc/powersgd.hip``): ``row_items`` = (0, matrix, row0, rows) row
+    groups of the project launch followed by (1, dense, start, len) copies of at most CHUNK
+    elements; ``tile_items`` = (0, matrix, column tile, row split) of the back-project and
+    reconstruct launches, followed by the same dense items.  A matrix whose rows are cut into S
+    > 1 splits owns S slabs of ``m * r`` floats (``slab_off``) and one arrival counter per column
+    tile (``tick_off``)."""
+
+    def __init__(self, bucket_plan: BucketPlan, shapes, rank: int):
+        if rank not in POWERSGD_RANKS:
+            raise ValueError(f"PowerSGD rank must be one of {POWERSGD_RANKS}, not {rank!r}")
+        shapes = [tuple(int(v) for v in s) for s in shapes]
+        if len(shapes) != bucket_plan.num_tensors:
+            raise ValueError("one shape per tensor of the bucket")
+        if bucket_plan.num_tensors > MAX_SEGMENTS:
+            raise ValueError(f"bucket has {bucket_plan.num_tensors} tensors (max {MAX_SEGMENTS})")
+        self.plan, self.rank, self.shapes = bucket_plan, rank, shapes
+        self.mats, self.dense = [], []
+        p = q = 0
+        for t, (s, off, numel) in enumerate(zip(shapes, bucket_plan.offsets, bucket_plan.numels)):
+            n = s[0] if s else 1
+            m = numel // max(n, 1)
+            if n * m != numel:
+                raise ValueError(f"shape {s} does not hold {numel} elements")
+            if len(s) >= 2 and n * m >= POWERSGD_MIN_COMPRESSION_RATE * rank * (n + m):
+                self.mats.append((off, n, m, p, q, t))
+                p += n * rank
+                q += m * rank
+            else:
+                self.dense.append((off, numel, 0, t))
+        self.p_factor_floats = p
+        for d, (off, numel, _, t) in enumerate(self.dense):
+            self.dense[d] = (off, numel, p, t)
+            p += numel
+        self.p_floats, self.q_floats = p, q
+        if max(p, q, 1) >= 1 << 31:
+            raise ValueError("PowerSGD factor buffer of 2^31 floats or more: use smaller buckets")
+        # work lists
+        dense_items = [(1, d, s0, min(CHUNK, numel - s0))
+                       for d, (_, numel, _, _) in enumerate(self.dense)
+                       for s0 in range(0, numel, CHUNK)]
+        self.row_items, self.tile_items, self.split = [], [], []
+        slab = tick = 0
+        for i, (_, n, m, _, _, _) in enumerate(self.mats):
+            rows = max(4, min(64, PSGD_ROWS // m))
+            self.row_items += [(0, i, r0, min(rows, n - r0)) for r0 in range(0, n, rows)]
+            per = max(PSGD_SPLIT_ROWS, -(-n // PSGD_MAX_SPLITS))
+            S, tiles = -(-n // per), -(-m // PSGD_COLS)
+            self.split.append((per, S, slab if S > 1 else -1, tick if S > 1 else -1))
+            if S > 1:
+                slab += S * m * rank
+                tick += tiles
+            self.tile_items += [(0, i, jt, z) for jt in range(tiles) for z in range(S)]
+        self.num_mat_tiles = len(self.tile_items)
+        self.row_items += dense_items
+        self.tile_items += dense_items
+        self.slab_floats, self.num_tickets = slab, tick
+
+    @property
+    def compressed(self):
+        """Indices (in the bucket) of the compressed tensors."""
+        return [t for *_, t in self.mats]
+
+    def mat_table(self, device) -> torch.Tensor:
+        """int32 [max(1, T_m), 12]: offset, n, m, p_off, q_off, rows per split, splits, slab_off,
+        tick_off, 0, 0, 0 (csrc PsgdMat)."""
+        rows = [[off, n, m, p, q, per, S, so, to, 0, 0, 0]
+                for (off, n, m, p, q, _), (per, S, so, to) in zip(self.mats, self.split)]
+        return torch.tensor(rows or [[0] * 12], dtype=torch.int32, device=device)
+
+    def dense_table(self, device) -> torch.Tensor:
+        """int32 [max(1, T_d), 4]: offset, numel, offset in the P buffer, 0 (csrc PsgdDense)."""
+        rows = [[off, numel, tail, 0] for off, numel, tail, _ in self.dense]
+        return torch.tensor(rows or [[0] * 4], dtype=torch.int32, device=device)
+
+    def row_table(self, device) -> torch.Tensor:
+        """int32 [W, 4]: the project launch's work items (one block each)."""
+        return torch.tensor(self.row_items, dtype=torch.int32, device=device)
+
+    def tile_table(self, device) -> torch.Tensor:
+        """int32 [W, 4]: the back-project (first ``num_mat_tiles``) and reconstruct items."""
+        return torch.tensor(self.tile_items, dtype=torch.int32, device=device)

@@ -58,7 +58,8 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    compress: str = "topk_qsgd"  # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign
+    compress: str = "topk_qsgd"  # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd
+    powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
     qsgd_levels: int = 127
@@ -188,7 +189,8 @@ class Config:
             # top-k runs keep the reference's schedule (no EF warm-up) and record no EF
             c.error_feedback = ((c.compress in ("topk", "topk_qsgd", "sign")
                                  and c.topology == "allgather")
-                                or (c.compress == "sign" and c.topology == "twostage"))
+                                or (c.compress == "sign" and c.topology == "twostage")
+                                or c.compress == "powersgd")
         if c.topology == "twostage":
             # the two-stage sign all-reduce (parallel/twostage.py): both of its quantisations
             # are error-compensated, and the owners average with 1/N
@@ -218,6 +220,36 @@ class Config:
                              "not run with --topology ps / sharded, --sync-every > 1 or "
                              "--select-best (those exchanges keep no error feedback); "
                              "--topology twostage is the sign codec's sharded exchange")
+        if c.compress == "powersgd":
+            # PowerSGD (parallel/powersgd.py): two dependent all-reduces of rank-r factors per
+            # bucket, always with its residual, averaged with 1/N inside its kernels
+            why = None
+            if c.powersgd_rank not in (1, 2, 4, 8):
+                why = f"supports ranks 1, 2, 4 and 8, not --powersgd-rank {c.powersgd_rank}"
+            elif c.topology != "allgather":
+                why = (f"averages its factors by all-reduce on every rank: it does not run with "
+                       f"--topology {c.topology}")
+            elif c.sync_every > 1:
+                why = "exchanges every step: it does not run with --sync-every > 1"
+            elif c.select_best:
+                why = "averages all workers: it does not run with --select-best"
+            elif not c.error_feedback:
+                why = ("is a biased compressor that relies on its residual: it does not run with "
+                       "--no-error-feedback")
+            elif c.predivide != 1.0:
+                why = ("averages its factors with 1/N in its kernels: it does not run with "
+                       "--predivide other than 1")
+            elif c.hip_graph in ("full", "segmented"):
+                why = (f"issues its two all-reduces, the orthogonalisation and the back-projection "
+                       f"between two graphs: --hip-graph {c.hip_graph} is not supported (auto "
+                       f"resolves to split)")
+            elif c.optimizer == "onebit_adam":
+                why = ("is not the sign codec: --optimizer onebit_adam exchanges sign-compressed "
+                       "momentum (--compress sign)")
+            if why is not None:
+                raise ValueError("--compress powersgd " + why)
+        elif c.powersgd_rank != Config.powersgd_rank:
+            raise ValueError("--powersgd-rank belongs to --compress powersgd")
         if c.optimizer == "onebit_adam":
             # the compressed stage is the sign codec's all-gather with its residual; every option
             # that changes what is exchanged, or that scales it, breaks the momentum's linearity
@@ -297,7 +329,8 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # exchange
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
-      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign"])
+      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd"])
+    a("--powersgd-rank", type=int, default=d.powersgd_rank)
     a("--topk-ratio", type=float, default=d.topk_ratio)
     a("--topk-dense-below", type=int, default=d.topk_dense_below)
     a("--qsgd-levels", type=int, default=d.qsgd_levels)

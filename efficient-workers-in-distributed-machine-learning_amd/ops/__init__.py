@@ -584,6 +584,123 @@ def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_s
                          key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, sp, end)
 
 
+class LowRankTables:
+    """Device tables, slabs and arrival counters of one bucket of PowerSGD (``compress/plan.py
+    LowRankPlan``).  The kernels trust the tables, so the host copy is checked here: every
+    matrix, dense tensor and work item must lie inside the bucket and the factor buffers."""
+
+    def __init__(self, lrp, device):
+        from ..compress.plan import CHUNK, PSGD_COLS
+
+        self.lrp, self.plan = lrp, lrp.plan
+        L, r = lrp.plan.length, lrp.rank
+        for (off, n, m, po, qo, _), (per, S, so, to) in zip(lrp.mats, lrp.split):
+            tiles = -(-m // PSGD_COLS)
+            if (off < 0 or n < 1 or m < 1 or off + n * m > L or po < 0 or qo < 0
+                    or po + n * r > lrp.p_factor_floats or qo + m * r > lrp.q_floats
+                    or per < 1 or S != -(-n // per) or (S > 1 and (
+                        so < 0 or so + S * m * r > lrp.slab_floats or to < 0
+                        or to + tiles > lrp.num_tickets))):
+                raise ValueError("PowerSGD matrix table does not fit its buffers")
+        for off, numel, tail, _ in lrp.dense:
+            if (off < 0 or numel < 1 or off + numel > L or tail < lrp.p_factor_floats
+                    or tail + numel > lrp.p_floats):
+                raise ValueError("PowerSGD dense table does not fit its buffers")
+        for items, tiled in ((lrp.row_items, False), (lrp.tile_items, True)):
+            for kind, i, a, b in items:
+                if kind == 1:
+                    good = (0 <= i < len(lrp.dense) and 0 <= a and 1 <= b <= CHUNK
+                            and a + b <= lrp.dense[i][1])
+                elif tiled:
+                    good = (0 <= i < len(lrp.mats) and 0 <= a < -(-lrp.mats[i][2] // PSGD_COLS)
+                            and 0 <= b < lrp.split[i][1])
+                else:
+                    good = 0 <= i < len(lrp.mats) and 0 <= a and b >= 1 and \
+                        a + b <= lrp.mats[i][1]
+                if not good:
+                    raise ValueError("PowerSGD work list does not fit its plan")
+        if [it[0] for it in lrp.tile_items[:lrp.num_mat_tiles]].count(0) != lrp.num_mat_tiles:
+            raise ValueError("PowerSGD tile list: the matrix items come first")
+        self.mats = lrp.mat_table(device)
+        self.dense = lrp.dense_table(device)
+        self.rows = lrp.row_table(device)
+        self.tiles = lrp.tile_table(device)
+        self.slabs = torch.zeros(max(4, lrp.slab_floats), dtype=torch.float32, device=device)
+        # zero at allocation; every back-project launch leaves them zeroed
+        self.tickets = torch.zeros(max(1, lrp.num_tickets), dtype=torch.int32, device=device)
+
+
+def _psgd_buf(t, n, name):
+    _check(t, torch.float32, name)
+    if t.numel() < n:
+        raise ValueError(f"{name} has {t.numel()} floats, the plan needs {n}")
+
+
+def _psgd(op, lt, items, num_items, grad=None, resid=None, p=None, q=None, inv_n=1.0, q_out=None,
+          param=None, mom=None, grad_out=None, shadow=None, lr_tensor=None, lr=0.0, momentum=0.0,
+          dampening=0.0, weight_decay=0.0, nesterov=False, first=False, apply=False):
+    lrp = lt.lrp
+    _psgd_buf(p, lrp.p_floats, "p")
+    for t, nm in ((grad, "grad"), (resid, "resid"), (param, "param"), (mom, "mom"),
+                  (grad_out, "grad_out")):
+        if t is not None:
+            _check_bucket(lt, t, nm)
+    for t, nm in ((q, "q"), (q_out, "q_out")):
+        if t is not None:
+            _psgd_buf(t, lrp.q_floats, nm)
+    _check_shadow(lt, shadow)
+    require().psgd(op, lrp.rank, _ptr(lt.mats), len(lrp.mats), _ptr(lt.dense), len(lrp.dense),
+                   _ptr(items), num_items, lrp.plan.length, lrp.p_floats, lrp.q_floats,
+                   _ptr(grad), _ptr(resid), _ptr(p), _ptr(q), _ptr(lt.slabs), lrp.slab_floats,
+                   _ptr(lt.tickets), lrp.num_tickets, float(inv_n), _ptr(q_out), _ptr(param),
+                   _ptr(mom), _ptr(grad_out), _ptr(shadow), _lrp(lr_tensor), float(lr),
+                   float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
+                   int(bool(first)), int(bool(apply)), _stream())
+
+
+def psgd_project(lt: LowRankTables, grad, resid, q, p):
+    """PowerSGD launch 1 (``csrc/powersgd.hip``): ``resid <- M = grad + resid`` on the compressed
+    tensors, ``p`` = the ``M Q`` factors followed by the dense tensors' gradients.  ``grad`` and
+    ``resid`` are the bucket's flat views."""
+    if grad is None or resid is None or q is None:
+        raise ValueError("the project launch needs grad, resid and q")
+    _psgd(0, lt, lt.rows, len(lt.lrp.row_items), grad=grad, resid=resid, p=p, q=q)
+
+
+def psgd_orth(lt: LowRankTables, p, inv_n: float):
+    """PowerSGD launch 2: every P block times ``inv_n``, then modified Gram-Schmidt."""
+    _psgd(1, lt, None, 0, p=p, inv_n=inv_n)
+
+
+def psgd_backproject(lt: LowRankTables, resid, p, q):
+    """PowerSGD launch 3: ``q`` = the ``M^T P`` factors (``resid`` holds M)."""
+    if resid is None or q is None:
+        raise ValueError("the back-project launch needs resid and q")
+    _psgd(2, lt, lt.tiles, lt.lrp.num_mat_tiles, resid=resid, p=p, q=q)
+
+
+def psgd_decode_apply(lt: LowRankTables, resid, p, q, q_out, inv_n, param=None, mom=None,
+                      grad_out=None, lr=0.0, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                      nesterov=False, first=False, shadow=None, lr_tensor=None):
+    """PowerSGD launch 4: ``q_out = q * inv_n``, ``g^ = P q_out^T`` (dense tensors: ``p``'s tail
+    times ``inv_n``), ``resid <- M - g^`` and the fused SGD step on ``param`` with ``g^``
+    (``param`` None: write ``g^`` to ``grad_out`` only).  Bitwise ``compress/oracle.py
+    powersgd_reconstruct_apply``."""
+    if resid is None or q is None or q_out is None:
+        raise ValueError("the reconstruct launch needs resid, q and q_out")
+    if q.data_ptr() == q_out.data_ptr():
+        raise ValueError("q_out must not be q: other blocks still read q")
+    apply = param is not None
+    if apply and mom is None and (momentum != 0.0 or nesterov):
+        raise ValueError("a momentum step needs the momentum buffer")
+    if not apply and grad_out is None:
+        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    _psgd(3, lt, lt.tiles, len(lt.lrp.tile_items), resid=resid, p=p, q=q, inv_n=inv_n,
+          q_out=q_out, param=param, mom=mom, grad_out=grad_out, shadow=shadow,
+          lr_tensor=lr_tensor, lr=lr, momentum=momentum, dampening=dampening,
+          weight_decay=weight_decay, nesterov=nesterov, first=first, apply=apply)
+
+
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 

@@ -354,6 +354,56 @@ PYBIND11_MODULE(_C, m) {
           ew_sign_decode_apply(a);
         });
 
+  // PowerSGD (powersgd.hip): op 0 = project, 1 = orth, 2 = backproject, 3 = decode_apply
+  m.def("psgd",
+        [](int op, int rank, uintptr_t mats, int num_mats, uintptr_t dense, int num_dense,
+           uintptr_t items, int num_items, long long bucket_len, long long p_floats,
+           long long q_floats, uintptr_t grad, uintptr_t resid, uintptr_t p, uintptr_t q,
+           uintptr_t slabs, long long slab_floats, uintptr_t tickets, int num_tickets,
+           float inv_n, uintptr_t q_out, uintptr_t param, uintptr_t mom, uintptr_t grad_out,
+           uintptr_t shadow, uintptr_t lr_ptr, float lr, float momentum, float dampening,
+           float weight_decay, int nesterov, int first, int apply, uintptr_t stream) {
+          PsgdArgs a{};
+          a.mats = mats;
+          a.dense = dense;
+          a.items = items;
+          a.stream = stream;
+          a.rank = rank;
+          a.num_mats = num_mats;
+          a.num_dense = num_dense;
+          a.num_items = num_items;
+          a.bucket_len = bucket_len;
+          a.p_floats = p_floats;
+          a.q_floats = q_floats;
+          a.grad = grad;
+          a.resid = resid;
+          a.p = p;
+          a.q = q;
+          a.slabs = slabs;
+          a.tickets = tickets;
+          a.slab_floats = slab_floats;
+          a.num_tickets = num_tickets;
+          a.inv_n = inv_n;
+          a.q_out = q_out;
+          a.param = param;
+          a.mom = mom;
+          a.grad_out = grad_out;
+          a.shadow = shadow;
+          a.lr_ptr = lr_ptr;
+          a.lr = lr;
+          a.momentum = momentum;
+          a.dampening = dampening;
+          a.weight_decay = weight_decay;
+          a.nesterov = nesterov;
+          a.first = first;
+          a.apply = apply;
+          if (op == 0) ew_psgd_project(a);
+          else if (op == 1) ew_psgd_orth(a);
+          else if (op == 2) ew_psgd_backproject(a);
+          else if (op == 3) ew_psgd_decode_apply(a);
+          else throw std::runtime_error("ewdml powersgd: unknown op");
+        });
+
   m.def("sgd_flat",
         [](uintptr_t param, uintptr_t mom, uintptr_t grad, uintptr_t shadow, long long n,
            int grad_dtype, float lr, float momentum, float dampening, float weight_decay,

@@ -153,6 +153,25 @@ struct SignDecodeArgs {
   long long slot_end;
 };
 
+// PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /
+// dense / items are the plan's device tables; p / q the factor buffers of p_floats / q_floats
+// fp32.  The bucket views (grad, resid, param, mom, grad_out, shadow) hold bucket_len elements.
+struct PsgdArgs {
+  uintptr_t mats, dense, items, stream;
+  int rank, num_mats, num_dense, num_items;
+  long long bucket_len, p_floats, q_floats;
+  uintptr_t grad, resid, p, q;
+  // back-project: the row splits' slabs (slab_floats fp32) and the zeroed arrival counters
+  uintptr_t slabs, tickets;
+  long long slab_floats;
+  int num_tickets;
+  // orthogonalise / reconstruct: the all-reduce's 1/N; reconstruct: q_out receives q * inv_n
+  float inv_n;
+  uintptr_t q_out, param, mom, grad_out, shadow, lr_ptr;
+  float lr, momentum, dampening, weight_decay;
+  int nesterov, first, apply;
+};
+
 struct SgdFlatArgs {
   uintptr_t param, mom, grad, shadow, stream;
   long long n;
@@ -195,6 +214,11 @@ void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
 void ew_sign_reduce_encode(const SignReduceArgs& a);
+
+void ew_psgd_project(const PsgdArgs& a);
+void ew_psgd_orth(const PsgdArgs& a);
+void ew_psgd_backproject(const PsgdArgs& a);
+void ew_psgd_decode_apply(const PsgdArgs& a);
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

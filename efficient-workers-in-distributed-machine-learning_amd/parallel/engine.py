@@ -754,7 +754,13 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
     Returns ``{"mode", "splits", "bucket_bytes", "wire_bytes", "reason"}`` (+ ``predicted_ms``)."""
     from .step_model import overlap_splits, predict, profile_for
 
-    per_elem = {"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
+    if codec_kind == "powersgd":
+        # parallel/powersgd.py: two dependent all-reduces with kernels between them, so the step
+        # is always graph A -> eager collectives -> graph B; the wire bytes depend on the
+        # tensors' shapes (LowRankPlan) and are reported by the exchange itself
+        return {"mode": "split", "splits": 1, "bucket_bytes": int(bucket_bytes), "wire_bytes": 0,
+                "reason": "PowerSGD: collectives between two graphs"}
+    per_elem ={"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
                 "sign": 1.0 / 8.0}.get(codec_kind)
     payload = grad_numel * (per_elem or 0.0)
     # top-k payload per rank (estimate): k entries of one code byte (4-bit: half) + a 2-byte index

@@ -152,6 +152,13 @@ class Compression:
         """Scaled sign, 1 bit per element; the optimizer wrapper keeps its error feedback."""
         return Codec("sign")
 
+    @staticmethod
+    def powersgd(rank: int = 4):
+        """PowerSGD rank-r factors.  Its two dependent all-reduces do not fit this wrapper's
+        exchange: ``DistributedOptimizer`` refuses it (use ``--compress powersgd`` on the
+        trainer)."""
+        return Codec("powersgd", rank=rank)
+
 
 def _as_codec(compression) -> Codec:
     if isinstance(compression, Codec):
@@ -248,6 +255,12 @@ class _DistributedOptimizer:
         self.op = op
         self.bpps = max(1, int(backward_passes_per_step))
         codec = Codec("none") if op == Adasum else _as_codec(compression)
+        if codec.kind == "powersgd":
+            # GradientExchange's encode -> one collective -> decode protocol has no place for two
+            # dependent all-reduces (as 1-bit Adam, PowerSGD runs through the trainer only)
+            raise ValueError("Compression.powersgd is not supported by DistributedOptimizer: "
+                             "PowerSGD exchanges two dependent all-reduces per bucket; train "
+                             "with --compress powersgd on the trainer (distributed_nn.py)")
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
                                          # scaled sign is biased without its residual

@@ -29,6 +29,7 @@ from ..parallel.flat import FlatModel
 from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
 from ..parallel.sharded import ShardedPSExchange
+from ..parallel.powersgd import PowerSGDExchange
 from ..parallel.twostage import TwoStageSignExchange
 from ..utils import checkpoint as ckpt
 from ..utils.metrics import MetricsLogger, accuracy, byte_summary
@@ -146,7 +147,8 @@ class Trainer:
         # pointer-mode gradients (read in place by the HIP kernels) for the all-to-all exchange
         # and local SGD (its local steps read them through the same pointer tables); the
         # parameter server keeps flat gradient views
-        ptr_grads = (self.cuda and cfg.topology == "allgather"
+        # (and PowerSGD, whose project launch reads the flat gradient buffer)
+        ptr_grads = (self.cuda and cfg.topology == "allgather" and cfg.compress != "powersgd"
                      and os.environ.get("EWDML_GRAD_VIEWS") != "1")
         bf16_params = (ptr_grads and cfg.amp == "bf16" and cfg.param_dtype == "auto"
                        and not self.amp_kept_fp32)
@@ -162,6 +164,7 @@ class Trainer:
         # here because the segmented step wants smaller buckets
         self.graph_plan = None
         if (cfg.hip_graph == "auto" and self.cuda and not cfg.sync_debug
+                and cfg.compress != "powersgd"  # always split graphs (below)
                 and cfg.topology == "allgather" and cfg.sync_every == 1 and not cfg.select_best):
             # EWDML_PLAN_AS_WORLD (test hook): plan as if the job had that many ranks, so the
             # N > 1 decision runs end to end on a one-GPU box (world of one, real communicator)
@@ -201,6 +204,10 @@ class Trainer:
                                        else None)
         elif cfg.topology == "sharded":
             self.exchange = ShardedPSExchange(self.flat, self.comm, cfg.compress, self.opt, **ckw)
+        elif cfg.compress == "powersgd":
+            self.exchange = PowerSGDExchange(self.flat, self.comm,
+                                             make_codec("powersgd", seed=cfg.seed,
+                                                        rank=cfg.powersgd_rank), self.opt)
         elif cfg.topology == "twostage" and cfg.optimizer != "onebit_adam":
             self.exchange = TwoStageSignExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt)
@@ -262,7 +269,10 @@ class Trainer:
         ps_split = ((isinstance(self.exchange, PSExchange) and self.exchange.k == self.world - 1)
                     or isinstance(self.exchange, ShardedPSExchange)
                     # 1-bit Adam's dense warm-up runs split too: one graph mode for both stages
-                    or cfg.topology == "twostage")
+                    or cfg.topology == "twostage"
+                    # PowerSGD: graph A = ..., project -> eager all-reduces, orthogonalise and
+                    # back-project -> graph B = reconstruct + step
+                    or isinstance(self.exchange, PowerSGDExchange))
         self.ps_graph = ps_split
         if self.graph_mode == "auto":
             # graphs wherever the step can be captured: the all-to-all exchange, local SGD's
@@ -272,7 +282,7 @@ class Trainer:
             # update); the k-of-n arrival polling stays eager
             if self.graph_plan is not None:
                 self.graph_mode = self.graph_plan["mode"]
-            elif cfg.topology == "twostage":
+            elif cfg.topology == "twostage" or cfg.compress == "powersgd":
                 self.graph_mode = "split"
             elif isinstance(self.exchange, GradientExchange) or self.local_sgd:
                 self.graph_mode = "full"
@@ -978,6 +988,8 @@ class Trainer:
                 allr = torch.zeros((self.world, r.numel()), dtype=r.dtype, device=r.device)
                 self.comm.all_gather(allr.view(-1), r)
                 extra[name] = allr
+        if isinstance(inner, PowerSGDExchange):
+            extra["powersgd_q"] = inner.q  # the warm start, the same on every rank: rank 0's
         if self.local_sgd:
             # between syncs every replica (and its momentum) has drifted on its own: keep every
             # rank's row, the common anchor of the model-delta exchange and the sync count (the
@@ -1037,6 +1049,8 @@ class Trainer:
                     mine.copy_(r[self.rank].to(self.device))
                 else:
                     self.log.info(f"resume: world size changed, {name} reset")
+        if isinstance(inner, PowerSGDExchange) and st["extra"].get("powersgd_q") is not None:
+            inner.q.copy_(st["extra"]["powersgd_q"].to(self.device))
         if self.local_sgd:
             ex, ext = self.exchange, st["extra"]
             rows = [(ext.get("local_params"), self.flat.data),
