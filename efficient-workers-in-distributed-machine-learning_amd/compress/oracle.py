@@ -495,6 +495,54 @@ def adam_apply(p, m, v, vmax, g, lr, beta1, beta2, eps, weight_decay, step, amsg
     p.addcdiv_(m, denom, value=-lr * math.sqrt(bc2) / bc1)
 
 
+# Layer-wise trust ratios (LARS: You et al., 2017; LAMB: You et al., ICLR 2020).  The definition
+# of ``ops/csrc/layerwise.hip``.  ``p`` / ``g`` / the state are views of one flat range and
+# ``tensors`` its ``(offset, numel, adapts)`` rows: every norm runs over a tensor's own ``numel``
+# elements, never over the alignment padding, and a tensor that does not adapt (``ndim < 2``:
+# biases, BatchNorm scales) or that has a zero norm takes ratio 1.  ``g`` is already scaled.
+# Both return the tensors' ratios (fp32).
+def _l2(x):
+    return (x * x).sum().sqrt()
+
+
+def lars_apply(p, buf, g, tensors, lr, momentum, dampening, weight_decay, nesterov, first, eta):
+    """``r = eta |p| / (|g| + wd |p|)``, then :func:`sgd_apply` on ``r (g + wd p)`` with its own
+    weight decay off."""
+    ratios = torch.ones(len(tensors), dtype=torch.float32, device=p.device)
+    for t, (off, n, adapts) in enumerate(tensors):
+        pt, gt = p[off:off + n], g[off:off + n]
+        pn, gn = _l2(pt), _l2(gt)
+        if adapts and float(pn) > 0 and float(gn) > 0:
+            ratios[t] = eta * pn / (gn + weight_decay * pn)
+        d = gt
+        if weight_decay != 0:
+            d = d + weight_decay * pt
+        d = ratios[t] * d
+        sgd_apply(pt, buf[off:off + n], d, lr, momentum, dampening, 0.0, nesterov, first)
+    return ratios
+
+
+def lamb_apply(p, m, v, g, tensors, lr, beta1, beta2, eps, weight_decay, step):
+    """Adam's moments, ``u = m^ / (sqrt(v^) + eps) + wd p``, ``r = |p| / |u|``, ``p -= lr r u``
+    (``step`` is 1-based; no clamp on ``|p|``, no gradient clipping)."""
+    bc1 = 1 - beta1 ** step
+    bc2 = 1 - beta2 ** step
+    ratios = torch.ones(len(tensors), dtype=torch.float32, device=p.device)
+    for t, (off, n, adapts) in enumerate(tensors):
+        pt, gt = p[off:off + n], g[off:off + n]
+        mt, vt = m[off:off + n], v[off:off + n]
+        mt.mul_(beta1).add_(gt, alpha=1 - beta1)
+        vt.mul_(beta2).addcmul_(gt, gt, value=1 - beta2)
+        u = (mt / bc1) / ((vt / bc2).sqrt() + eps)
+        if weight_decay != 0:
+            u = u + weight_decay * pt
+        pn, un = _l2(pt), _l2(u)
+        if adapts and float(pn) > 0 and float(un) > 0:
+            ratios[t] = pn / un
+        pt.add_(u, alpha=-(lr * float(ratios[t])))
+    return ratios
+
+
 # ---------------------------------------------------------------------------------------------
 # PowerSGD (Vogels et al., NeurIPS 2019; torch's ``powerSGD_hook``): rank-r factors of the
 # error-compensated gradient matrices of one bucket (``plan.LowRankPlan``).  The CPU path and the

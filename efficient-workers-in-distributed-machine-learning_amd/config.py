@@ -99,11 +99,14 @@ class Config:
     predivide: float = 1.0  # Horovod gradient_predivide_factor
     sync_bn: bool = False  # broadcast BN running stats from rank 0 at every checkpoint/eval
     # ---- optimizer -------------------------------------------------------------------------------
-    optimizer: str = "sgd"  # sgd | adam | amsgrad | onebit_adam (1-bit Adam: optim/flat.py)
+    # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios):
+    # optim/flat.py
+    optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / onebit_adam
     # onebit_adam: dense Adam steps before the variance is frozen and the sign-compressed
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
+    lars_eta: Optional[float] = None  # lars: trust coefficient (None: 0.001)
     weight_decay: float = 0.0
     dampening: float = 0.0
     nesterov: bool = False
@@ -268,6 +271,13 @@ class Config:
                 raise ValueError("--optimizer onebit_adam " + why)
         elif c.onebit_warmup_steps is not None:
             raise ValueError("--onebit-warmup-steps belongs to --optimizer onebit_adam")
+        if c.optimizer == "lars":
+            if c.lars_eta is None:
+                c.lars_eta = 0.001
+            if not c.lars_eta > 0:
+                raise ValueError("--lars-eta must be > 0")
+        elif c.lars_eta is not None:
+            raise ValueError("--lars-eta belongs to --optimizer lars")
         if c.ef_mode == "ef21" and c.error_feedback and c.device != "cpu" and not c.no_cuda:
             import os
 
@@ -356,9 +366,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
-      choices=["sgd", "adam", "amsgrad", "onebit_adam"])
+      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb"])
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)
+    a("--lars-eta", type=float, default=None)
     a("--weight-decay", type=float, default=d.weight_decay)
     a("--dampening", type=float, default=d.dampening)
     a("--nesterov", action="store_true", default=False)

@@ -750,6 +750,79 @@ def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, 
                 grad_scale, int(amsgrad), _stream(), _ptr(step), float(lr), _lrp(lr_tensor))
 
 
+# Longest chain of fp32 additions behind one chunk's sum of squares in k_lw_stage
+# (csrc/layerwise.hip): 32 serial terms per thread + 6 shuffle levels + 3 across the waves.  The
+# per-tensor sums over the chunks are fp64.
+LAYERWISE_SUM_CHAIN = 41
+LAYERWISE_KINDS = {"lars": 0, "lamb": 1}
+
+
+class LayerwisePlan:
+    """Device tables of one flat range (a bucket or the whole model) for the layer-wise
+    optimizers: the range's ``BucketPlan`` tables and its views of the optimizer's per-tensor
+    ``adapt`` flags (int32), ``ratio`` output (fp32) and per-chunk ``partials`` (fp32 [C, 2])."""
+
+    def __init__(self, plan, adapt, ratio, partials):
+        T, C = plan.num_tensors, plan.num_chunks
+        _check(adapt, torch.int32, "adapt", align=4)
+        _check(ratio, torch.float32, "ratio", align=4)
+        _check(partials, torch.float32, "partials", align=4)
+        if adapt.numel() != T or ratio.numel() != T or partials.numel() != 2 * C:
+            raise ValueError(f"layer-wise plan of {T} tensors / {C} chunks: adapt, ratio must "
+                             f"hold {T} entries and partials {2 * C}")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        if plan.length >= 1 << 31:
+            raise ValueError("flat range of 2^31 elements or more")
+        self.plan = plan
+        self.adapt, self.ratio, self.partials = adapt, ratio, partials
+        self.tensors = plan.tensor_table(adapt.device)
+        self.chunks = plan.chunk_table(adapt.device)
+
+
+def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=None, *, lr,
+                   weight_decay=0.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, eta=0.001,
+                   momentum=0.0, dampening=0.0, nesterov=False, first=False, t=1, step=None,
+                   lr_tensor=None, shadow=None):
+    """One LARS (``state1`` = momentum buffer) or LAMB (``state1`` / ``state2`` = ``exp_avg`` /
+    ``exp_avg_sq``) step of the flat range ``lw`` describes, in two launches: ``k_lw_stage``
+    (per-chunk sums of squares; LAMB's moments) and ``k_lw_apply`` (trust ratios -> ``lw.ratio``,
+    the step, the bf16 shadow).  ``step`` (int32 device tensor, optional): the kernels read the
+    0-based step count from it (``t = step + 1``) instead of the host's ``t`` / ``first``."""
+    C = require()
+    if kind not in LAYERWISE_KINDS:
+        raise ValueError(f"unknown layer-wise rule {kind!r}")
+    n = lw.plan.length
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    states = [(state1, "exp_avg"), (state2, "exp_avg_sq")] if kind == "lamb" else \
+        [(state1, "mom")]
+    for s, nm in states:
+        if s is None:
+            raise ValueError(f"the {kind} step needs {nm}")
+        _check(s, torch.float32, nm)
+    for s, nm in [(param, "param"), (grad, "grad")] + states:
+        if s.numel() < n:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {n}")
+    _check_shadow(lw, shadow)
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    b1, b2 = betas
+    args = (LAYERWISE_KINDS[kind], _ptr(param), _ptr(grad), _GDT[grad.dtype], _ptr(state1),
+            _ptr(state2) if kind == "lamb" else 0, _ptr(shadow), _ptr(lw.chunks),
+            lw.plan.num_chunks, _ptr(lw.tensors), _ptr(lw.adapt), _ptr(lw.partials),
+            _ptr(lw.ratio), float(lr), float(b1), float(b2), float(eps), float(weight_decay),
+            float(grad_scale), float(eta), float(momentum), float(dampening),
+            int(bool(nesterov)), int(bool(first)), 1.0 - b1 ** t, 1.0 - b2 ** t, _ptr(step),
+            _lrp(lr_tensor), _stream())
+    C.layerwise(0, *args)
+    C.layerwise(1, *args)
+
+
 _DDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 

@@ -456,6 +456,50 @@ PYBIND11_MODULE(_C, m) {
           ew_adam_flat(a);
         });
 
+  m.def("layerwise",
+        [](int op, int kind, uintptr_t param, uintptr_t grad, int grad_dtype, uintptr_t state1,
+           uintptr_t state2, uintptr_t shadow, uintptr_t chunks, int num_chunks,
+           uintptr_t tensors, uintptr_t adapt, uintptr_t partials, uintptr_t ratio, float lr,
+           double beta1, double beta2, float eps, float weight_decay, float grad_scale, float eta,
+           float momentum, float dampening, int nesterov, int first, float bc1, float bc2,
+           uintptr_t step, uintptr_t lr_ptr, uintptr_t stream) {
+          LayerwiseArgs a{};
+          a.kind = kind;
+          a.param = param;
+          a.grad = grad;
+          a.grad_dtype = grad_dtype;
+          a.state1 = state1;
+          a.state2 = state2;
+          a.shadow = shadow;
+          a.chunks = chunks;
+          a.num_chunks = num_chunks;
+          a.tensors = tensors;
+          a.adapt = adapt;
+          a.partials = partials;
+          a.ratio = ratio;
+          a.lr = lr;
+          a.beta1 = (float)beta1;
+          a.beta2 = (float)beta2;
+          a.beta1d = beta1;
+          a.beta2d = beta2;
+          a.eps = eps;
+          a.weight_decay = weight_decay;
+          a.grad_scale = grad_scale;
+          a.eta = eta;
+          a.momentum = momentum;
+          a.dampening = dampening;
+          a.nesterov = nesterov;
+          a.first = first;
+          a.bc1 = bc1;
+          a.bc2 = bc2;
+          a.step = step;
+          a.lr_ptr = lr_ptr;
+          a.stream = stream;
+          if (op == 0) ew_layerwise_stage(a);
+          else if (op == 1) ew_layerwise_apply(a);
+          else throw std::runtime_error("ewdml layerwise: unknown op");
+        });
+
   m.def("cast_scale", &ew_cast_scale);
 
   m.def("pack_grads",

@@ -9,6 +9,7 @@
 //     (compress/oracle.py) bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
 #include <stdint.h>
 
 #include <stdexcept>
@@ -67,6 +68,23 @@ __device__ __forceinline__ uint16_t ew_f2bf(float x) {  // round-to-nearest-even
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
+}
+
+// 4 consecutive elements of a flat gradient (GT: 0 = fp32, 1 = bf16, 2 = fp16) as fp32; i % 4 == 0
+template <int GT>
+__device__ __forceinline__ void ew_load_grad4(const void* g, long long i, float out[4]) {
+  if (GT == 0) {
+    const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g) + i);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+  } else if (GT == 1) {
+    const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(g) + i);
+    out[0] = ew_bf16f(v.x); out[1] = ew_bf16f(v.x >> 16);
+    out[2] = ew_bf16f(v.y); out[3] = ew_bf16f(v.y >> 16);
+  } else {
+    const __half* h = reinterpret_cast<const __half*>(g) + i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = __half2float(h[j]);
+  }
 }
 
 // Gradient source of a chunk: the per-tensor table (fp32 or bf16 per tensor), or -- when `flat`

@@ -192,6 +192,26 @@ struct AdamFlatArgs {
   uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
 };
 
+// LARS / LAMB over a flat range (layerwise.hip): chunks / tensors are the range's BucketPlan
+// tables; param, grad, state1, state2 and shadow its views.  adapt int32[T] (1: the tensor takes a
+// trust ratio), ratio fp32[T] (out), partials fp32[2 * num_chunks] (stage -> apply).
+struct LayerwiseArgs {
+  uintptr_t param, grad, state1, state2, shadow, chunks, tensors, adapt, partials, ratio, stream;
+  int num_chunks;
+  int kind;        // 0 = LARS (state1 = momentum buffer), 1 = LAMB (state1 / state2 = exp_avg / _sq)
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  float lr, beta1, beta2, eps, weight_decay, grad_scale, eta, momentum, dampening;
+  float bc1, bc2;  // LAMB: 1 - beta^t of this step (used when step is 0)
+  // the betas in double: 1 - beta and 1 - beta^t are formed in double and rounded once, as the
+  // oracle's python scalars are
+  double beta1d, beta2d;
+  int nesterov, first;
+  uintptr_t step;    // nullable int32 device step counter: t = *step + 1, first = (*step == 0)
+  uintptr_t lr_ptr;  // nullable device fp32 lr (overrides lr)
+};
+void ew_layerwise_stage(const LayerwiseArgs& a);
+void ew_layerwise_apply(const LayerwiseArgs& a);
+
 size_t ew_topk_scratch_bytes(int num_tensors, int num_chunks, long long bucket_len,
                              long long total_cap);
 std::vector<int> ew_topk_stats(uintptr_t scratch, int num_tensors, int num_chunks);

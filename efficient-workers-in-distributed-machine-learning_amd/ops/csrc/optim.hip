@@ -11,24 +11,7 @@
 
 namespace {
 
-__device__ __forceinline__ float ew_bf16_to_f32(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 __device__ __forceinline__ uint16_t ew_f32_to_bf16(float x) { return ew_f2bf(x); }
-
-template <int GT>
-__device__ __forceinline__ void ew_load_grad4(const void* g, long long i, float out[4]) {
-  if (GT == 0) {
-    const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g) + i);
-    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
-  } else if (GT == 1) {
-    const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(g) + i);
-    out[0] = ew_bf16_to_f32(v.x & 0xffff); out[1] = ew_bf16_to_f32(v.x >> 16);
-    out[2] = ew_bf16_to_f32(v.y & 0xffff); out[3] = ew_bf16_to_f32(v.y >> 16);
-  } else {
-    const __half* h = reinterpret_cast<const __half*>(g) + i;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) out[j] = __half2float(h[j]);
-  }
-}
 
 template <int GT>
 __global__ __launch_bounds__(EW_BLOCK) void k_sgd_flat(float* __restrict__ p, float* __restrict__ mom,

@@ -1,4 +1,4 @@
 """Optimizers with explicit gradients over the flat parameter buffer (reference ``optim/``)."""
-from .flat import FlatAdam, FlatSGD, make_optimizer
+from .flat import FlatAdam, FlatLAMB, FlatLARS, FlatSGD, make_optimizer
 
-__all__ = ["FlatSGD", "FlatAdam", "make_optimizer"]
+__all__ = ["FlatSGD", "FlatAdam", "FlatLARS", "FlatLAMB", "make_optimizer"]

@@ -236,8 +236,193 @@ class FlatOnebitAdam(FlatAdam):
         self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
 
 
+class _Layerwise(_LrMixin):
+    """Shared part of the layer-wise trust-ratio optimizers :class:`FlatLARS` / :class:`FlatLAMB`.
+
+    A tensor *adapts* (takes a trust ratio) when it has two or more dimensions; biases and
+    BatchNorm scales take ratio 1.  ``ratio`` (fp32, one entry per tensor in flat order) holds
+    the ratios of the last step.  A step covers one bucket or the whole model
+    (:meth:`step_range` with that range): on the GPU two launches (``ops.layerwise_step``), on the
+    CPU the torch oracle.  The 1-based step ``t`` is read from the device counter ``step_t``, so a
+    captured step replays the current step's values."""
+    fusable = False
+    kind = None
+
+    def __init__(self, flat, lr, weight_decay):
+        self.flat = flat
+        dev = flat.data.device
+        self._init_lr(lr, dev)
+        self.weight_decay = weight_decay
+        self.steps = 0
+        self.adapts = [p.dim() >= 2 for p in flat.params]
+        self.ratio = torch.ones(len(flat.params), dtype=torch.float32, device=dev)
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        # flat ranges a step may cover -> (first tensor, tensors): the whole model and each bucket
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        self._plans = {}
+        if dev.type == "cuda":
+            from ..compress.plan import CHUNK
+
+            self._adapt_t = torch.tensor(self.adapts, dtype=torch.int32, device=dev)
+            self._chunk0 = [0]
+            for p in flat.params:
+                self._chunk0.append(self._chunk0[-1] + (p.numel() + CHUNK - 1) // CHUNK)
+            self._partials = torch.zeros(2 * self._chunk0[-1], dtype=torch.float32, device=dev)
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            raise ValueError(f"a layer-wise step covers a bucket or the whole model (norms are "
+                             f"per tensor), not the range [{start}, {start + length})") from None
+
+    def _plan(self, start, length):
+        """The range's device plan (built once): its tables and its views of ``adapt`` /
+        ``ratio`` / the per-chunk partial sums."""
+        lw = self._plans.get((start, length))
+        if lw is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            c0, c1 = self._chunk0[t0], self._chunk0[t0 + nt]
+            lw = ops.LayerwisePlan(plan, self._adapt_t[t0:t0 + nt], self.ratio[t0:t0 + nt],
+                                   self._partials[2 * c0:2 * c1])
+            self._plans[(start, length)] = lw
+        return lw
+
+    def _tensors(self, start, length):
+        t0, nt = self._range(start, length)
+        return t0, [(self.flat.offsets[t] - start, self.flat.params[t].numel(), self.adapts[t])
+                    for t in range(t0, t0 + nt)]
+
+    def trust_ratio_range(self):
+        """(min, max) of the last step's ratios over the adapting tensors (synchronises); None
+        when no tensor adapts."""
+        r = self.ratio[torch.tensor(self.adapts, dtype=torch.bool, device=self.ratio.device)]
+        return (float(r.min()), float(r.max())) if r.numel() else None
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    def _load_common(self, sd):
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        if "ratio" in sd and sd["ratio"] is not None:
+            self.ratio.copy_(sd["ratio"])
+        self.lr = sd.get("lr", self.lr)
+        self.weight_decay = sd.get("weight_decay", self.weight_decay)
+
+
+class FlatLARS(_Layerwise):
+    """LARS (You et al., 2017): per adapting tensor ``r = eta |p| / (|g| + wd |p|)`` (1 when a
+    norm is zero), then :class:`FlatSGD`'s rule on ``r (g + wd p)`` with its own weight decay off
+    (momentum buffer = the first such gradient, dampening, Nesterov)."""
+    kind = "lars"
+
+    def __init__(self, flat, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0,
+                 nesterov=False, eta=0.001):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(flat, lr, weight_decay)
+        self.momentum, self.dampening, self.nesterov, self.eta = momentum, dampening, nesterov, eta
+        self.mom = torch.zeros_like(flat.data)
+
+    @property
+    def first(self) -> bool:
+        return self.steps == 0
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        sl = slice(start, start + length)
+        p, m = self.flat.data[sl], self.mom[sl]
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.layerwise_step(self._plan(start, length), "lars", p, grad, m, lr=self.lr,
+                               weight_decay=self.weight_decay, grad_scale=grad_scale,
+                               eta=self.eta, momentum=self.momentum, dampening=self.dampening,
+                               nesterov=self.nesterov, first=self.first, step=self.step_t,
+                               lr_tensor=self.lr_t, shadow=sh)
+            return
+        t0, tensors = self._tensors(start, length)
+        g = grad.to(torch.float32) * grad_scale
+        self.ratio[t0:t0 + len(tensors)] = oracle.lars_apply(
+            p, m, g, tensors, self.lr, self.momentum, self.dampening, self.weight_decay,
+            self.nesterov, self.first, self.eta)
+
+    def state_dict(self):
+        return {"kind": "lars", "mom": self.mom, "steps": self.steps, "ratio": self.ratio,
+                "lr": self.lr, "momentum": self.momentum, "dampening": self.dampening,
+                "weight_decay": self.weight_decay, "nesterov": self.nesterov, "eta": self.eta}
+
+    def load_state_dict(self, sd):
+        self.mom.copy_(sd["mom"])
+        self._load_common(sd)
+        for k in ("momentum", "dampening", "nesterov", "eta"):
+            if k in sd:
+                setattr(self, k, sd[k])
+
+
+class FlatLAMB(_Layerwise):
+    """LAMB (You et al., ICLR 2020): Adam's moments with bias correction, ``u = m^ / (sqrt(v^) +
+    eps) + wd p``, per adapting tensor ``r = |p| / |u|`` (1 when a norm is zero), ``p -= lr r u``.
+    No clamp on ``|p|`` and no gradient clipping."""
+    kind = "lamb"
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(flat, lr, weight_decay)
+        self.betas, self.eps = betas, eps
+        self.exp_avg = torch.zeros_like(flat.data)
+        self.exp_avg_sq = torch.zeros_like(flat.data)
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        sl = slice(start, start + length)
+        p, m, v = self.flat.data[sl], self.exp_avg[sl], self.exp_avg_sq[sl]
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.layerwise_step(self._plan(start, length), "lamb", p, grad, m, v, lr=self.lr,
+                               weight_decay=self.weight_decay, grad_scale=grad_scale,
+                               betas=self.betas, eps=self.eps, t=self.steps + 1,
+                               step=self.step_t, lr_tensor=self.lr_t, shadow=sh)
+            return
+        t0, tensors = self._tensors(start, length)
+        g = grad.to(torch.float32) * grad_scale
+        b1, b2 = self.betas
+        self.ratio[t0:t0 + len(tensors)] = oracle.lamb_apply(
+            p, m, v, g, tensors, self.lr, b1, b2, self.eps, self.weight_decay, self.steps + 1)
+
+    def state_dict(self):
+        return {"kind": "lamb", "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+                "steps": self.steps, "ratio": self.ratio, "lr": self.lr,
+                "weight_decay": self.weight_decay}
+
+    def load_state_dict(self, sd):
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self._load_common(sd)
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "lars":
+        return FlatLARS(flat, eta=kw.get("eta", 0.001),
+                        **{k: v for k, v in kw.items()
+                           if k in ("lr", "momentum", "dampening", "weight_decay", "nesterov")})
+    if name == "lamb":
+        return FlatLAMB(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
+                        eps=kw.get("eps", 1e-8))
     if name == "sgd":
         return FlatSGD(flat, **{k: v for k, v in kw.items()
                                 if k in ("lr", "momentum", "dampening", "weight_decay",

@@ -9,6 +9,7 @@ data is sharded with equal step counts on every rank, the loop ends on ``--max-s
 ``--epochs`` identically everywhere (no deadlock), only rank 0 checkpoints.
 """
 import contextlib
+import gc
 import math
 import os
 import time
@@ -54,6 +55,29 @@ def resolve_device(cfg: Config) -> torch.device:
 
 class FaultInjected(RuntimeError):
     pass
+
+
+@contextlib.contextmanager
+def _no_gc():
+    """Collect garbage now and keep the cyclic collector off inside the block (a graph capture).
+
+    Seen once: with some 60 GPU tests behind it in one process, the capture of a ResNet-50 step
+    ended the process with SIGABRT on the main thread while Python was garbage-collecting (the
+    collector runs wherever an allocation crosses its threshold, so any change to what a process
+    imports moves it).  ``torch.cuda.graph`` (torch 2.10) no longer collects before it begins a
+    capture, so finalizers of objects that died long before can run in the middle of one, where
+    device synchronisation and frees are not allowed.  Which finalizer it was is not known (a
+    ``torch.cuda.CUDAGraph``, whose ROCm destructor synchronises, is the candidate; a closed LeNet
+    trainer frees its graph by reference count, without the collector).  Inside this block no
+    finalizer of older garbage can run whichever it was (profiles/validation/layerwise.md)."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class Trainer:
@@ -187,7 +211,7 @@ class Trainer:
         self.opt = make_optimizer(cfg.optimizer, self.flat, lr=lr, momentum=cfg.momentum,
                                   dampening=cfg.dampening, weight_decay=cfg.weight_decay,
                                   nesterov=cfg.nesterov, eps=cfg.adam_eps,
-                                  freeze_step=cfg.onebit_warmup_steps)
+                                  freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta)
 
         # exchange ---------------------------------------------------------------------------------
         ckw = dict(ratio=cfg.topk_ratio, levels=cfg.qsgd_levels, bits=cfg.qsgd_bits,
@@ -532,7 +556,8 @@ class Trainer:
             if self._ugraph is None or self._ugraph[0] != unroll:
                 err = None
                 try:
-                    self._capture_unrolled(unroll)
+                    with _no_gc():
+                        self._capture_unrolled(unroll)
                 except Exception as e:  # noqa: BLE001 - the one-step graph keeps running
                     err = e
                 # every rank or none (the graph holds the step's collectives)
@@ -720,7 +745,8 @@ class Trainer:
         peer would not match."""
         err = None
         try:
-            self._capture(x, y)
+            with _no_gc():
+                self._capture(x, y)
         except Exception as e:  # noqa: BLE001 - any capture failure falls back to eager
             err = e
         if self.ps_graph:
@@ -1131,6 +1157,12 @@ class Trainer:
                 ge = getattr(self.exchange, "inner", self.exchange)
                 if hasattr(ge, "codec_health"):
                     rec.update(ge.codec_health())
+                # lars / lamb: the last step's trust ratios over the adapting tensors (read only
+                # here, like the codec's health)
+                if hasattr(self.opt, "trust_ratio_range"):
+                    tr = self.opt.trust_ratio_range()
+                    if tr is not None:
+                        rec["trust_ratio_min"], rec["trust_ratio_max"] = tr
                 rec["bytes_sent_total"] = acc["bytes_sent"]
                 rec["bytes_recv_total"] = acc["bytes_recv"]
                 rec["payload_bytes_total"] = acc["payload_bytes"]
