@@ -544,6 +544,38 @@ def lamb_apply(p, m, v, g, tensors, lr, beta1, beta2, eps, weight_decay, step):
 
 
 # ---------------------------------------------------------------------------------------------
+# Global-norm gradient clipping of one rank's local gradient (DGC's local gradient clipping;
+# ``torch.nn.utils.clip_grad_norm_`` at a world of one).  The CPU path and the definition of the
+# arithmetic of ``ops/csrc/clip.hip``, up to the order of the fp32 sums (free here, a fixed tree
+# with an fp64 total there).
+# ---------------------------------------------------------------------------------------------
+CLIP_EPS = 1e-6  # torch's clip_grad_norm_ epsilon
+
+
+def clip_grad_norm_(grads, max_norm: float):
+    """``norm`` = the L2 norm over every element of ``grads`` (fp32 or bf16 tensors; bf16 enters
+    as its exact fp32 value), ``coef = min(1, max_norm / (norm + 1e-6))``, and every tensor set to
+    ``g * coef`` in place by one fp32 multiply (bf16: the fp32 product rounded to nearest even).
+    A NaN norm leaves ``coef`` at 1 as C's ``fminf`` does; the NaN elements themselves stay.
+    Returns ``(norm, coef)`` as 0-dim fp32 tensors."""
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("max_norm must be > 0")
+    grads = list(grads)
+    norms = torch.stack([torch.linalg.vector_norm(g.detach().float()) for g in grads])
+    norm = torch.linalg.vector_norm(norms)
+    q = torch.tensor(max_norm, dtype=torch.float32, device=norm.device) / (norm + CLIP_EPS)
+    coef = torch.where(q < 1.0, q, torch.ones_like(q))
+    for g in grads:
+        g = g.detach()
+        if g.dtype == torch.float32:
+            g.mul_(coef)
+        else:
+            g.copy_((g.float() * coef).to(g.dtype))
+    return norm, coef
+
+
+# ---------------------------------------------------------------------------------------------
 # PowerSGD (Vogels et al., NeurIPS 2019; torch's ``powerSGD_hook``): rank-r factors of the
 # error-compensated gradient matrices of one bucket (``plan.LowRankPlan``).  The CPU path and the
 # definition of the arithmetic of ``ops/csrc/powersgd.hip``.  Every function works in ``dtype``

@@ -107,6 +107,10 @@ class Config:
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
     lars_eta: Optional[float] = None  # lars: trust coefficient (None: 0.001)
+    # clip this rank's raw gradient by its global L2 norm before the exchange reads it (DGC's
+    # local gradient clipping, parallel/clip.py): coef = min(1, C / (norm + 1e-6)); None: off
+    clip_grad_norm: Optional[float] = None
+    clip_scale_world: bool = False  # the threshold becomes C / sqrt(N), N workers (DGC's rule)
     weight_decay: float = 0.0
     dampening: float = 0.0
     nesterov: bool = False
@@ -278,6 +282,28 @@ class Config:
                 raise ValueError("--lars-eta must be > 0")
         elif c.lars_eta is not None:
             raise ValueError("--lars-eta belongs to --optimizer lars")
+        if c.clip_grad_norm is not None:
+            # the clip scales every gradient of the rank once, after backward and before any
+            # encode (parallel/clip.py); the exchanges below do not take a clipper
+            why = None
+            if not float(c.clip_grad_norm) > 0:
+                why = f"must be > 0, not {c.clip_grad_norm!r}"
+            elif c.topology in ("ps", "sharded"):
+                why = (f"clips ahead of the all-to-all, two-stage and PowerSGD exchanges: "
+                       f"--topology {c.topology} is out of scope")
+            elif c.sync_every > 1:
+                why = ("clips the gradient of an exchanged step: local steps "
+                       "(--sync-every > 1) are out of scope")
+            elif c.select_best:
+                why = "clips the gradient of an exchanged step: --select-best is out of scope"
+            elif c.hip_graph == "segmented":
+                why = ("needs every gradient before any encode, so there is nothing to overlap: "
+                       "it does not run with --hip-graph segmented")
+            if why is not None:
+                raise ValueError("--clip-grad-norm " + why)
+        elif c.clip_scale_world:
+            raise ValueError("--clip-scale-world divides the --clip-grad-norm threshold by "
+                             "sqrt(N): it needs --clip-grad-norm")
         if c.ef_mode == "ef21" and c.error_feedback and c.device != "cpu" and not c.no_cuda:
             import os
 
@@ -370,6 +396,8 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)
     a("--lars-eta", type=float, default=None)
+    a("--clip-grad-norm", type=float, default=None)
+    a("--clip-scale-world", action="store_true", default=False)
     a("--weight-decay", type=float, default=d.weight_decay)
     a("--dampening", type=float, default=d.dampening)
     a("--nesterov", action="store_true", default=False)

@@ -823,6 +823,84 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
     C.layerwise(1, *args)
 
 
+# Longest chain of fp32 additions behind one chunk's sum of squares in k_clip_norm
+# (csrc/clip.hip), k_lw_stage's tree: 32 serial terms per thread + 6 shuffle levels + 3 across
+# the waves.  The model-wide sum over the chunks is fp64.
+CLIP_SUM_CHAIN = 41
+
+
+class _ClipBucket:
+    """One bucket's plan, device chunk table and first row in the model-wide partials."""
+
+    def __init__(self, plan, device, chunk0):
+        self.plan, self.chunk0 = plan, chunk0
+        self.chunks = plan.chunk_table(device)
+
+
+class ClipPlan:
+    """Device state of the global-norm gradient clip over a whole model: per bucket (``plans``,
+    the model's ``BucketPlan`` s in bucket order) the chunk table, and model-wide the per-chunk
+    ``partials`` (fp32, one per chunk row in bucket order, then chunk order) and
+    ``state`` = fp32 ``{norm, coef}``, rewritten by every step."""
+
+    def __init__(self, plans, device):
+        require()
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("ClipPlan holds device tables: it needs a GPU device")
+        if not plans:
+            raise ValueError("ClipPlan needs at least one bucket")
+        self.buckets, n = [], 0
+        for plan in plans:
+            if plan.num_tensors > MAX_TENSORS_PER_BUCKET:
+                raise ValueError(f"bucket has {plan.num_tensors} tensors (max "
+                                 f"{MAX_TENSORS_PER_BUCKET})")
+            if any(o % 4 for o in plan.offsets):
+                raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+            if max(o + k for o, k in zip(plan.offsets, plan.numels)) > plan.length:
+                raise ValueError("a tensor reaches past its bucket")
+            if plan.length >= 1 << 31:
+                raise ValueError("bucket of 2^31 elements or more")
+            self.buckets.append(_ClipBucket(plan, device, n))
+            n += plan.num_chunks
+        self.total_chunks = n
+        self.partials = torch.zeros(n, dtype=torch.float32, device=device)
+        self.state = torch.zeros(2, dtype=torch.float32, device=device)
+
+
+def _clip_args(cp, bi, grads, max_norm):
+    if not isinstance(cp, ClipPlan):
+        raise TypeError("expected an ops.ClipPlan")
+    if not 0 <= bi < len(cp.buckets):
+        raise ValueError(f"bucket {bi} of a clip plan of {len(cp.buckets)}")
+    b = cp.buckets[bi]
+    ptrs, mask = grad_pointers(b, grads)
+    dev = cp.partials.device
+    for t in ([grads] if torch.is_tensor(grads) else grads):
+        if t.device != dev:
+            raise ValueError("gradients and clip plan live on different devices")
+    return (ptrs, mask, b.plan.num_tensors, _ptr(b.chunks), b.plan.num_chunks, _ptr(cp.partials),
+            b.chunk0, cp.total_chunks, _ptr(cp.state), float(max_norm), _stream())
+
+
+def clip_norm(cp: ClipPlan, bi: int, grads):
+    """Launch ``k_clip_norm`` for bucket ``bi``: the per-chunk sums of squares of its gradients
+    (``grads`` as for :func:`pack_grads`: the bucket's flat fp32 view, or one fp32 / bf16 tensor per
+    plan tensor) into ``cp.partials``.  Every bucket's norm launch precedes any
+    :func:`clip_scale`."""
+    require().clip(0, *_clip_args(cp, bi, grads, 1.0))
+
+
+def clip_scale(cp: ClipPlan, bi: int, grads, max_norm: float):
+    """Launch ``k_clip_scale`` for bucket ``bi``: ``coef = min(1, max_norm / (norm + 1e-6))`` from
+    all of ``cp.partials``, the bucket's gradients scaled in place unless ``coef == 1``; bucket 0
+    stores ``cp.state = {norm, coef}``."""
+    max_norm = float(max_norm)
+    if not max_norm > 0.0 or max_norm != max_norm:
+        raise ValueError("max_norm must be > 0")
+    require().clip(1, *_clip_args(cp, bi, grads, max_norm))
+
+
 _DDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 

@@ -500,6 +500,29 @@ PYBIND11_MODULE(_C, m) {
           else throw std::runtime_error("ewdml layerwise: unknown op");
         });
 
+  m.def("clip",
+        [](int op, const Ptrs& grads, const Mask& mask, int T, uintptr_t chunks, int C,
+           uintptr_t partials, int chunk0, int total_chunks, uintptr_t state, float max_norm,
+           uintptr_t stream) {
+          ClipArgs a{};
+          a.grad_ptrs = grads.data();
+          a.n_grad_ptrs = (int)grads.size();
+          a.bf16_mask = mask.data();
+          a.n_bf16_mask = (int)mask.size();
+          a.num_tensors = T;
+          a.chunks = chunks;
+          a.num_chunks = C;
+          a.partials = partials;
+          a.chunk0 = chunk0;
+          a.total_chunks = total_chunks;
+          a.state = state;
+          a.max_norm = max_norm;
+          a.stream = stream;
+          if (op == 0) ew_clip_norm(a);
+          else if (op == 1) ew_clip_scale(a);
+          else throw std::runtime_error("ewdml clip: unknown op");
+        });
+
   m.def("cast_scale", &ew_cast_scale);
 
   m.def("pack_grads",

@@ -212,6 +212,22 @@ struct LayerwiseArgs {
 void ew_layerwise_stage(const LayerwiseArgs& a);
 void ew_layerwise_apply(const LayerwiseArgs& a);
 
+// Global-norm gradient clipping (clip.hip), one bucket per call: the bucket's gradients through
+// the pointer table of pack_grads, its chunk table, and the model-wide partials fp32[total_chunks]
+// in which this bucket's rows start at chunk0.  ew_clip_norm of every bucket comes before any
+// ew_clip_scale; the scale of the bucket with chunk0 == 0 stores state fp32[2] = {norm, coef}.
+struct ClipArgs {
+  const uintptr_t* grad_ptrs;
+  int n_grad_ptrs;
+  const uint32_t* bf16_mask;
+  int n_bf16_mask;
+  int num_tensors, num_chunks, chunk0, total_chunks;
+  uintptr_t chunks, partials, state, stream;
+  float max_norm;
+};
+void ew_clip_norm(const ClipArgs& a);
+void ew_clip_scale(const ClipArgs& a);
+
 size_t ew_topk_scratch_bytes(int num_tensors, int num_chunks, long long bucket_len,
                              long long total_cap);
 std::vector<int> ew_topk_stats(uintptr_t scratch, int num_tensors, int num_chunks);

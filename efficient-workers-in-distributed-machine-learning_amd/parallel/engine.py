@@ -40,13 +40,28 @@ class StepStats:
         self.collectives = 0
 
 
+def clip_final_grads(clipper, device):
+    """``--clip-grad-norm`` for the exchanges that encode everything after backward (two-stage
+    sign, PowerSGD): complete any deferred weight gradient, then clip once (no clipper: nothing)."""
+    if clipper is None:
+        return
+    if device.type == "cuda":
+        from ..ops.conv import flush_pending
+
+        flush_pending()
+    clipper.run()
+
+
 class GradientExchange:
     """All-to-all exchange: all-reduce for dense codecs, all-gather of payloads otherwise."""
 
     def __init__(self, flat, comm, codec, optimizer, overlap: bool = True,
                  error_feedback: bool = False, predivide: float = 1.0, seed_offset: int = 0,
-                 side_stream: bool = True, ef_mode: str = "dgc"):
+                 side_stream: bool = True, ef_mode: str = "dgc", clipper=None):
         self.flat, self.comm, self.codec, self.opt = flat, comm, codec, optimizer
+        # --clip-grad-norm (parallel/clip.py GradClipper): the norm needs every gradient, so the
+        # hooks launch nothing and launch_pending() clips once, then encodes every bucket
+        self.clipper = clipper
         self.device = flat.data.device
         self.cuda = self.device.type == "cuda"
         self.codec.bind([b.plan for b in flat.buckets], self.device)
@@ -241,7 +256,7 @@ class GradientExchange:
         self._active = True
 
     def _on_grad(self, p):
-        if not self._active:
+        if not self._active or self.clipper is not None:
             return
         b = self._bucket_of[id(p)]
         self._count[b] += 1
@@ -275,6 +290,14 @@ class GradientExchange:
 
             flush_pending()
             assert not pending(), "deferred weight-gradient transform still pending at encode"
+        if self.clipper is not None:  # every gradient is final; nothing has read one yet
+            if self.seg is not None or len(bis) != self.nb:
+                raise RuntimeError("gradient clipping needs every bucket encoded after backward")
+            if self.clock is not None and self.side is None:
+                self.clock.mark("backward")
+            self.clipper.run()
+            if self.clock is not None and self.side is None:
+                self.clock.mark("clip")
         if self.seg is not None:
             # segmented capture: buckets wait for the next split point (a byte threshold of the
             # step's gradient); their encode + collective then become one comm-stream graph
@@ -731,10 +754,12 @@ OVERLAP_MAX_SPLITS = 3
 
 def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int,
                     bits: int = 8, overlap: bool = True, bucket_bytes: int = 16 << 20,
-                    model: str = None, topk_ratio: float = 0.01, dtype: str = "fp32") -> dict:
+                    model: str = None, topk_ratio: float = 0.01, dtype: str = "fp32",
+                    clip: bool = False) -> dict:
     """``--hip-graph auto`` for the all-to-all exchange (``GradientExchange``).
 
-    * N = 1, or collectives on the process group (not capturable), or ``--no-overlap``: the
+    * N = 1, or collectives on the process group (not capturable), or ``--no-overlap``, or
+      ``--clip-grad-norm`` (``clip``: the norm needs every gradient before any encode): the
       one-graph step (``full``; the trainer demotes it to ``split`` for process-group
       collectives).  At N = 1 there is nothing to hide: the segmented step only adds graph
       boundaries (+11 % on dense VGG-11, profiles/ab/segmented_overlap.txt).
@@ -784,6 +809,8 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
         return dict(out, reason="process-group collectives are not captured")
     if not overlap:
         return dict(out, reason="--no-overlap")
+    if clip:
+        return dict(out, reason="--clip-grad-norm: every encode waits for the whole gradient")
     want = (4 * grad_numel) // (2 * (splits + 1))
     seg = {"mode": "segmented", "splits": splits,
            "bucket_bytes": int(min(bucket_bytes, max(1 << 20, want)))}

@@ -33,7 +33,7 @@ import torch
 
 from ..compress import oracle
 from ..compress.plan import LowRankPlan
-from .engine import StepStats
+from .engine import StepStats, clip_final_grads
 
 
 def _align(n, a=64):
@@ -41,7 +41,7 @@ def _align(n, a=64):
 
 
 class PowerSGDExchange:
-    def __init__(self, flat, comm, codec, optimizer):
+    def __init__(self, flat, comm, codec, optimizer, clipper=None):
         if codec.kind != "powersgd":
             raise ValueError("the PowerSGD exchange needs --compress powersgd")
         if not flat.attach_grads:
@@ -53,6 +53,7 @@ class PowerSGDExchange:
         self.N, self.rank = comm.world, comm.rank
         self.inv_n = 1.0 / self.N
         self.nb = len(flat.buckets)
+        self.clipper = clipper  # --clip-grad-norm: runs once per step, ahead of the projects
         self.step_idx = 0
         self.lr_plans = [LowRankPlan(b.plan, [tuple(p.shape) for p in b.params], codec.rank)
                          for b in flat.buckets]
@@ -100,6 +101,7 @@ class PowerSGDExchange:
         if self._projected:
             return
         self._mark("backward")
+        clip_final_grads(self.clipper, self.device)
         for b in self.flat.buckets:
             bi = b.index
             self.codec.ps_project(bi, self.flat.grad_view(b),

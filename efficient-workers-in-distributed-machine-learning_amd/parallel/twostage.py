@@ -30,7 +30,7 @@ same length and a checkpoint can all-gather the rows).
 import torch
 
 from ..compress.plan import TwoStagePlan
-from .engine import StepStats
+from .engine import StepStats, clip_final_grads
 from .sharded import shard_plans
 
 
@@ -44,7 +44,7 @@ class TwoStageSignExchange:
     backward and the push encodes; eager all-to-all, owner kernel and all-gather; graph B = the
     pull decode + optimizer step."""
 
-    def __init__(self, flat, comm, codec, optimizer):
+    def __init__(self, flat, comm, codec, optimizer, clipper=None):
         if codec.kind != "sign":
             raise ValueError("--topology twostage is the sign codec's exchange: it needs "
                              "--compress sign")
@@ -55,6 +55,7 @@ class TwoStageSignExchange:
         self.N, self.rank = comm.world, comm.rank
         self.nb = len(flat.buckets)
         self.onebit = bool(getattr(optimizer, "onebit", False))
+        self.clipper = clipper  # --clip-grad-norm: runs once per step, ahead of the push encodes
         self.step_idx = 0
         self.ts = [TwoStagePlan(b.plan, shard_plans(b.plan, self.N, b.start))
                    for b in flat.buckets]
@@ -100,6 +101,7 @@ class TwoStageSignExchange:
         if self._encoded:
             return
         self._mark("backward")
+        clip_final_grads(self.clipper, self.device)
         o = self.opt
         for b in self.flat.buckets:
             sl = slice(b.start, b.start + b.length)

@@ -26,6 +26,7 @@ from ..optim.flat import make_optimizer
 from ..parallel.comm import Comm, init_distributed
 from ..parallel.engine import (GradientExchange, SegmentedCapture, StepStats, Stopwatch,
                                plan_graph_mode, sync_buffers, sync_params)
+from ..parallel.clip import GradClipper
 from ..parallel.flat import FlatModel
 from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
@@ -199,7 +200,8 @@ class Trainer:
                 bits=cfg.qsgd_bits, overlap=cfg.overlap, bucket_bytes=bucket_bytes,
                 model=cfg.network, topk_ratio=cfg.topk_ratio,
                 dtype="fp32" if self.amp_kept_fp32 else
-                {"bf16": "bf16", "fp16": "fp16"}.get(cfg.amp, "fp32"))
+                {"bf16": "bf16", "fp16": "fp16"}.get(cfg.amp, "fp32"),
+                clip=cfg.clip_grad_norm is not None)
             bucket_bytes = self.graph_plan["bucket_bytes"]
         self.flat = FlatModel(model, bucket_bytes=bucket_bytes,
                               attach_grads=not ptr_grads, bf16_params=bf16_params)
@@ -212,6 +214,17 @@ class Trainer:
                                   dampening=cfg.dampening, weight_decay=cfg.weight_decay,
                                   nesterov=cfg.nesterov, eps=cfg.adam_eps,
                                   freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta)
+
+        # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
+        # Adam share it); it runs once per step, after backward and before the first encode
+        self.clipper = None
+        if cfg.clip_grad_norm is not None:
+            if os.environ.get("EWDML_PRODUCER_STAGE") == "1":
+                raise ValueError("--clip-grad-norm scales the stored gradient before the encode "
+                                 "reads it: EWDML_PRODUCER_STAGE=1 stages a weight gradient in the "
+                                 "kernel that forms it and never stores it")
+            self.clipper = GradClipper(self.flat, cfg.clip_grad_norm, world=n_workers,
+                                       scale_world=cfg.clip_scale_world)
 
         # exchange ---------------------------------------------------------------------------------
         ckw = dict(ratio=cfg.topk_ratio, levels=cfg.qsgd_levels, bits=cfg.qsgd_bits,
@@ -231,10 +244,12 @@ class Trainer:
         elif cfg.compress == "powersgd":
             self.exchange = PowerSGDExchange(self.flat, self.comm,
                                              make_codec("powersgd", seed=cfg.seed,
-                                                        rank=cfg.powersgd_rank), self.opt)
+                                                        rank=cfg.powersgd_rank), self.opt,
+                                             clipper=self.clipper)
         elif cfg.topology == "twostage" and cfg.optimizer != "onebit_adam":
             self.exchange = TwoStageSignExchange(self.flat, self.comm,
-                                                 make_codec(cfg.compress, **ckw), self.opt)
+                                                 make_codec(cfg.compress, **ckw), self.opt,
+                                                 clipper=self.clipper)
         elif cfg.optimizer == "onebit_adam":
             # 1-bit Adam: two exchanges over the same flat model and optimizer -- the dense fp32
             # all-reduce of the warm-up (steps 1..T_w: FlatAdam's step) and the sign exchange of
@@ -246,14 +261,15 @@ class Trainer:
             self._stages = tuple(
                 GradientExchange(self.flat, self.comm, make_codec(kind, **ckw), self.opt,
                                  overlap=cfg.overlap, error_feedback=ef, predivide=1.0,
-                                 side_stream=side, ef_mode="plain")
+                                 side_stream=side, ef_mode="plain", clipper=self.clipper)
                 for kind, ef in (("none", False), ("sign", True))[:1 if cfg.topology == "twostage"
                                                                   else 2])
             if cfg.topology == "twostage":
                 # the warm-up is unchanged; the compressed stage runs the two-stage exchange
                 # (momentum push, owner average + re-encode, 1-bit pull with inv_n = 1)
                 self._stages += (TwoStageSignExchange(self.flat, self.comm,
-                                                      make_codec("sign", **ckw), self.opt),)
+                                                      make_codec("sign", **ckw), self.opt,
+                                                      clipper=self.clipper),)
             self.exchange = self._stages[1 if self.opt.frozen else 0]
         else:
             # captured steps keep the encode + collectives on the step's own stream: a side-stream
@@ -271,7 +287,7 @@ class Trainer:
                                              # no sender-side momentum there
                                              ef_mode=cfg.ef_mode if (cfg.sync_every == 1 and
                                                                      not cfg.select_best)
-                                             else "plain")
+                                             else "plain", clipper=self.clipper)
             if cfg.sync_every > 1 or cfg.select_best:
                 self.exchange = LocalSGDExchange(self.exchange, cfg.sync_every, cfg.sync_mode,
                                                  cfg.select_best, score_fn=self._holdout_score)
@@ -1163,6 +1179,11 @@ class Trainer:
                     tr = self.opt.trust_ratio_range()
                     if tr is not None:
                         rec["trust_ratio_min"], rec["trust_ratio_max"] = tr
+                # --clip-grad-norm: this rank's gradient norm and coefficient of the last step
+                if self.clipper is not None:
+                    clipped = self.clipper.last()
+                    if clipped is not None:
+                        rec["grad_norm"], rec["clip_coef"] = clipped
                 rec["bytes_sent_total"] = acc["bytes_sent"]
                 rec["bytes_recv_total"] = acc["bytes_recv"]
                 rec["payload_bytes_total"] = acc["payload_bytes"]
