@@ -9,6 +9,9 @@
   * ``topk_qsgd`` -- top-k then QSGD (Method 5); the flagship codec
   * ``sign``  -- scaled sign, 1 bit per element plus one fp32 scale per 8192-element chunk
     (1-bit SGD / EF-signSGD); meant to run with error feedback, which the all-gather exchange keeps
+  * ``vote``  -- Distributed Lion's 1-bit majority vote (Liu et al. 2024): one bit per element, the
+    sign of the rank's own Lion update direction; no scale, no residual (``encode_vote`` /
+    ``decode_apply_vote``; needs ``optim/flat.py FlatLion``)
   * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
     al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
     methods below)
@@ -29,20 +32,26 @@ from . import oracle
 from .plan import POWERSGD_RANKS, BucketPlan, Layout
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd")
+KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote")
+VOTE_AGGREGATES = ("majority", "average")
 
 
 class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
-                 rank: int = 4):
+                 rank: int = 4, aggregate: str = "majority"):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
             raise ValueError(f"PowerSGD rank must be one of {POWERSGD_RANKS}, not {rank!r}")
         self.rank = int(rank)
-        # the sign and low-rank codecs have neither bits nor levels
-        if kind not in ("sign", "powersgd") and bits not in (4, 8):
+        if aggregate not in VOTE_AGGREGATES:
+            raise ValueError(f"vote aggregate must be one of {VOTE_AGGREGATES}, not {aggregate!r}")
+        if aggregate != "majority" and kind != "vote":
+            raise ValueError("the aggregate belongs to the vote codec")
+        self.aggregate = aggregate
+        # the sign, vote and low-rank codecs have neither bits nor levels
+        if kind not in ("sign", "powersgd", "vote") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -79,6 +88,8 @@ class Codec:
             return "sign1b"
         if self.kind == "powersgd":
             return f"powersgd-r{self.rank}"
+        if self.kind == "vote":
+            return "vote1b"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -151,6 +162,9 @@ class Codec:
             raise ValueError("momentum correction needs a top-k codec and a residual")
         if self.kind == "sign" and apply is not None:
             raise ValueError("the sign codec has no encode-side apply")
+        if self.kind == "vote":
+            raise ValueError("the vote codec sends the sign of Lion's update direction: "
+                             "encode_vote, with the rank's momentum")
         plan, lay = self.plans[b], self.layouts[b]
         key = self.key(step, rank)
         on_dev = (grad[0] if isinstance(grad, (list, tuple)) else grad).is_cuda
@@ -202,6 +216,43 @@ class Codec:
         out = oracle.encode_sign_momentum(grad, plan, lay, resid, exp_avg, beta1, weight_decay,
                                           param)
         payload[:lay.nbytes].copy_(out)
+
+    # -- Distributed Lion's vote (optim/flat.py FlatLion): one launch per bucket and side ---------
+    def encode_vote(self, b: int, grad, payload: torch.Tensor, exp_avg: torch.Tensor,
+                    betas, step: int, rank: int, step_tensor: torch.Tensor = None):
+        """This rank's vote of bucket ``b``: one bit per element, the sign of ``exp_avg * beta1 +
+        (1 - beta1) * grad``; ``exp_avg`` (the rank's own momentum, that bucket's view) then moves
+        with ``beta2``.  ``step``: the 1-based step of the exact-zero dither (on the GPU
+        ``step_tensor``, the optimizer's device counter, is read instead)."""
+        if self.kind != "vote":
+            raise ValueError("the vote encode needs the vote codec")
+        plan, lay = self.plans[b], self.layouts[b]
+        b1, b2 = betas
+        on_dev = (grad[0] if isinstance(grad, (list, tuple)) else grad).is_cuda
+        if on_dev and not _FORCE_ORACLE:
+            ops.lion_encode(self.dplans[b], grad, payload, lay, exp_avg, b1, b2, step, rank,
+                            step_tensor=step_tensor)
+            return
+        if isinstance(grad, (list, tuple)):
+            raise TypeError("CPU encode takes the bucket's flat gradient view")
+        payload[:lay.nbytes].copy_(oracle.encode_vote(grad, plan, lay, exp_avg, b1, b2, step,
+                                                      rank))
+
+    def decode_apply_vote(self, b: int, recv: torch.Tensor, param: torch.Tensor, hp: dict,
+                          shadow=None, key_state=None, rank: int = 0):
+        """Count the N received votes of bucket ``b`` and step its parameters by the majority (or
+        the average, ``aggregate``) of the signs.  ``hp``: ``FlatLion.hparams()``."""
+        if self.kind != "vote":
+            raise ValueError("the vote apply needs the vote codec")
+        plan, lay = self.plans[b], self.layouts[b]
+        inv_n = 1.0 / recv.shape[0]
+        if recv.is_cuda and not _FORCE_ORACLE:
+            ops.lion_vote_apply(self.dplans[b], recv, lay, param, hp["lr"], hp["weight_decay"],
+                                self.aggregate, inv_n, shadow=shadow, lr_tensor=hp.get("lr_t"),
+                                key_state=key_state, key_seed=self.seed, key_rank=rank)
+            return
+        oracle.vote_apply(recv, plan, lay, param, hp["lr"], hp["weight_decay"], self.aggregate,
+                          inv_n)
 
     # -- two-stage sign all-reduce (parallel/twostage.py): three launches per bucket ------------
     def bind_twostage(self, ts_plans, device):
@@ -414,6 +465,9 @@ class Codec:
 
     def decode(self, b: int, recv: torch.Tensor, out: torch.Tensor, scale: float):
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""
+        if self.kind == "vote":
+            raise ValueError("a vote carries no magnitudes: there is no gradient to decode "
+                             "(decode_apply_vote steps the parameters)")
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
             if self.kind == "sign":

@@ -495,6 +495,105 @@ def adam_apply(p, m, v, vmax, g, lr, beta1, beta2, eps, weight_decay, step, amsg
     p.addcdiv_(m, denom, value=-lr * math.sqrt(bc2) / bc1)
 
 
+# ---------------------------------------------------------------------------------------------
+# Lion (Chen et al. 2023) and Distributed Lion's 1-bit vote (Liu et al. 2024).  The definition of
+# ``ops/csrc/lion.hip``: fp32 throughout, every product and sum rounded on its own, the betas, the
+# weight decay and the lr rounded to fp32 first and ``1 - beta`` formed in fp32.  With beta1 =
+# beta2 = 0 the vote is signSGD with majority vote (Bernstein et al. 2018), with beta1 = beta2
+# Signum.
+# ---------------------------------------------------------------------------------------------
+def _lion_betas(beta1: float, beta2: float):
+    f32 = np.float32
+    b1, b2 = f32(beta1), f32(beta2)
+    return float(b1), float(f32(1.0) - b1), float(b2), float(f32(1.0) - b2)
+
+
+def _lion_step(p: torch.Tensor, d: torch.Tensor, lr: float, weight_decay: float) -> torch.Tensor:
+    """``p - lr * (d + wd * p)`` (``wd == 0``: ``p - lr * d``, no product with p)."""
+    wd = float(np.float32(weight_decay))
+    if wd != 0.0:
+        d = d + p * wd
+    return p - d * float(np.float32(lr))
+
+
+def lion_apply(p, m, g, lr, beta1, beta2, weight_decay):
+    """Dense Lion on the flat views ``p`` / ``m`` with the already scaled gradient ``g``::
+
+        c = m * b1 + (1 - b1) * g
+        u = sign(c)                       (-1, 0, +1; 0 and NaN give 0)
+        p = p - lr * (u + wd * p)
+        m = m * b2 + (1 - b2) * g"""
+    b1, c1, b2, c2 = _lion_betas(beta1, beta2)
+    g = g.to(torch.float32)
+    c = m * b1 + g * c1
+    u = (c > 0).to(torch.float32) - (c < 0).to(torch.float32)
+    p.copy_(_lion_step(p, u, lr, weight_decay))
+    m.copy_(m * b2 + g * c2)
+
+
+def encode_vote(g: torch.Tensor, plan: BucketPlan, layout: Layout, exp_avg: torch.Tensor,
+                beta1: float, beta2: float, step: int, rank: int) -> torch.Tensor:
+    """This rank's vote of one bucket -> uint8 payload (``bits u32[256 C]``); ``exp_avg`` (the
+    rank's own momentum, the bucket's view) is updated in place.  ``g`` is the raw local gradient.
+
+    ``c = m * b1 + (1 - b1) * g``; the bit of chunk-local element i is ``(c < 0) | ((c == 0) & ((i
+    + step + rank) & 1))`` with the 1-based ``step``: set = -1, clear = +1, NaN gives 0, and an
+    exact zero (+0 or -0), which one bit cannot say, votes by that parity so that its votes cancel
+    over two steps and across an even world.  Bits past a chunk's length are 0.  Then ``m = m * b2
+    + (1 - b2) * g`` at every element of every tensor."""
+    if layout.kind != "vote":
+        raise ValueError(f"encode_vote given a {layout.kind!r} layout")
+    b1, c1, b2, c2 = _lion_betas(beta1, beta2)
+    g = g.to(torch.float32)[:plan.length]
+    m = exp_avg[:plan.length]
+    C = plan.num_chunks
+    pos, valid, _ = _sign_gather(plan, g.device)
+    c = (m * b1 + g * c1)[pos]
+    odd = ((torch.arange(CHUNK, dtype=torch.int64, device=g.device) + int(step) + int(rank)) & 1
+           ).bool()
+    neg = ((c < 0) | ((c == 0) & odd[None, :])) & valid
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=g.device)
+    sh = torch.arange(32, dtype=torch.int64, device=g.device)
+    words = (neg.reshape(C, CHUNK // 32, 32).to(torch.int64) << sh).sum(-1)
+    words = ((words + (1 << 31)) % (1 << 32)) - (1 << 31)  # uint32 bits as int32
+    _section(out, layout.codes, C * (CHUNK // 32), torch.int32).copy_(
+        words.to(torch.int32).flatten())
+    m[pos[valid]] = (m * b2 + g * c2)[pos[valid]]
+    return out
+
+
+def vote_counts(recv: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    """int32 ``[C, CHUNK]``: ``s = N - 2 * (set bits over the N rows of recv)`` per chunk element."""
+    C, N = plan.num_chunks, recv.shape[0]
+    sh = torch.arange(32, dtype=torch.int64, device=recv.device)
+    cnt = torch.zeros(C, CHUNK, dtype=torch.int32, device=recv.device)
+    for r in range(N):
+        words = _section(recv[r], layout.codes, C * (CHUNK // 32), torch.int32).to(torch.int64)
+        cnt += ((words[:, None] >> sh) & 1).reshape(C, CHUNK).to(torch.int32)
+    return N - 2 * cnt
+
+
+def vote_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, param: torch.Tensor,
+               lr: float, weight_decay: float, aggregate: str, inv_n: float) -> None:
+    """The receive side of the vote on the bucket view ``param`` (``recv``: uint8 ``[N, nbytes]``):
+    ``s`` of :func:`vote_counts`, ``d = (s > 0) - (s < 0)`` (``majority``; a tie gives 0) or
+    ``float(s) * inv_n`` (``average``; ``inv_n`` the fp32 value of 1 / N), then ``p = p - lr * (d
+    + wd * p)``.  Integer arithmetic up to ``d``: every rank forms the same update.  Positions
+    between tensors are not touched."""
+    if layout.kind != "vote":
+        raise ValueError(f"vote_apply given a {layout.kind!r} layout")
+    if aggregate not in ("majority", "average"):
+        raise ValueError("aggregate must be 'majority' or 'average'")
+    s = vote_counts(recv, plan, layout)
+    if aggregate == "majority":
+        d = torch.sign(s).to(torch.float32)
+    else:
+        d = s.to(torch.float32) * float(np.float32(inv_n))
+    pos, valid, _ = _sign_gather(plan, recv.device)
+    at = pos[valid]
+    param[at] = _lion_step(param[at], d[valid], lr, weight_decay)
+
+
 # Layer-wise trust ratios (LARS: You et al., 2017; LAMB: You et al., ICLR 2020).  The definition
 # of ``ops/csrc/layerwise.hip``.  ``p`` / ``g`` / the state are views of one flat range and
 # ``tensors`` its ``(offset, numel, adapts)`` rows: every norm runs over a tensor's own ``numel``

@@ -24,6 +24,8 @@ exchange is a fixed-size all-gather with no size handshake):
 ``qsgd``     : scales f32[T] | codes i8[D'] or nibbles  (dense; D' = numels padded to 16 per tensor)
 ``sign``     : scales f32[C] | bits u32[256 C]  (one scale per chunk; chunk c owns words [256 c,
                256 c + 256), element i of the chunk is bit i & 31 of word i >> 5, padding bits 0)
+``vote``     : bits u32[256 C]  (Distributed Lion: the words and bit addressing of ``sign``, no
+               scales section; exactly 1024 C bytes)
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -210,6 +212,11 @@ class Layout:
             off = _align(4 * C)
             counts = idx = codes = off
             off += 4 * BM_WORDS * C
+        elif kind == "vote":
+            # the chunks' bit words and nothing else (`codes` is their byte offset): 1024 C bytes
+            bits = 1
+            scales = counts = idx = codes = 0
+            off = 4 * BM_WORDS * C
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)

@@ -58,7 +58,8 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    compress: str = "topk_qsgd"  # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd
+    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote
+    compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
@@ -99,14 +100,19 @@ class Config:
     predivide: float = 1.0  # Horovod gradient_predivide_factor
     sync_bn: bool = False  # broadcast BN running stats from rank 0 at every checkpoint/eval
     # ---- optimizer -------------------------------------------------------------------------------
-    # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios):
-    # optim/flat.py
+    # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
+    # lion: optim/flat.py
     optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / onebit_adam
     # onebit_adam: dense Adam steps before the variance is frozen and the sign-compressed
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
     lars_eta: Optional[float] = None  # lars: trust coefficient (None: 0.001)
+    # lion: "B1,B2" (None: 0.9,0.99), each in [0, 1); resolved to a tuple of two floats
+    lion_betas: Optional[str] = None
+    # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
+    # signs (None: majority)
+    vote_aggregate: Optional[str] = None
     # clip this rank's raw gradient by its global L2 norm before the exchange reads it (DGC's
     # local gradient clipping, parallel/clip.py): coef = min(1, C / (norm + 1e-6)); None: off
     clip_grad_norm: Optional[float] = None
@@ -190,6 +196,48 @@ class Config:
                     c.sync_mode = "model"
         if c.compress_grad.lower() == "none":
             c.compress = "none"
+        if c.compress == "vote":
+            # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
+            # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
+            # can step on it and nothing that scales or compensates a magnitude applies
+            why = None
+            if c.optimizer != "lion":
+                why = (f"carries no magnitudes, only Lion's sign update can step on it: it needs "
+                       f"--optimizer lion, not {c.optimizer!r}")
+            elif c.topology != "allgather":
+                why = (f"is an all-gather of every rank's bits: it does not run with --topology "
+                       f"{c.topology} (a sharded or two-stage vote is out of scope)")
+            elif c.sync_every > 1:
+                why = "votes every step: it does not run with --sync-every > 1"
+            elif c.select_best:
+                why = "takes the vote of all workers: it does not run with --select-best"
+            elif c.predivide != 1.0:
+                why = ("counts signs, there is nothing to pre-divide: it does not run with "
+                       "--predivide other than 1")
+            elif c.error_feedback:
+                why = ("sends no magnitude that a residual could compensate: it does not run "
+                       "with --error-feedback")
+            if why is not None:
+                raise ValueError("--compress vote " + why)
+            c.error_feedback = False
+            if c.vote_aggregate is None:
+                c.vote_aggregate = "majority"
+            if c.vote_aggregate not in ("majority", "average"):
+                raise ValueError("--vote-aggregate must be majority or average")
+        elif c.vote_aggregate is not None:
+            raise ValueError("--vote-aggregate belongs to --compress vote")
+        if c.optimizer == "lion":
+            try:
+                raw = c.lion_betas or "0.9,0.99"  # a tuple when an already resolved Config
+                betas = tuple(float(v) for v in (raw.split(",") if isinstance(raw, str) else raw))
+            except (TypeError, ValueError):
+                betas = ()
+            if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+                raise ValueError(f"--lion-betas takes B1,B2 with each in [0, 1), not "
+                                 f"{c.lion_betas!r}")
+            c.lion_betas = betas
+        elif c.lion_betas is not None:
+            raise ValueError("--lion-betas belongs to --optimizer lion")
         if c.error_feedback is None:
             # only the all-gather exchange keeps a residual (parallel/engine.py
             # GradientExchange); the parameter-server / sharded exchanges have none, so their
@@ -365,7 +413,8 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # exchange
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
-      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd"])
+      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote"])
+    a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])
     a("--powersgd-rank", type=int, default=d.powersgd_rank)
     a("--topk-ratio", type=float, default=d.topk_ratio)
     a("--topk-dense-below", type=int, default=d.topk_dense_below)
@@ -392,7 +441,8 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
-      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb"])
+      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb", "lion"])
+    a("--lion-betas", type=str, default=None)
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)
     a("--lars-eta", type=float, default=None)

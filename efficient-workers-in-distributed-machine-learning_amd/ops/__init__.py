@@ -750,6 +750,78 @@ def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, 
                 grad_scale, int(amsgrad), _stream(), _ptr(step), float(lr), _lrp(lr_tensor))
 
 
+def lion_flat(param, exp_avg, grad, lr, beta1, beta2, weight_decay=0.0, grad_scale=1.0,
+              shadow=None, lr_tensor=None):
+    """Lion over flat fp32 buffers (``csrc/lion.hip``; bitwise ``compress/oracle.py lion_apply``
+    on ``grad * grad_scale``): any ``numel`` (16-byte accesses, scalar tail)."""
+    C = require()
+    _check(param, torch.float32, "param")
+    _check(exp_avg, torch.float32, "exp_avg")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    n = param.numel()
+    if n < 1 or grad.numel() != n or exp_avg.numel() != n:
+        raise ValueError("flat buffers must have equal, non-zero numel")
+    if shadow is not None:
+        _check(shadow, torch.bfloat16, "shadow", align=8)
+        if shadow.numel() != n:
+            raise ValueError("shadow must match param")
+    C.lion_flat(_ptr(param), _ptr(exp_avg), _ptr(grad), _ptr(shadow), n, _GDT[grad.dtype],
+                float(lr), float(beta1), float(beta2), float(weight_decay), float(grad_scale),
+                _stream(), _lrp(lr_tensor))
+
+
+def _check_vote_layout(dp, layout):
+    if layout.kind != "vote":
+        raise ValueError(f"vote codec given a {layout.kind!r} layout")
+    if layout.codes % 16 or layout.nbytes < layout.codes + 1024 * dp.plan.num_chunks:
+        raise ValueError("vote layout does not match the bucket plan")
+
+
+def lion_encode(dp, grad, payload, layout, exp_avg, beta1, beta2, step, rank, step_tensor=None):
+    """Distributed Lion's vote of one bucket (``csrc/lion.hip``): one bit per element, the sign of
+    ``exp_avg * beta1 + (1 - beta1) * grad`` (an exact zero votes by the parity of index + step +
+    rank), then ``exp_avg = exp_avg * beta2 + (1 - beta2) * grad``.  ``step``: the 1-based step,
+    read as ``step_tensor + 1`` (int32 device counter) when given.  One launch; bitwise
+    ``compress/oracle.py encode_vote``."""
+    C = require()
+    ptrs, mask = grad_pointers(dp, grad)
+    _check_vote_layout(dp, layout)
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+    _check_bucket(dp, exp_avg, "exp_avg")
+    if step_tensor is not None:
+        _check(step_tensor, torch.int32, "step", align=4)
+    C.lion_encode(ptrs, mask, _ptr(exp_avg), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
+                  dp.plan.num_tensors, dp.plan.num_chunks, layout.codes, float(beta1),
+                  float(beta2), int(step), _ptr(step_tensor), int(rank), _stream())
+
+
+def lion_vote_apply(dp, recv, layout, param, lr, weight_decay=0.0, aggregate="majority",
+                    inv_n=None, shadow=None, lr_tensor=None, key_state=None, key_seed=0,
+                    key_rank=0):
+    """The receive side of the vote: per element ``s = N - 2 * (set bits over the rows of recv)``,
+    ``d = sign(s)`` (``majority``) or ``s * inv_n`` (``average``; ``inv_n`` defaults to 1 / N),
+    ``param -= lr * (d + weight_decay * param)``.  Bitwise ``compress/oracle.py vote_apply``."""
+    C = require()
+    _check_vote_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 1 << 20:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+    if aggregate not in ("majority", "average"):
+        raise ValueError("aggregate must be 'majority' or 'average'")
+    _check_bucket(dp, param, "param")
+    _check_shadow(dp, shadow)
+    n = recv.shape[0]
+    C.lion_vote_apply(_ptr(recv), n, layout.nbytes, _ptr(dp.chunks), dp.plan.num_chunks,
+                      layout.codes, _ptr(param), _ptr(shadow), float(lr), float(weight_decay),
+                      float(1.0 / n if inv_n is None else inv_n), int(aggregate == "average"),
+                      _lrp(lr_tensor), _stream(), _keyp(key_state), key_seed & 0xFFFFFFFF,
+                      key_rank & 0xFFFFFFFF)
+
+
 # Longest chain of fp32 additions behind one chunk's sum of squares in k_lw_stage
 # (csrc/layerwise.hip): 32 serial terms per thread + 6 shuffle levels + 3 across the waves.  The
 # per-tensor sums over the chunks are fp64.

@@ -456,6 +456,78 @@ PYBIND11_MODULE(_C, m) {
           ew_adam_flat(a);
         });
 
+  m.def("lion_flat",
+        [](uintptr_t param, uintptr_t exp_avg, uintptr_t grad, uintptr_t shadow, long long n,
+           int grad_dtype, float lr, float beta1, float beta2, float weight_decay,
+           float grad_scale, uintptr_t stream, uintptr_t lr_ptr) {
+          LionFlatArgs a{};
+          a.param = param;
+          a.exp_avg = exp_avg;
+          a.grad = grad;
+          a.shadow = shadow;
+          a.stream = stream;
+          a.n = n;
+          a.grad_dtype = grad_dtype;
+          a.lr = lr;
+          a.beta1 = beta1;
+          a.beta2 = beta2;
+          a.weight_decay = weight_decay;
+          a.grad_scale = grad_scale;
+          a.lr_ptr = lr_ptr;
+          ew_lion_flat(a);
+        });
+
+  m.def("lion_encode",
+        [](const Ptrs& grads, const Mask& mask, uintptr_t exp_avg, uintptr_t chunks,
+           uintptr_t payload, long long payload_bytes, int T, int C, int bits_off, float beta1,
+           float beta2, int step, uintptr_t step_ptr, int rank, uintptr_t stream) {
+          LionEncodeArgs a{};
+          a.grad_ptrs = grads.data();
+          a.n_grad_ptrs = (int)grads.size();
+          a.bf16_mask = mask.data();
+          a.n_bf16_mask = (int)mask.size();
+          a.exp_avg = exp_avg;
+          a.chunks = chunks;
+          a.payload = payload;
+          a.stream = stream;
+          a.payload_bytes = payload_bytes;
+          a.num_tensors = T;
+          a.num_chunks = C;
+          a.bits_off = bits_off;
+          a.beta1 = beta1;
+          a.beta2 = beta2;
+          a.step = step;
+          a.step_ptr = step_ptr;
+          a.rank = rank;
+          ew_lion_encode(a);
+        });
+
+  m.def("lion_vote_apply",
+        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int bits_off,
+           uintptr_t param, uintptr_t shadow, float lr, float weight_decay, float inv_n,
+           int average, uintptr_t lr_ptr, uintptr_t stream, uintptr_t key_state,
+           uint32_t key_seed, uint32_t key_rank) {
+          LionVoteArgs a{};
+          a.recv = recv;
+          a.chunks = chunks;
+          a.param = param;
+          a.shadow = shadow;
+          a.stream = stream;
+          a.stride = stride;
+          a.nranks = nranks;
+          a.num_chunks = C;
+          a.bits_off = bits_off;
+          a.lr = lr;
+          a.weight_decay = weight_decay;
+          a.inv_n = inv_n;
+          a.average = average;
+          a.lr_ptr = lr_ptr;
+          a.key_state = key_state;
+          a.key_seed = key_seed;
+          a.key_rank = key_rank;
+          ew_lion_vote_apply(a);
+        });
+
   m.def("layerwise",
         [](int op, int kind, uintptr_t param, uintptr_t grad, int grad_dtype, uintptr_t state1,
            uintptr_t state2, uintptr_t shadow, uintptr_t chunks, int num_chunks,

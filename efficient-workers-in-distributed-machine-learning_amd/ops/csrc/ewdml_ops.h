@@ -192,6 +192,50 @@ struct AdamFlatArgs {
   uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
 };
 
+// Lion over a flat range (lion.hip k_lion_flat): the calling shape of AdamFlatArgs; n need not be
+// a multiple of 4 (scalar tail)
+struct LionFlatArgs {
+  uintptr_t param, exp_avg, grad, shadow, stream;
+  long long n;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  float lr, beta1, beta2, weight_decay, grad_scale;
+  uintptr_t lr_ptr;  // nullable device fp32 lr (overrides lr)
+};
+
+// Distributed Lion's 1-bit vote (lion.hip): payload = bits u32[256 * C] from bits_off, nothing else.
+// Encode: this rank's exp_avg (the bucket's view) is read and rewritten.  step: the 1-based step
+// of the exact-zero dither, read as *step_ptr + 1 when step_ptr (int32 device counter) is set.
+struct LionEncodeArgs {
+  const uintptr_t* grad_ptrs;
+  int n_grad_ptrs;
+  const uint32_t* bf16_mask;
+  int n_bf16_mask;
+  uintptr_t exp_avg, chunks, payload, stream;
+  long long payload_bytes;
+  int num_tensors, num_chunks;
+  int bits_off;
+  float beta1, beta2;
+  int step, rank;
+  uintptr_t step_ptr;
+};
+
+// Apply: s = nranks - 2 * (set bits over the rows of recv, stride bytes apart); d = sign(s)
+// (average 0) or float(s) * inv_n (average 1); p -= lr * (d + weight_decay * p)
+struct LionVoteArgs {
+  uintptr_t recv, chunks, param, shadow, stream;
+  long long stride;
+  int nranks, num_chunks;
+  int bits_off;
+  float lr, weight_decay, inv_n;
+  int average;
+  uintptr_t lr_ptr;
+  uintptr_t key_state;  // see TopkDecodeArgs
+  uint32_t key_seed, key_rank;
+};
+void ew_lion_flat(const LionFlatArgs& a);
+void ew_lion_encode(const LionEncodeArgs& a);
+void ew_lion_vote_apply(const LionVoteArgs& a);
+
 // LARS / LAMB over a flat range (layerwise.hip): chunks / tensors are the range's BucketPlan
 // tables; param, grad, state1, state2 and shadow its views.  adapt int32[T] (1: the tensor takes a
 // trust ratio), ratio fp32[T] (out), partials fp32[2 * num_chunks] (stage -> apply).

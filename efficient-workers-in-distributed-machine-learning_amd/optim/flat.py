@@ -236,6 +236,69 @@ class FlatOnebitAdam(FlatAdam):
         self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
 
 
+class FlatLion(_LrMixin):
+    """Lion (Chen et al., "Symbolic Discovery of Optimization Algorithms", 2023): the update is
+    the sign of an interpolation of the momentum and the gradient, ``p -= lr * (sign(m * beta1 +
+    (1 - beta1) * g) + wd * p)``, then ``m = m * beta2 + (1 - beta2) * g``; one state buffer, half
+    of Adam's.  ``step_range`` is the dense step (one HIP kernel over a flat range, the torch
+    oracle on the CPU).  Under the ``vote`` codec (Distributed Lion, Liu et al. 2024) the
+    exchange runs the step instead: every rank keeps its *own* ``exp_avg``, sends one bit per
+    element and applies the vote (``Codec.encode_vote`` / ``decode_apply_vote``).  ``step_t`` is
+    the device copy of the step count: the vote's exact-zero dither reads it, so a captured step
+    dithers with the current step."""
+    fusable = False
+    lion = True
+
+    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0):
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"Lion's betas must lie in [0, 1), not {betas!r}")
+        self.flat = flat
+        self._init_lr(lr, flat.data.device)
+        self.betas, self.weight_decay = (b1, b2), weight_decay
+        self.exp_avg = torch.zeros_like(flat.data)
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=flat.data.device) \
+            if flat.data.is_cuda else None
+
+    def hparams(self) -> dict:
+        return dict(lr=self.lr, betas=self.betas, weight_decay=self.weight_decay,
+                    step_t=self.step_t, lr_t=self.lr_t)
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        b1, b2 = self.betas
+        sl = slice(start, start + length)
+        p, m = self.flat.data[sl], self.exp_avg[sl]
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.lion_flat(p, m, grad, self.lr, b1, b2, self.weight_decay, grad_scale, shadow=sh,
+                          lr_tensor=self.lr_t)
+            return
+        g = grad.to(torch.float32)
+        if grad_scale != 1.0:
+            g = g * grad_scale
+        oracle.lion_apply(p, m, g, self.lr, b1, b2, self.weight_decay)
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    def state_dict(self):
+        return {"kind": "lion", "exp_avg": self.exp_avg, "steps": self.steps, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+
+
 class _Layerwise(_LrMixin):
     """Shared part of the layer-wise trust-ratio optimizers :class:`FlatLARS` / :class:`FlatLAMB`.
 
@@ -431,6 +494,9 @@ def make_optimizer(name, flat, **kw):
         return FlatAdam(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
                         eps=kw.get("eps", 1e-8),
                         amsgrad=(name == "amsgrad") or kw.get("amsgrad", False))
+    if name == "lion":
+        return FlatLion(flat, lr=kw.get("lr", 1e-4), betas=kw.get("betas") or (0.9, 0.99),
+                        weight_decay=kw.get("weight_decay", 0.0))
     if name == "onebit_adam":
         return FlatOnebitAdam(flat, lr=kw.get("lr", 1e-3),
                               weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),

@@ -110,6 +110,16 @@ class GradientExchange:
         if self.onebit and (codec.kind != "sign" or self.resid is None or predivide != 1.0):
             raise ValueError("1-bit Adam's compressed stage needs the sign codec with error "
                              "feedback and predivide 1")
+        # Distributed Lion (optim/flat.py FlatLion under the vote codec): the encode sends the sign
+        # of this rank's own update direction and moves this rank's own momentum, the apply
+        # counts the votes and steps.  No residual, no velocity; opt.exp_avg is per-rank state
+        self.vote = bool(getattr(optimizer, "lion", False)) and codec.kind == "vote"
+        if codec.kind == "vote" and not self.vote:
+            raise ValueError("the vote codec's payload carries no magnitudes: only Lion "
+                             "(optim/flat.py FlatLion), whose update is a sign, can step on it")
+        if self.vote and (self.resid is not None or predivide != 1.0):
+            raise ValueError("the vote exchange has no magnitude to compensate or to scale: it "
+                             "runs without error feedback and with predivide 1")
         self.gest = torch.zeros_like(flat.grad) if self.ef21 else None  # EF21's global G
         self.local_apply = False  # enable_local_apply
         self.local_apply_dense = False
@@ -349,6 +359,11 @@ class GradientExchange:
             else:
                 self.send[bi].copy_(g * (1.0 / self.predivide))
             return
+        if self.vote:  # sign(exp_avg * beta1 + (1 - beta1) * g) of this rank's own momentum
+            o = self.opt
+            self.codec.encode_vote(bi, g, self.payload[bi], o.exp_avg[b.start:b.start + b.length],
+                                   o.betas, o.steps + 1, self.comm.rank, step_tensor=o.step_t)
+            return
         resid = None if self.resid is None else self.resid[b.start:b.start + b.length]
         if self.onebit:  # sign(exp_avg * beta1 + (1 - beta1) * (g + wd * p) + residual)
             o = self.opt
@@ -478,6 +493,12 @@ class GradientExchange:
                     opt.step_range(b.start, b.length, G, 1.0)
                 elif self.local_apply:
                     continue  # applied by the encode's write pass (enable_local_apply)
+                elif self.vote:  # count the votes; p -= lr * (majority or average + wd * p)
+                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
+                    self.codec.decode_apply_vote(b.index, recv, self.flat.data_view(b),
+                                                 opt.hparams(), shadow=self.flat.shadow_view(b),
+                                                 key_state=self.key_state if adv else None,
+                                                 rank=self.comm.rank)
                 elif self.onebit:  # exp_avg = mean of the decoded momenta; frozen-variance step
                     adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     sl = slice(b.start, b.start + b.length)
@@ -786,7 +807,7 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
         return {"mode": "split", "splits": 1, "bucket_bytes": int(bucket_bytes), "wire_bytes": 0,
                 "reason": "PowerSGD: collectives between two graphs"}
     per_elem ={"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
-                "sign": 1.0 / 8.0}.get(codec_kind)
+                "sign": 1.0 / 8.0, "vote": 1.0 / 8.0}.get(codec_kind)
     payload = grad_numel * (per_elem or 0.0)
     # top-k payload per rank (estimate): k entries of one code byte (4-bit: half) + a 2-byte index
     pb = payload if per_elem is not None else grad_numel * topk_ratio * (2.0 + max(bits, 4) / 8.0)

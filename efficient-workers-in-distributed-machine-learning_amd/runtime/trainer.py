@@ -213,7 +213,8 @@ class Trainer:
         self.opt = make_optimizer(cfg.optimizer, self.flat, lr=lr, momentum=cfg.momentum,
                                   dampening=cfg.dampening, weight_decay=cfg.weight_decay,
                                   nesterov=cfg.nesterov, eps=cfg.adam_eps,
-                                  freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta)
+                                  freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta,
+                                  betas=cfg.lion_betas)
 
         # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
         # Adam share it); it runs once per step, after backward and before the first encode
@@ -229,6 +230,8 @@ class Trainer:
         # exchange ---------------------------------------------------------------------------------
         ckw = dict(ratio=cfg.topk_ratio, levels=cfg.qsgd_levels, bits=cfg.qsgd_bits,
                    norm=cfg.qsgd_norm, seed=cfg.seed, dense_below=cfg.topk_dense_below)
+        if cfg.compress == "vote":
+            ckw["aggregate"] = cfg.vote_aggregate
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
         self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
@@ -1030,6 +1033,13 @@ class Trainer:
                 allr = torch.zeros((self.world, r.numel()), dtype=r.dtype, device=r.device)
                 self.comm.all_gather(allr.view(-1), r)
                 extra[name] = allr
+        if getattr(inner, "vote", False):
+            # Distributed Lion: every rank's momentum is its own (the optimizer's state dict holds
+            # rank 0's): keep every rank's row
+            m = self.opt.exp_avg
+            allr = torch.zeros((self.world, m.numel()), dtype=m.dtype, device=m.device)
+            self.comm.all_gather(allr.view(-1), m)
+            extra["lion_momentum"] = allr
         if isinstance(inner, PowerSGDExchange):
             extra["powersgd_q"] = inner.q  # the warm start, the same on every rank: rank 0's
         if self.local_sgd:
@@ -1091,6 +1101,13 @@ class Trainer:
                     mine.copy_(r[self.rank].to(self.device))
                 else:
                     self.log.info(f"resume: world size changed, {name} reset")
+        if getattr(inner, "vote", False):
+            r = st["extra"].get("lion_momentum")
+            if r is not None and r.dim() == 2 and r.shape[0] == self.world:
+                self.opt.exp_avg.copy_(r[self.rank].to(self.device))
+            else:  # rank 0's momentum would make every rank vote alike
+                self.opt.exp_avg.zero_()
+                self.log.info("resume: world size changed, lion_momentum reset")
         if isinstance(inner, PowerSGDExchange) and st["extra"].get("powersgd_q") is not None:
             inner.q.copy_(st["extra"]["powersgd_q"].to(self.device))
         if self.local_sgd:
