@@ -480,11 +480,20 @@ def sgd_apply(p, buf, g, lr, momentum, dampening, weight_decay, nesterov, first)
 
 
 def adam_apply(p, m, v, vmax, g, lr, beta1, beta2, eps, weight_decay, step, amsgrad):
+    """Adam / AMSGrad in the reference form (``denom = sqrt(v) + eps``).  The betas are rounded to
+    the state's dtype first and ``1 - beta`` is formed in it, as ``ew_adam`` does in fp32:
+    ``1 - fp32(0.999)`` and ``fp32(1 - 0.999)`` differ by 1.3e-5 relative, and so would
+    ``exp_avg_sq`` between the CPU and the kernel.  The bias correction uses the same rounded
+    betas (the kernel's device-step path), so the decay and its correction stay consistent."""
     import math
+    one = torch.ones((), dtype=p.dtype)
+    b1, b2 = torch.tensor(beta1, dtype=p.dtype), torch.tensor(beta2, dtype=p.dtype)
+    c1, c2 = float(one - b1), float(one - b2)
+    beta1, beta2 = float(b1), float(b2)
     if weight_decay != 0:
         g = g + weight_decay * p
-    m.mul_(beta1).add_(g, alpha=1 - beta1)
-    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    m.mul_(beta1).add_(g, alpha=c1)
+    v.mul_(beta2).addcmul_(g, g, value=c2)
     if amsgrad:
         torch.maximum(vmax, v, out=vmax)
         denom = vmax.sqrt().add_(eps)

@@ -736,11 +736,17 @@ def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, 
     for t, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _check(t, torch.float32, nm)
     if amsgrad:
+        if max_exp_avg_sq is None:
+            raise ValueError("amsgrad needs max_exp_avg_sq")
         _check(max_exp_avg_sq, torch.float32, "max_exp_avg_sq")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
     _check(grad, grad.dtype, "grad", align=8)
     n = param.numel()
     if n % 4 or grad.numel() != n or exp_avg.numel() != n or exp_avg_sq.numel() != n:
         raise ValueError("flat buffers must have equal numel, a multiple of 4")
+    if amsgrad and max_exp_avg_sq.numel() != n:
+        raise ValueError("max_exp_avg_sq must match param")
     if shadow is not None:
         _check(shadow, torch.bfloat16, "shadow", align=8)
         if shadow.numel() != n:
