@@ -259,10 +259,16 @@ class Codec:
         """Bind the buckets' :class:`TwoStagePlan` s.  On the GPU every bucket gets its slot
         tables and every non-empty shard its chunk table (any rank may be asked to own any shard:
         the kernel tests drive all of them from one process)."""
-        if self.kind != "sign":
-            raise ValueError("the two-stage exchange needs the sign codec")
+        if self.kind not in ("sign", "vote"):
+            raise ValueError("the two-stage exchange needs the sign codec (or, for the two-stage "
+                             "vote, the vote codec)")
+        if self.kind == "vote" and self.aggregate != "majority":
+            raise ValueError("the two-stage vote returns one bit per element: a mean does not "
+                             "fit it (aggregate must be majority)")
         self.device = torch.device(device)
         self.ts = list(ts_plans)
+        if any(getattr(t, "kind", "sign") != self.kind for t in self.ts):
+            raise ValueError(f"the {self.kind} codec binds two-stage plans of kind {self.kind!r}")
         self.ts_dev = self.ts_shard_dev = None
         if self.device.type == "cuda" and not _FORCE_ORACLE:
             if ops.hip_required():
@@ -379,6 +385,61 @@ class Codec:
                 oracle.onebit_adam_apply(rows[r:r + 1, :lay.nbytes], sp, lay, param[sl],
                                          exp_avg[sl], exp_avg_sq[sl], 1.0, hp["lr_step"],
                                          hp["eps"])
+
+    # -- two-stage vote (parallel/twostage.py TwoStageVoteExchange): three launches per bucket ------
+    def ts_encode_vote(self, b: int, grad: torch.Tensor, rows: torch.Tensor,
+                       exp_avg: torch.Tensor, betas, step: int, rank: int,
+                       step_tensor: torch.Tensor = None):
+        """Push: this rank's vote (``encode_vote``) on every shard of bucket ``b`` of the flat
+        gradient view ``grad``, shard r into row r of ``rows`` (``[N, P]``); ``exp_avg`` (the
+        bucket's view of the rank's own momentum) then moves with ``beta2``.  One launch on the
+        GPU."""
+        if self.kind != "vote":
+            raise ValueError("the vote push needs the vote codec")
+        b1, b2 = betas
+        if self._ts_kernel(rows):
+            sl = self.ts_dev[b]
+            ops.lion_encode(sl, grad, rows, None, exp_avg, b1, b2, step, rank,
+                            step_tensor=step_tensor, slots=sl)
+            return
+        if isinstance(grad, (list, tuple)):
+            raise TypeError("CPU encode takes the bucket's flat gradient view")
+        for r, (s0, ln, sp, lay, _) in enumerate(self.ts[b].shards):
+            if sp is not None:
+                rows[r, :lay.nbytes].copy_(oracle.encode_vote(
+                    grad[s0:s0 + ln], sp, lay, exp_avg[s0:s0 + ln], b1, b2, step, rank))
+
+    def ts_vote_reduce(self, b: int, r: int, recv: torch.Tensor, out: torch.Tensor):
+        """Owner step of shard ``r`` of bucket ``b``: the N votes ``recv`` (``[N, P]``) become
+        one bit per element again in the row ``out``; a tie takes row ``r``'s (the owner's own)
+        vote.  One launch on the GPU; no parameter is touched."""
+        if self.kind != "vote":
+            raise ValueError("the vote owner step needs the vote codec")
+        _, _, sp, lay, _ = self.ts[b].shards[r]
+        if sp is None:
+            raise ValueError("an empty shard has no owner step")
+        if self._ts_kernel(recv):
+            ops.vote_reduce(self.ts_shard_dev[b][r], recv, lay, r, out)
+            return
+        out[:lay.nbytes].copy_(oracle.vote_reduce(recv, sp, lay, r))
+
+    def ts_decode_apply_vote(self, b: int, rows: torch.Tensor, param: torch.Tensor, hp: dict,
+                             shadow=None, key_state=None, rank: int = 0):
+        """Pull: every owner's row of the gathered ``rows`` (``[N, P]``) is the direction of its
+        shard (``d = 1 - 2 * bit``) and bucket ``b``'s parameters take Lion's step.  ``hp``:
+        ``FlatLion.hparams()``.  One launch on the GPU."""
+        if self.kind != "vote":
+            raise ValueError("the vote pull needs the vote codec")
+        if self._ts_kernel(rows):
+            sl = self.ts_dev[b]
+            ops.lion_vote_apply(sl, rows, None, param, hp["lr"], hp["weight_decay"], "majority",
+                                1.0, shadow=shadow, lr_tensor=hp.get("lr_t"),
+                                key_state=key_state, key_seed=self.seed, key_rank=rank, slots=sl)
+            return
+        for r, (s0, ln, sp, lay, _) in enumerate(self.ts[b].shards):
+            if sp is not None:
+                oracle.vote_apply(rows[r:r + 1, :lay.nbytes], sp, lay, param[s0:s0 + ln],
+                                  hp["lr"], hp["weight_decay"], "majority", 1.0)
 
     # -- PowerSGD (parallel/powersgd.py): four launches per bucket --------------------------------
     def bind_powersgd(self, lr_plans, device):

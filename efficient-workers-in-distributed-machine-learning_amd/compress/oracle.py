@@ -603,6 +603,41 @@ def vote_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, param: torc
     param[at] = _lion_step(param[at], d[valid], lr, weight_decay)
 
 
+def vote_reduce(recv: torch.Tensor, plan: BucketPlan, layout: Layout,
+                owner_row: int) -> torch.Tensor:
+    """The two-stage vote's owner step (``parallel/twostage.py TwoStageVoteExchange``): the N votes
+    on one shard (``recv``: uint8 ``[N, >= nbytes]``, ``plan`` / ``layout`` the shard's) -> one
+    uint8 payload of the same layout.  ``s`` of :func:`vote_counts`; the output bit is ``(s < 0)
+    | ((s == 0) & bit of row owner_row)``: one bit cannot say 0, so the owner's own vote decides a
+    tie -- deterministic, integer, and decided per shard (no rank decides globally).  Ties cannot
+    occur at odd N.  Padding bits are 0 in every row, so ``s = N > 0`` and they stay 0.
+
+    The push that fills ``recv`` is :func:`encode_vote` of every shard over its own plan.
+    ``shard_plans`` cuts at multiples of ``CHUNK`` and tensor offsets are multiples of 64, so every
+    element has the same chunk-local index parity in its shard's plan as in the bucket's plan:
+    the pushed votes are the very bits of the all-gather encode, placed elsewhere.  The pull is
+    :func:`vote_apply` of the owner's row alone (``majority``, N = 1: ``d = 1 - 2 * bit``).  At
+    odd N the two-stage result is therefore bitwise the all-gather majority vote's, and at even N
+    wherever ``s != 0``."""
+    if layout.kind != "vote":
+        raise ValueError(f"vote_reduce given a {layout.kind!r} layout")
+    N = recv.shape[0]
+    if not 0 <= int(owner_row) < N:
+        raise ValueError(f"owner row {owner_row} is not one of the {N} received rows")
+    C = plan.num_chunks
+    s = vote_counts(recv, plan, layout)
+    sh = torch.arange(32, dtype=torch.int64, device=recv.device)
+    own = _section(recv[owner_row], layout.codes, C * (CHUNK // 32), torch.int32).to(torch.int64)
+    own = ((own[:, None] >> sh) & 1).reshape(C, CHUNK).bool()
+    neg = (s < 0) | ((s == 0) & own)
+    words = (neg.reshape(C, CHUNK // 32, 32).to(torch.int64) << sh).sum(-1)
+    words = ((words + (1 << 31)) % (1 << 32)) - (1 << 31)  # uint32 bits as int32
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=recv.device)
+    _section(out, layout.codes, C * (CHUNK // 32), torch.int32).copy_(
+        words.to(torch.int32).flatten())
+    return out
+
+
 # Layer-wise trust ratios (LARS: You et al., 2017; LAMB: You et al., ICLR 2020).  The definition
 # of ``ops/csrc/layerwise.hip``.  ``p`` / ``g`` / the state are views of one flat range and
 # ``tensors`` its ``(offset, numel, adapts)`` rows: every norm runs over a tensor's own ``numel``

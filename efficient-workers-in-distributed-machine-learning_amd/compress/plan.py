@@ -226,8 +226,8 @@ MAX_SEGMENTS = 128  # EW_MAX_T in ops/csrc/common.h: the kernels' pointer-table 
 
 
 class TwoStagePlan:
-    """One bucket of the two-stage sign all-reduce (``parallel/twostage.py``), cut into one shard
-    per rank by ``parallel.sharded.shard_plans``.
+    """One bucket of the two-stage sign all-reduce or vote (``parallel/twostage.py``), cut into one
+    shard per rank by ``parallel.sharded.shard_plans``.
 
     ``plan``: the bucket's *shard-major* plan -- one "tensor" per segment (a tensor crossing a cut
     is two segments, each chunked from its own start), so its chunk list is the shards' chunk
@@ -239,15 +239,25 @@ class TwoStagePlan:
     shard r's payload ``scales f32[C_r] | bits u32[256 C_r]`` from byte 0.  ``slots[c] = (byte
     offset of chunk c's scale, byte offset of its 256 words)`` inside such a buffer -- the same
     table addresses the push rows (row r goes to rank r) and the all-gathered pull rows (row r
-    came from owner r).  Row padding and alignment pads are never written."""
+    came from owner r).  Row padding and alignment pads are never written.
 
-    def __init__(self, bucket_plan: BucketPlan, shards):
+    ``kind="vote"`` (the two-stage vote, ``TwoStageVoteExchange``): a shard's layout is the vote
+    codec's, ``bits u32[256 C_r]`` from byte 0 of its row and nothing else, so ``P = 1024 * max
+    C_r``.  ``slots[c]`` keeps its two-int shape so the device table and its checks are shared
+    with the sign codec; there is no scale, and both ints are the byte offset of the chunk's
+    words (the kernels read the second)."""
+
+    def __init__(self, bucket_plan: BucketPlan, shards, kind: str = "sign"):
+        if kind not in ("sign", "vote"):
+            raise ValueError(f"two-stage plans are built for the sign or the vote codec, not "
+                             f"{kind!r}")
+        self.kind = kind
         self.N = len(shards)
         numels, offsets = [], []
         self.shards = []
         c0 = 0
         for s0, ln, sp in shards:
-            lay = Layout.build("sign", sp) if sp is not None else None
+            lay = Layout.build(kind, sp) if sp is not None else None
             self.shards.append((s0, ln, sp, lay, c0))
             if sp is not None:
                 numels += sp.numels
@@ -265,10 +275,13 @@ class TwoStagePlan:
         self.max_shard = max(ln for _, ln, _, _, _ in self.shards)
         self.slots = []
         for r, (_, _, sp, lay, _) in enumerate(self.shards):
-            if sp is not None:
-                self.slots += [(r * self.P + lay.scales + 4 * c,
-                                r * self.P + lay.codes + 4 * BM_WORDS * c)
-                               for c in range(sp.num_chunks)]
+            if sp is None:
+                continue
+            words = [r * self.P + lay.codes + 4 * BM_WORDS * c for c in range(sp.num_chunks)]
+            if kind == "vote":
+                self.slots += [(w, w) for w in words]
+            else:
+                self.slots += [(r * self.P + lay.scales + 4 * c, w) for c, w in enumerate(words)]
         self.slot_end = max(w for _, w in self.slots) + 4 * BM_WORDS
 
     def slot_table(self, device) -> torch.Tensor:

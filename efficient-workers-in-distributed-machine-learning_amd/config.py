@@ -113,6 +113,10 @@ class Config:
     # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
     # signs (None: majority)
     vote_aggregate: Optional[str] = None
+    # --compress vote: allgather (every rank receives every rank's bits) | twostage (workers ->
+    # shard owners -> workers, one bit each way: parallel/twostage.py TwoStageVoteExchange)
+    # (None: allgather)
+    vote_exchange: Optional[str] = None
     # clip this rank's raw gradient by its global L2 norm before the exchange reads it (DGC's
     # local gradient clipping, parallel/clip.py): coef = min(1, C / (norm + 1e-6)); None: off
     clip_grad_norm: Optional[float] = None
@@ -206,7 +210,7 @@ class Config:
                        f"--optimizer lion, not {c.optimizer!r}")
             elif c.topology != "allgather":
                 why = (f"is an all-gather of every rank's bits: it does not run with --topology "
-                       f"{c.topology} (a sharded or two-stage vote is out of scope)")
+                       f"{c.topology} (the vote's own sharded form is --vote-exchange twostage)")
             elif c.sync_every > 1:
                 why = "votes every step: it does not run with --sync-every > 1"
             elif c.select_best:
@@ -224,8 +228,27 @@ class Config:
                 c.vote_aggregate = "majority"
             if c.vote_aggregate not in ("majority", "average"):
                 raise ValueError("--vote-aggregate must be majority or average")
+            if c.vote_exchange is None:
+                c.vote_exchange = "allgather"
+            if c.vote_exchange not in ("allgather", "twostage"):
+                raise ValueError("--vote-exchange must be allgather or twostage")
+            if c.vote_exchange == "twostage":
+                # workers -> shard owners -> workers (parallel/twostage.py TwoStageVoteExchange)
+                why = None
+                if c.vote_aggregate == "average":
+                    why = ("sends one bit per element back from the shard owners, and a mean "
+                           "does not fit one bit: it does not run with --vote-aggregate average")
+                elif c.hip_graph in ("full", "segmented"):
+                    why = (f"issues its two collectives and the owner step between two graphs: "
+                           f"--hip-graph {c.hip_graph} is not supported (auto resolves to split)")
+                if why is not None:
+                    raise ValueError("--vote-exchange twostage " + why)
+                if c.hip_graph == "auto":  # graph A -> eager collectives + owner step -> graph B
+                    c.hip_graph = "split"
         elif c.vote_aggregate is not None:
             raise ValueError("--vote-aggregate belongs to --compress vote")
+        elif c.vote_exchange is not None:
+            raise ValueError("--vote-exchange belongs to --compress vote")
         if c.optimizer == "lion":
             try:
                 raw = c.lion_betas or "0.9,0.99"  # a tuple when an already resolved Config
@@ -415,6 +438,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--compress", type=str, default=d.compress,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote"])
     a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])
+    a("--vote-exchange", type=str, default=None, choices=["allgather", "twostage"])
     a("--powersgd-rank", type=int, default=d.powersgd_rank)
     a("--topk-ratio", type=float, default=d.topk_ratio)
     a("--topk-dense-below", type=int, default=d.topk_dense_below)

@@ -785,47 +785,94 @@ def _check_vote_layout(dp, layout):
         raise ValueError("vote layout does not match the bucket plan")
 
 
-def lion_encode(dp, grad, payload, layout, exp_avg, beta1, beta2, step, rank, step_tensor=None):
+def _check_vote_slots(dp, slots, buf, name):
+    """As :func:`_check_slots`, for the slot table of a ``TwoStagePlan`` of kind ``vote``."""
+    if getattr(getattr(slots, "ts", None), "kind", None) != "vote":
+        raise ValueError("the vote kernels take the slot table of a vote two-stage plan")
+    return _check_slots(dp, slots, buf, name)
+
+
+def lion_encode(dp, grad, payload, layout, exp_avg, beta1, beta2, step, rank, step_tensor=None,
+                slots=None):
     """Distributed Lion's vote of one bucket (``csrc/lion.hip``): one bit per element, the sign of
     ``exp_avg * beta1 + (1 - beta1) * grad`` (an exact zero votes by the parity of index + step +
     rank), then ``exp_avg = exp_avg * beta2 + (1 - beta2) * grad``.  ``step``: the 1-based step,
     read as ``step_tensor + 1`` (int32 device counter) when given.  One launch; bitwise
-    ``compress/oracle.py encode_vote``."""
+    ``compress/oracle.py encode_vote``.  ``slots`` (:class:`SignSlots` of a vote two-stage plan,
+    also ``dp``): ``payload`` is the two-stage vote's ``[N, P]`` row buffer and every chunk's
+    words are written to its slot (``layout`` unused; nothing else is written)."""
     C = require()
     ptrs, mask = grad_pointers(dp, grad)
-    _check_vote_layout(dp, layout)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    if slots is not None:
+        sp, end = _check_vote_slots(dp, slots, payload, "payload")
+        nbytes, codes = payload.numel(), 0
+    else:
+        _check_vote_layout(dp, layout)
+        _check(payload, torch.uint8, "payload")
+        if payload.numel() < layout.nbytes:
+            raise ValueError("payload too small")
+        nbytes, codes, sp, end = layout.nbytes, layout.codes, 0, 0
     _check_bucket(dp, exp_avg, "exp_avg")
     if step_tensor is not None:
         _check(step_tensor, torch.int32, "step", align=4)
-    C.lion_encode(ptrs, mask, _ptr(exp_avg), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
-                  dp.plan.num_tensors, dp.plan.num_chunks, layout.codes, float(beta1),
-                  float(beta2), int(step), _ptr(step_tensor), int(rank), _stream())
+    C.lion_encode(ptrs, mask, _ptr(exp_avg), _ptr(dp.chunks), _ptr(payload), nbytes,
+                  dp.plan.num_tensors, dp.plan.num_chunks, codes, float(beta1),
+                  float(beta2), int(step), _ptr(step_tensor), int(rank), _stream(), sp, end)
+
+
+def vote_reduce(dp, recv, layout, owner_row, out):
+    """The two-stage vote's owner step for one shard (``dp``: :class:`SignTables` of the shard's
+    plan, ``layout`` its vote layout): per element ``s = N - 2 * (set bits over the rows of
+    recv)``; the bit written to ``out`` is ``(s < 0) | (s == 0 & the bit of row owner_row)``.
+    ``recv`` is ``[N, P]`` with ``P >= layout.nbytes``; only the words of ``out`` are written and
+    no parameter is touched.  Bitwise ``compress/oracle.py vote_reduce``."""
+    C = require()
+    _check_vote_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or not 1 <= recv.shape[0] <= 1 << 20:
+        raise ValueError("recv must be [nranks, P]")
+    if recv.shape[1] < layout.nbytes or recv.shape[1] % 16:
+        raise ValueError(f"recv rows must be 16-byte multiples of at least {layout.nbytes} bytes "
+                         "(row stride >= payload)")
+    if not 0 <= int(owner_row) < recv.shape[0]:
+        raise ValueError(f"owner row {owner_row} is not one of the {recv.shape[0]} received rows")
+    _check(out, torch.uint8, "out")
+    if out.numel() < layout.nbytes:
+        raise ValueError("out too small")
+    C.vote_reduce(_ptr(recv), recv.shape[0], recv.shape[1], int(owner_row), dp.plan.num_chunks,
+                  layout.codes, _ptr(out), out.numel(), _stream())
 
 
 def lion_vote_apply(dp, recv, layout, param, lr, weight_decay=0.0, aggregate="majority",
                     inv_n=None, shadow=None, lr_tensor=None, key_state=None, key_seed=0,
-                    key_rank=0):
+                    key_rank=0, slots=None):
     """The receive side of the vote: per element ``s = N - 2 * (set bits over the rows of recv)``,
     ``d = sign(s)`` (``majority``) or ``s * inv_n`` (``average``; ``inv_n`` defaults to 1 / N),
-    ``param -= lr * (d + weight_decay * param)``.  Bitwise ``compress/oracle.py vote_apply``."""
+    ``param -= lr * (d + weight_decay * param)``.  Bitwise ``compress/oracle.py vote_apply``.
+    ``slots`` (:class:`SignSlots` of a vote two-stage plan, also ``dp``): ``recv`` is the
+    two-stage vote's gathered ``[N, P]`` buffer, every chunk's words read once from its slot and
+    ``d = 1 - 2 * bit`` (``layout`` unused; ``majority`` only)."""
     C = require()
-    _check_vote_layout(dp, layout)
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 1 << 20:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
     if aggregate not in ("majority", "average"):
         raise ValueError("aggregate must be 'majority' or 'average'")
+    if slots is not None:
+        if aggregate != "majority":
+            raise ValueError("the slot-addressed apply takes each bit as the direction: majority")
+        sp, end = _check_vote_slots(dp, slots, recv, "recv")
+        n, stride, codes = 1, recv.numel(), 0
+    else:
+        _check_vote_layout(dp, layout)
+        _check(recv, torch.uint8, "recv")
+        if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 1 << 20:
+            raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
+        n, stride, codes, sp, end = recv.shape[0], layout.nbytes, layout.codes, 0, 0
     _check_bucket(dp, param, "param")
     _check_shadow(dp, shadow)
-    n = recv.shape[0]
-    C.lion_vote_apply(_ptr(recv), n, layout.nbytes, _ptr(dp.chunks), dp.plan.num_chunks,
-                      layout.codes, _ptr(param), _ptr(shadow), float(lr), float(weight_decay),
+    C.lion_vote_apply(_ptr(recv), n, stride, _ptr(dp.chunks), dp.plan.num_chunks,
+                      codes, _ptr(param), _ptr(shadow), float(lr), float(weight_decay),
                       float(1.0 / n if inv_n is None else inv_n), int(aggregate == "average"),
                       _lrp(lr_tensor), _stream(), _keyp(key_state), key_seed & 0xFFFFFFFF,
-                      key_rank & 0xFFFFFFFF)
+                      key_rank & 0xFFFFFFFF, sp, end)
 
 
 # Longest chain of fp32 additions behind one chunk's sum of squares in k_lw_stage

@@ -480,8 +480,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("lion_encode",
         [](const Ptrs& grads, const Mask& mask, uintptr_t exp_avg, uintptr_t chunks,
            uintptr_t payload, long long payload_bytes, int T, int C, int bits_off, float beta1,
-           float beta2, int step, uintptr_t step_ptr, int rank, uintptr_t stream) {
+           float beta2, int step, uintptr_t step_ptr, int rank, uintptr_t stream,
+           uintptr_t slots, long long slot_end) {
           LionEncodeArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.grad_ptrs = grads.data();
           a.n_grad_ptrs = (int)grads.size();
           a.bf16_mask = mask.data();
@@ -506,8 +509,10 @@ PYBIND11_MODULE(_C, m) {
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int bits_off,
            uintptr_t param, uintptr_t shadow, float lr, float weight_decay, float inv_n,
            int average, uintptr_t lr_ptr, uintptr_t stream, uintptr_t key_state,
-           uint32_t key_seed, uint32_t key_rank) {
+           uint32_t key_seed, uint32_t key_rank, uintptr_t slots, long long slot_end) {
           LionVoteArgs a{};
+          a.slots = slots;
+          a.slot_end = slot_end;
           a.recv = recv;
           a.chunks = chunks;
           a.param = param;
@@ -526,6 +531,22 @@ PYBIND11_MODULE(_C, m) {
           a.key_seed = key_seed;
           a.key_rank = key_rank;
           ew_lion_vote_apply(a);
+        });
+
+  m.def("vote_reduce",
+        [](uintptr_t recv, int nranks, long long stride, int owner, int C, int bits_off,
+           uintptr_t out, long long out_bytes, uintptr_t stream) {
+          VoteReduceArgs a{};
+          a.recv = recv;
+          a.out = out;
+          a.stream = stream;
+          a.stride = stride;
+          a.out_bytes = out_bytes;
+          a.nranks = nranks;
+          a.owner = owner;
+          a.num_chunks = C;
+          a.bits_off = bits_off;
+          ew_vote_reduce(a);
         });
 
   m.def("layerwise",

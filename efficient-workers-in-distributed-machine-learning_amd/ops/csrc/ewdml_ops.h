@@ -217,6 +217,12 @@ struct LionEncodeArgs {
   float beta1, beta2;
   int step, rank;
   uintptr_t step_ptr;
+  // slot-addressed form (slots != 0; the two-stage vote's push): int2 per chunk, .y = the byte
+  // offset of its 256 words in `payload`, an [N, P] row buffer of payload_bytes bytes (.x, the sign
+  // codec's scale offset, is not read); slot_end = the largest offset a slot reaches; bits_off is
+  // unused
+  uintptr_t slots;
+  long long slot_end;
 };
 
 // Apply: s = nranks - 2 * (set bits over the rows of recv, stride bytes apart); d = sign(s)
@@ -231,10 +237,23 @@ struct LionVoteArgs {
   uintptr_t lr_ptr;
   uintptr_t key_state;  // see TopkDecodeArgs
   uint32_t key_seed, key_rank;
+  uintptr_t slots;  // see LionEncodeArgs: recv is the gathered row buffer (stride = its bytes),
+  long long slot_end;  // nranks must be 1 and average 0 (d = 1 - 2 * bit)
+};
+
+// The two-stage vote's owner step: per element of the owner's shard (num_chunks chunks, words from
+// bits_off of every row) s = nranks - 2 * (set bits over the rows of recv, stride bytes apart); the
+// bit written to `out` (out_bytes bytes, same layout) is (s < 0) | (s == 0 & the bit of row owner)
+struct VoteReduceArgs {
+  uintptr_t recv, out, stream;
+  long long stride, out_bytes;
+  int nranks, owner, num_chunks;
+  int bits_off;
 };
 void ew_lion_flat(const LionFlatArgs& a);
 void ew_lion_encode(const LionEncodeArgs& a);
 void ew_lion_vote_apply(const LionVoteArgs& a);
+void ew_vote_reduce(const VoteReduceArgs& a);
 
 // LARS / LAMB over a flat range (layerwise.hip): chunks / tensors are the range's BucketPlan
 // tables; param, grad, state1, state2 and shadow its views.  adapt int32[T] (1: the tensor takes a

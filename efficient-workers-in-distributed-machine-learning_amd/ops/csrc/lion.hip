@@ -16,6 +16,12 @@
 // by the parity of i + step + rank: its votes cancel over two steps and across an even world.
 //
 // The decode counts set bits in integers, so every rank forms the same update by construction.
+//
+// The two-stage vote (parallel/twostage.py TwoStageVoteExchange) adds a slot-addressed form of the
+// encode and of the apply -- `slots` (int2 per chunk of the shard-major plan, compress/plan.py
+// TwoStagePlan kind "vote") holds in .y the byte offset of the chunk's 256 words inside an [N, P]
+// row buffer (.x is the sign codec's scale offset and is not read) -- and the owner step
+// k_vote_reduce, which turns the N votes on a shard into one bit per element again.
 #include "common.h"
 #include "ewdml_ops.h"
 
@@ -91,12 +97,15 @@ __device__ __forceinline__ uint32_t ew_lion_bit(float c, bool valid, uint32_t od
   return (uint32_t)(valid && (c < 0.0f || (c == 0.0f && odd)));
 }
 
+// SLOT: chunk c's words go to byte slots[c].y of `payload` (the two-stage push's [N, P] rows)
+// and bits_off is not read; otherwise to the bucket's own layout (slots is not read).
+template <bool SLOT>
 __global__ __launch_bounds__(EW_BLOCK) void k_lion_encode(GradPtrs gp, float* __restrict__ mom,
                                                           const ChunkRow* __restrict__ chunks,
                                                           uint8_t* __restrict__ payload,
                                                           int bits_off, float beta1, float beta2,
                                                           int step, const int* __restrict__ step_ptr,
-                                                          int rank) {
+                                                          int rank, const int2* __restrict__ slots) {
   const ChunkRow c = chunks[blockIdx.x];
   if (step_ptr) step = *step_ptr + 1;  // the 1-based step of this replay
   float4 g[EW_CU], m[EW_CU];
@@ -125,8 +134,9 @@ __global__ __launch_bounds__(EW_BLOCK) void k_lion_encode(GradPtrs gp, float* __
     w |= __shfl_xor(w, 4, 64);
     mine = (u == k) ? w : mine;
   }
-  uint32_t* words =
-      reinterpret_cast<uint32_t*>(payload + (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS);
+  const size_t words_at =
+      SLOT ? (size_t)slots[blockIdx.x].y : (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS;
+  uint32_t* words = reinterpret_cast<uint32_t*>(payload + words_at);
   words[k * (EW_BLOCK / 8) + (threadIdx.x >> 3)] = mine;
 
 #pragma unroll
@@ -137,12 +147,14 @@ __global__ __launch_bounds__(EW_BLOCK) void k_lion_encode(GradPtrs gp, float* __
 }
 
 // s = N - 2 * (set bits over the N rows), an integer; majority: d = sign(s), a tie gives 0;
-// average: d = float(s) * inv_n
-template <bool AVG>
+// average: d = float(s) * inv_n.  SLOT (the two-stage pull; nranks = 1, so d = 1 - 2 * bit): chunk
+// c's words are read at byte slots[c].y of `recv`, the gathered [N, P] rows.
+template <bool AVG, bool SLOT>
 __global__ __launch_bounds__(EW_BLOCK) void k_lion_vote_apply(
     const uint8_t* __restrict__ recv, int nranks, long long stride,
     const ChunkRow* __restrict__ chunks, int bits_off, float* __restrict__ param,
-    uint16_t* __restrict__ shadow, LionArgs a, float inv_n, SgdArgs key) {
+    uint16_t* __restrict__ shadow, LionArgs a, float inv_n, SgdArgs key,
+    const int2* __restrict__ slots) {
   const ChunkRow c = chunks[blockIdx.x];
   ew_lion_resolve(a);
   ew_key_advance(key);
@@ -152,7 +164,8 @@ __global__ __launch_bounds__(EW_BLOCK) void k_lion_vote_apply(
   for (int u = 0; u < EW_CU; ++u)
 #pragma unroll
     for (int j = 0; j < 4; ++j) cnt[u][j] = 0;
-  const size_t words_at = (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS;
+  const size_t words_at =
+      SLOT ? (size_t)slots[blockIdx.x].y : (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS;
   for (int r = 0; r < nranks; ++r) {
     const uint32_t* words =
         reinterpret_cast<const uint32_t*>(recv + r * stride + words_at) + (threadIdx.x >> 3);
@@ -196,6 +209,56 @@ __global__ __launch_bounds__(EW_BLOCK) void k_lion_vote_apply(
   }
 }
 
+// The two-stage vote's owner step: one block per chunk of the owner's shard.  Per element s = N -
+// 2 * (set bits over the N rows of recv), counted in integer registers as above; the output bit is
+// (s < 0) | (s == 0 & the bit of row `owner`): one bit cannot say 0, so the owner's own vote breaks
+// a tie.  Padding bits are 0 in every row, so s = N > 0 and they stay 0: no chunk table is read.
+// Packed as in k_lion_encode, one dword store per thread into the owner's row `out`.
+__global__ __launch_bounds__(EW_BLOCK) void k_vote_reduce(const uint8_t* __restrict__ recv,
+                                                          int nranks, long long stride, int owner,
+                                                          int bits_off, uint8_t* __restrict__ out) {
+  const int k = threadIdx.x & 7, shift = 4 * k;
+  int cnt[EW_CU][4];
+  uint32_t own[EW_CU];
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    own[u] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cnt[u][j] = 0;
+  }
+  const size_t words_at = (size_t)bits_off + 4 * (size_t)blockIdx.x * EW_BM_WORDS;
+  for (int r = 0; r < nranks; ++r) {
+    const uint32_t* words =
+        reinterpret_cast<const uint32_t*>(recv + r * stride + words_at) + (threadIdx.x >> 3);
+    uint32_t w[EW_CU];
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u) w[u] = words[u * (EW_BLOCK / 8)];
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u) {
+      const uint32_t nib = (w[u] >> shift) & 15u;
+      own[u] = (r == owner) ? nib : own[u];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cnt[u][j] += (int)((nib >> j) & 1u);
+    }
+  }
+  uint32_t mine = 0;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int s = nranks - 2 * cnt[u][j];
+      w |= (uint32_t)(s < 0 || (s == 0 && ((own[u] >> j) & 1u))) << j;
+    }
+    w <<= shift;
+    w |= __shfl_xor(w, 1, 64);
+    w |= __shfl_xor(w, 2, 64);
+    w |= __shfl_xor(w, 4, 64);
+    mine = (u == k) ? w : mine;
+  }
+  reinterpret_cast<uint32_t*>(out + words_at)[k * (EW_BLOCK / 8) + (threadIdx.x >> 3)] = mine;
+}
+
 inline int ew_lion_grid(long long n4) {
   long long b = (n4 + EW_BLOCK - 1) / EW_BLOCK;
   return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048);  // 8 blocks per CU, grid-stride the rest
@@ -228,25 +291,61 @@ static void ew_vote_fit(const std::string& who, int bits_off, int C, long long b
     throw std::runtime_error(who + ": the bit words do not fit the payload");
 }
 
+// Slot-addressed: every slot of the table must lie inside the row buffer.  slot_end is the largest
+// byte offset a slot reaches (compress/plan.py TwoStagePlan; ops/__init__.py checks each slot).
+static void ew_vote_slots_fit(const std::string& who, long long slot_end, long long bytes) {
+  if (slot_end < 4LL * EW_BM_WORDS || slot_end > bytes || slot_end > 0x7fffffffLL)
+    throw std::runtime_error(who + ": the slot table does not fit the row buffer");
+}
+
 void ew_lion_encode(const LionEncodeArgs& a) {
   const int C = a.num_chunks;
   if (C <= 0) throw std::runtime_error("ewdml lion encode: empty bucket");
-  ew_vote_fit("ewdml lion encode", a.bits_off, C, a.payload_bytes);
+  if (a.slots) ew_vote_slots_fit("ewdml lion encode", a.slot_end, a.payload_bytes);
+  else ew_vote_fit("ewdml lion encode", a.bits_off, C, a.payload_bytes);
   if (!a.exp_avg || !a.payload || !a.chunks)
     throw std::runtime_error("ewdml lion encode: needs exp_avg, the payload and the chunk table");
   GradPtrs g;
   ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
-  EW_LAUNCH(k_lion_encode, C, a.stream, g, reinterpret_cast<float*>(a.exp_avg),
-            reinterpret_cast<const ChunkRow*>(a.chunks), reinterpret_cast<uint8_t*>(a.payload),
-            a.bits_off, a.beta1, a.beta2, a.step, reinterpret_cast<const int*>(a.step_ptr),
-            a.rank);
+  auto* mom = reinterpret_cast<float*>(a.exp_avg);
+  auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
+  auto* payload = reinterpret_cast<uint8_t*>(a.payload);
+  auto* step_ptr = reinterpret_cast<const int*>(a.step_ptr);
+  auto* slots = reinterpret_cast<const int2*>(a.slots);
+  if (slots)
+    EW_LAUNCH(k_lion_encode<true>, C, a.stream, g, mom, chunks, payload, a.bits_off, a.beta1,
+              a.beta2, a.step, step_ptr, a.rank, slots);
+  else
+    EW_LAUNCH(k_lion_encode<false>, C, a.stream, g, mom, chunks, payload, a.bits_off, a.beta1,
+              a.beta2, a.step, step_ptr, a.rank, slots);
+  EW_CHECK_LAUNCH();
+}
+
+void ew_vote_reduce(const VoteReduceArgs& a) {
+  const int C = a.num_chunks;
+  if (C <= 0 || a.nranks <= 0) throw std::runtime_error("ewdml vote reduce: nothing to reduce");
+  if (a.owner < 0 || a.owner >= a.nranks)
+    throw std::runtime_error("ewdml vote reduce: the owner row is not one of the received rows");
+  if (a.stride % 16) throw std::runtime_error("ewdml vote reduce: rows must be 16-byte multiples");
+  ew_vote_fit("ewdml vote reduce", a.bits_off, C, a.stride);
+  ew_vote_fit("ewdml vote reduce (out)", a.bits_off, C, a.out_bytes);
+  if (!a.recv || !a.out) throw std::runtime_error("ewdml vote reduce: needs the rows and the output");
+  EW_LAUNCH(k_vote_reduce, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv), a.nranks,
+            a.stride, a.owner, a.bits_off, reinterpret_cast<uint8_t*>(a.out));
   EW_CHECK_LAUNCH();
 }
 
 void ew_lion_vote_apply(const LionVoteArgs& a) {
   const int C = a.num_chunks;
   if (C <= 0 || a.nranks <= 0) throw std::runtime_error("ewdml lion vote: nothing to decode");
-  ew_vote_fit("ewdml lion vote", a.bits_off, C, a.stride);
+  if (a.slots) {
+    if (a.nranks != 1 || a.average)
+      throw std::runtime_error("ewdml lion vote: the slot-addressed apply reads one row buffer and "
+                               "takes its bit as the direction");
+    ew_vote_slots_fit("ewdml lion vote", a.slot_end, a.stride);
+  } else {
+    ew_vote_fit("ewdml lion vote", a.bits_off, C, a.stride);
+  }
   if (!a.recv || !a.param || !a.chunks)
     throw std::runtime_error("ewdml lion vote: needs the received rows, the parameters and the "
                              "chunk table");
@@ -259,11 +358,15 @@ void ew_lion_vote_apply(const LionVoteArgs& a) {
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
   auto* p = reinterpret_cast<float*>(a.param);
   auto* sh = reinterpret_cast<uint16_t*>(a.shadow);
-  if (a.average)
-    EW_LAUNCH(k_lion_vote_apply<true>, C, a.stream, recv, a.nranks, a.stride, chunks, a.bits_off,
-              p, sh, la, a.inv_n, key);
+  auto* slots = reinterpret_cast<const int2*>(a.slots);
+  if (slots)
+    EW_LAUNCH((k_lion_vote_apply<false, true>), C, a.stream, recv, a.nranks, a.stride, chunks,
+              a.bits_off, p, sh, la, a.inv_n, key, slots);
+  else if (a.average)
+    EW_LAUNCH((k_lion_vote_apply<true, false>), C, a.stream, recv, a.nranks, a.stride, chunks,
+              a.bits_off, p, sh, la, a.inv_n, key, slots);
   else
-    EW_LAUNCH(k_lion_vote_apply<false>, C, a.stream, recv, a.nranks, a.stride, chunks, a.bits_off,
-              p, sh, la, a.inv_n, key);
+    EW_LAUNCH((k_lion_vote_apply<false, false>), C, a.stream, recv, a.nranks, a.stride, chunks,
+              a.bits_off, p, sh, la, a.inv_n, key, slots);
   EW_CHECK_LAUNCH();
 }

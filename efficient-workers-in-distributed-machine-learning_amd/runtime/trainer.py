@@ -32,7 +32,7 @@ from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
 from ..parallel.sharded import ShardedPSExchange
 from ..parallel.powersgd import PowerSGDExchange
-from ..parallel.twostage import TwoStageSignExchange
+from ..parallel.twostage import TwoStageSignExchange, TwoStageVoteExchange
 from ..utils import checkpoint as ckpt
 from ..utils.metrics import MetricsLogger, accuracy, byte_summary
 
@@ -172,8 +172,11 @@ class Trainer:
         # pointer-mode gradients (read in place by the HIP kernels) for the all-to-all exchange
         # and local SGD (its local steps read them through the same pointer tables); the
         # parameter server keeps flat gradient views
-        # (and PowerSGD, whose project launch reads the flat gradient buffer)
+        # (and PowerSGD, whose project launch reads the flat gradient buffer, and the two-stage
+        # vote, whose push encode does)
+        vote_ts = cfg.compress == "vote" and cfg.vote_exchange == "twostage"
         ptr_grads = (self.cuda and cfg.topology == "allgather" and cfg.compress != "powersgd"
+                     and not vote_ts
                      and os.environ.get("EWDML_GRAD_VIEWS") != "1")
         bf16_params = (ptr_grads and cfg.amp == "bf16" and cfg.param_dtype == "auto"
                        and not self.amp_kept_fp32)
@@ -249,6 +252,10 @@ class Trainer:
                                              make_codec("powersgd", seed=cfg.seed,
                                                         rank=cfg.powersgd_rank), self.opt,
                                              clipper=self.clipper)
+        elif vote_ts:
+            self.exchange = TwoStageVoteExchange(self.flat, self.comm,
+                                                 make_codec(cfg.compress, **ckw), self.opt,
+                                                 clipper=self.clipper)
         elif cfg.topology == "twostage" and cfg.optimizer != "onebit_adam":
             self.exchange = TwoStageSignExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt,
@@ -313,6 +320,7 @@ class Trainer:
                     or isinstance(self.exchange, ShardedPSExchange)
                     # 1-bit Adam's dense warm-up runs split too: one graph mode for both stages
                     or cfg.topology == "twostage"
+                    or isinstance(self.exchange, TwoStageVoteExchange)
                     # PowerSGD: graph A = ..., project -> eager all-reduces, orthogonalise and
                     # back-project -> graph B = reconstruct + step
                     or isinstance(self.exchange, PowerSGDExchange))
