@@ -524,6 +524,38 @@ class Codec:
         oracle.onebit_adam_apply(recv, plan, lay, param, exp_avg, exp_avg_sq, inv_n,
                                  hp["lr_step"], hp["eps"])
 
+    def decode_apply_onebit_lamb(self, b: int, recv: torch.Tensor, inv_n: float,
+                                 param: torch.Tensor, exp_avg: torch.Tensor,
+                                 exp_avg_sq: torch.Tensor, exp_avg_sq_fresh: torch.Tensor,
+                                 hp: dict, shadow=None, key_state=None, rank: int = 0):
+        """1-bit LAMB's receive side of bucket ``b``: ``exp_avg`` = the mean of the decoded
+        momenta, the fresh variance, the per-tensor factor and the trust-ratio step (two kernels
+        on the GPU, ``oracle.onebit_lamb_apply`` on the CPU).  ``hp``:
+        ``FlatOnebitLamb.hparams(start, length)`` of the bucket (on the GPU ``step_t`` / ``lr_t``
+        make the kernels read the step and the lr from device memory)."""
+        if self.kind != "sign":
+            raise ValueError("the 1-bit LAMB step needs the sign codec")
+        plan, lay = self.plans[b], self.layouts[b]
+        kw = dict(lr=hp["lr"], eps=hp["eps"], freeze_step=hp["freeze_step"],
+                  factor_min=hp["factor_min"], factor_max=hp["factor_max"],
+                  factor_threshold=hp["factor_threshold"])
+        t = hp["t"]
+        if recv.is_cuda and not _FORCE_ORACLE:
+            ops.onebit_lamb_step(hp["tables"](self.dplans[b]), recv, lay, param, exp_avg,
+                                 exp_avg_sq, exp_avg_sq_fresh, inv_n, betas=hp["betas"],
+                                 weight_decay=hp["weight_decay"], t=t, step=hp.get("step_t"),
+                                 lr_tensor=hp.get("lr_t"), shadow=shadow, key_state=key_state,
+                                 key_seed=self.seed, key_rank=rank, **kw)
+            return
+        b1, b2 = hp["betas"]
+        fac = hp["factors"]
+        ratios, factors = oracle.onebit_lamb_apply(
+            recv, plan, lay, param, exp_avg, exp_avg_sq, exp_avg_sq_fresh, hp["tensors"],
+            hp["r_frozen"], fac[(t - 1) & 1], inv_n, b1=b1, b2=b2, wd=hp["weight_decay"], step=t,
+            **kw)
+        hp["ratio"].copy_(ratios)
+        fac[t & 1].copy_(factors)
+
     def decode(self, b: int, recv: torch.Tensor, out: torch.Tensor, scale: float):
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""
         if self.kind == "vote":

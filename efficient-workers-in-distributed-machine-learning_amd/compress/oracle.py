@@ -22,6 +22,9 @@ Reference semantics being reproduced:
   * 1-bit Adam's compressed stage (no reference counterpart; Tang et al., ICML 2021):
     ``encode_sign_momentum`` (the sign encode of the error-compensated momentum candidate) and
     ``onebit_adam_apply`` (averaged momentum, frozen-variance step), bitwise the kernels'.
+  * 1-bit LAMB's compressed stage (no reference counterpart; Li et al., 2021): the same sender
+    with weight decay 0 and ``onebit_lamb_apply`` (averaged momentum, fresh variance, per-tensor
+    factor on the frozen trust ratio), bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -356,6 +359,79 @@ def onebit_adam_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, para
         root = v.to(torch.float64).sqrt().to(torch.float32)
         step = (m / (root + float(f32(eps)))) * float(f32(lr_step))
         param[sl] = torch.where(v > 0, p - step, p)
+
+
+def onebit_lamb_apply(recv: torch.Tensor, plan: BucketPlan, layout: Layout, param: torch.Tensor,
+                      exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                      exp_avg_sq_fresh: torch.Tensor, tensors, r_frozen: torch.Tensor,
+                      last_factor: torch.Tensor, inv_n: float, lr: float, b1: float, b2: float,
+                      eps: float, wd: float, step: int, freeze_step: int, factor_min: float = 0.5,
+                      factor_max: float = 4.0, factor_threshold: float = 0.1, bc1: float = None):
+    """1-bit LAMB's compressed stage (Li et al., 2021), receiver side, on the bucket views
+    ``param`` / ``exp_avg`` / ``exp_avg_sq`` (frozen, only read) / ``exp_avg_sq_fresh``; ``tensors``
+    are the bucket's ``(offset, numel, adapts)`` rows, ``r_frozen`` / ``last_factor`` (only read)
+    their fp32 entries.  Every operation is rounded to fp32 on its own; ``1 - b1`` and ``1 - b2``
+    are formed in fp32 (as the momentum encode forms its ``1 - beta1``), ``bc1 = 1 - b1^step``
+    and ``1 - b2^freeze_step`` in double, then rounded (``bc1``: the caller's value instead)::
+
+        m     = inv_n * sum_r decode(r)                      (rank order, from 0)
+        g     = (m - m_old * b1) / (1 - b1)
+        vf    = vf * b2 + (1 - b2) * (g * g)                 exp_avg = m, exp_avg_sq_fresh = vf
+        q     = (sqrt(v) + eps) / (sqrt(vf) + eps)           where the frozen v > 0
+        f_raw = max(0, max q)                                a NaN q does not enter
+        u     = (m / bc1) / (sqrt(v / bc2(freeze_step)) + eps) [+ wd * p]
+        p    -= (lr * r) * u                                 where v > 0
+
+    with ``r = 1`` for a tensor that does not adapt, ``r = r_frozen`` when ``f_raw == 0`` (both keep
+    their ``last_factor``), and otherwise ``f = clamp(clamp(f_raw, factor_min, factor_max),
+    last_factor * (1 - factor_threshold), last_factor * (1 + factor_threshold))``, ``r = r_frozen
+    * f``.  Positions between tensors are not touched.  Returns ``(ratios, factors)``: the
+    tensors' ``r`` and their new ``last_factor``."""
+    f32 = np.float32
+    if step <= freeze_step or freeze_step < 1:
+        raise ValueError("the compressed stage starts after freeze_step >= 1")
+    m_all = decode_sum(recv, plan, layout, 0, inv_n)
+    b1f, b2f, epsf, wdf = f32(b1), f32(b2), f32(eps), f32(wd)
+    omb1, omb2 = f32(1.0) - b1f, f32(1.0) - b2f
+    bc1 = f32(1.0 - b1 ** step) if bc1 is None else f32(bc1)
+    bc2w = f32(1.0 - b2 ** freeze_step)
+    fmin, fmax = f32(factor_min), f32(factor_max)
+    lo_k, hi_k = f32(1.0) - f32(factor_threshold), f32(1.0) + f32(factor_threshold)
+
+    def root(x):  # the correctly rounded fp32 square root: see onebit_adam_apply
+        return x.to(torch.float64).sqrt().to(torch.float32)
+
+    def over(x, c):  # x / c as an elementwise IEEE divide (never a product with 1 / c)
+        return x / torch.full_like(x, float(c))
+
+    ratios = torch.ones(len(tensors), dtype=torch.float32, device=param.device)
+    factors = last_factor.clone()
+    for t, (off, n, adapts) in enumerate(tensors):
+        sl = slice(off, off + n)
+        m, v, p = m_all[sl], exp_avg_sq[sl], param[sl]
+        g = over(m - exp_avg[sl] * float(b1f), omb1)
+        vf = exp_avg_sq_fresh[sl] * float(b2f) + (g * g) * float(omb2)
+        exp_avg[sl] = m
+        exp_avg_sq_fresh[sl] = vf
+        live = v > 0
+        q = (root(v) + float(epsf)) / (root(vf) + float(epsf))
+        q = q[live & ~torch.isnan(q)]
+        f_raw = f32(max(0.0, float(q.max()))) if q.numel() else f32(0.0)
+        r = f32(1.0)
+        if adapts:
+            r = f32(r_frozen[t])
+            if f_raw != 0:
+                lf = f32(last_factor[t])
+                f = min(max(f_raw, fmin), fmax)
+                f = min(max(f, lf * lo_k), lf * hi_k)
+                r = r * f
+                factors[t] = float(f)
+        ratios[t] = float(r)
+        u = over(m, bc1) / (root(over(v, bc2w)) + float(epsf))
+        if wd != 0:
+            u = u + p * float(wdf)
+        param[sl] = torch.where(live, p - u * float(f32(lr) * r), p)
+    return ratios, factors
 
 
 def sign_reduce_encode(recv: torch.Tensor, plan: BucketPlan, layout: Layout, inv_n: float,

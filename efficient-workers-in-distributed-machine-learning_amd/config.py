@@ -101,10 +101,11 @@ class Config:
     sync_bn: bool = False  # broadcast BN running stats from rank 0 at every checkpoint/eval
     # ---- optimizer -------------------------------------------------------------------------------
     # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
+    # onebit_lamb (1-bit LAMB) |
     # lion: optim/flat.py
     optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / onebit_adam
-    # onebit_adam: dense Adam steps before the variance is frozen and the sign-compressed
+    # onebit_adam / onebit_lamb: dense steps before the variance is frozen and the sign-compressed
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
     lars_eta: Optional[float] = None  # lars: trust coefficient (None: 0.001)
@@ -269,6 +270,34 @@ class Config:
                                  and c.topology == "allgather")
                                 or (c.compress == "sign" and c.topology == "twostage")
                                 or c.compress == "powersgd")
+        if c.optimizer == "onebit_lamb":
+            # 1-bit LAMB's compressed stage is the sign codec's all-gather with its residual, as
+            # 1-bit Adam's; refused ahead of the exchanges' own checks so the reason names it
+            why = None
+            if c.onebit_warmup_steps is None or int(c.onebit_warmup_steps) < 1:
+                why = "needs --onebit-warmup-steps N >= 1 (the dense LAMB steps before the freeze)"
+            elif c.compress != "sign":
+                why = "exchanges sign-compressed momentum: it needs --compress sign"
+            elif c.topology == "twostage":
+                why = ("runs the all-gather exchange: --topology twostage (the natural next "
+                       "step, as for 1-bit Adam) is not built yet")
+            elif c.topology != "allgather":
+                why = (f"keeps its residual in the all-gather exchange: it does not run with "
+                       f"--topology {c.topology}")
+            elif c.sync_every > 1:
+                why = "exchanges its momentum every step: it does not run with --sync-every > 1"
+            elif c.select_best:
+                why = "averages all workers' momenta: it does not run with --select-best"
+            elif not c.error_feedback:
+                why = ("compresses the error-compensated momentum: it does not run with "
+                       "--no-error-feedback")
+            elif c.predivide != 1.0:
+                why = ("averages decoded momenta with 1/N: it does not run with --predivide "
+                       "other than 1")
+            elif c.lars_eta is not None:
+                why = "takes LAMB's trust ratios, which have no eta: --lars-eta belongs to lars"
+            if why is not None:
+                raise ValueError("--optimizer onebit_lamb " + why)
         if c.topology == "twostage":
             # the two-stage sign all-reduce (parallel/twostage.py): both of its quantisations
             # are error-compensated, and the owners average with 1/N
@@ -344,8 +373,9 @@ class Config:
                        "other than 1")
             if why is not None:
                 raise ValueError("--optimizer onebit_adam " + why)
-        elif c.onebit_warmup_steps is not None:
-            raise ValueError("--onebit-warmup-steps belongs to --optimizer onebit_adam")
+        elif c.onebit_warmup_steps is not None and c.optimizer != "onebit_lamb":
+            raise ValueError("--onebit-warmup-steps belongs to --optimizer onebit_adam / "
+                             "onebit_lamb")
         if c.optimizer == "lars":
             if c.lars_eta is None:
                 c.lars_eta = 0.001
@@ -465,7 +495,8 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
-      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb", "lion"])
+      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb", "lion",
+               "onebit_lamb"])
     a("--lion-betas", type=str, default=None)
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)

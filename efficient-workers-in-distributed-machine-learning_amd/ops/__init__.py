@@ -584,6 +584,70 @@ def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_s
                          key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, sp, end)
 
 
+class OnebitLambTables:
+    """Per-tensor device state of one bucket for 1-bit LAMB's receive side, in the order of the
+    bucket's tensor table: ``adapt`` (int32 [T]), ``r_frozen`` / ``ratio`` (fp32 [T]),
+    ``last_factor`` (fp32 [2, T], possibly two column ranges of a wider table: a step reads the row
+    of the previous step's parity and writes its own) and ``partials`` (fp32, one per chunk
+    row)."""
+
+    def __init__(self, dp, adapt, r_frozen, last_factor, ratio, partials):
+        T, C = dp.plan.num_tensors, dp.plan.num_chunks
+        _check(adapt, torch.int32, "adapt", align=4)
+        for t, nm in ((r_frozen, "r_frozen"), (ratio, "ratio"), (partials, "partials")):
+            _check(t, torch.float32, nm, align=4)
+        _check(last_factor[0], torch.float32, "last_factor", align=4)
+        if (adapt.numel() != T or r_frozen.numel() != T or ratio.numel() != T
+                or tuple(last_factor.shape) != (2, T) or last_factor.stride(0) < T
+                or partials.numel() != C):
+            raise ValueError(f"1-bit LAMB tables of {T} tensors / {C} chunks: adapt, r_frozen and "
+                             f"ratio hold {T} entries, last_factor [2, {T}], partials {C}")
+        if any(o % 4 for o in dp.plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        self.dp = dp
+        self.adapt, self.r_frozen, self.last_factor = adapt, r_frozen, last_factor
+        self.ratio, self.partials = ratio, partials
+
+
+def onebit_lamb_step(lt: OnebitLambTables, recv, layout, param, exp_avg, exp_avg_sq,
+                     exp_avg_sq_fresh, inv_n, *, lr, betas=(0.9, 0.999), eps=1e-8,
+                     weight_decay=0.0, t, freeze_step, factor_min=0.5, factor_max=4.0,
+                     factor_threshold=0.1, bc1=None, step=None, lr_tensor=None, shadow=None,
+                     key_state=None, key_seed=0, key_rank=0):
+    """1-bit LAMB's receive side of one bucket in two launches (``csrc/sign_codec.hip``; bitwise
+    ``compress/oracle.py onebit_lamb_apply``): ``k_sign_decode_lamb_stage`` (``exp_avg`` = the
+    mean of the decoded momenta, ``exp_avg_sq_fresh``, per-chunk ``max q``) and
+    ``k_lamb_onebit_apply`` (per tensor the factor and ``r = r_frozen * f`` -> ``lt.ratio``, the
+    new ``lt.last_factor`` row, the step where ``exp_avg_sq > 0``, the bf16 shadow).  ``t`` is the
+    1-based step (``> freeze_step``) and ``bc1`` its ``1 - beta1^t``; ``step`` (int32 device
+    tensor, optional): the kernels read ``t = step + 1`` and derive ``bc1`` on the device."""
+    C = require()
+    dp = lt.dp
+    nranks, stride, so, bo, _, _ = _sign_recv(dp, recv, layout, None)
+    for x, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"),
+                  (exp_avg_sq_fresh, "exp_avg_sq_fresh")):
+        if x is None:
+            raise ValueError(f"the 1-bit LAMB step needs {nm}")
+        _check_bucket(dp, x, nm)
+    if int(freeze_step) < 1 or (step is None and int(t) <= int(freeze_step)):
+        raise ValueError("the compressed stage starts after freeze_step >= 1")
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    _check_shadow(dp, shadow)
+    b1, b2 = betas
+    args = (_ptr(recv), nranks, stride, _ptr(dp.chunks), dp.plan.num_chunks, _ptr(dp.tensors),
+            dp.plan.num_tensors, so, bo, _ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq),
+            _ptr(exp_avg_sq_fresh), _ptr(shadow), _ptr(lt.adapt), _ptr(lt.partials),
+            _ptr(lt.r_frozen), _ptr(lt.last_factor), lt.last_factor.stride(0), _ptr(lt.ratio), float(lr), float(inv_n),
+            float(b1), float(b2), float(eps), float(weight_decay),
+            float(1.0 - b1 ** t if bc1 is None else bc1), 1.0 - b2 ** int(freeze_step),
+            float(factor_min), float(factor_max), float(factor_threshold), int(t),
+            int(freeze_step), _ptr(step), _lrp(lr_tensor), _stream(), _keyp(key_state),
+            key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF)
+    C.onebit_lamb(0, *args)
+    C.onebit_lamb(1, *args)
+
+
 class LowRankTables:
     """Device tables, slabs and arrival counters of one bucket of PowerSGD (``compress/plan.py
     LowRankPlan``).  The kernels trust the tables, so the host copy is checked here: every

@@ -317,6 +317,60 @@ PYBIND11_MODULE(_C, m) {
           ew_sign_decode_onebit(a);
         });
 
+  m.def("onebit_lamb",
+        [](int op, uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C,
+           uintptr_t tensors, int T, int scales_off, int bits_off, uintptr_t param,
+           uintptr_t exp_avg, uintptr_t exp_avg_sq, uintptr_t exp_avg_sq_fresh, uintptr_t shadow,
+           uintptr_t adapt, uintptr_t partials, uintptr_t r_frozen, uintptr_t last_factor,
+           int lf_stride, uintptr_t ratio, float lr, float inv_n, double beta1, double beta2, float eps,
+           float weight_decay, float bc1, float bc2w, float factor_min, float factor_max,
+           float factor_threshold, int t, int freeze_step, uintptr_t step, uintptr_t lr_ptr,
+           uintptr_t stream, uintptr_t key_state, uint32_t key_seed, uint32_t key_rank) {
+          SignLambArgs a{};
+          a.recv = recv;
+          a.nranks = nranks;
+          a.stride = stride;
+          a.chunks = chunks;
+          a.num_chunks = C;
+          a.tensors = tensors;
+          a.num_tensors = T;
+          a.scales_off = scales_off;
+          a.bits_off = bits_off;
+          a.param = param;
+          a.exp_avg = exp_avg;
+          a.exp_avg_sq = exp_avg_sq;
+          a.exp_avg_sq_fresh = exp_avg_sq_fresh;
+          a.shadow = shadow;
+          a.adapt = adapt;
+          a.partials = partials;
+          a.r_frozen = r_frozen;
+          a.last_factor = last_factor;
+          a.lf_stride = lf_stride;
+          a.ratio = ratio;
+          a.lr = lr;
+          a.inv_n = inv_n;
+          a.beta1 = beta1;
+          a.beta2 = beta2;
+          a.eps = eps;
+          a.weight_decay = weight_decay;
+          a.bc1 = bc1;
+          a.bc2w = bc2w;
+          a.factor_min = factor_min;
+          a.factor_max = factor_max;
+          a.factor_threshold = factor_threshold;
+          a.t = t;
+          a.freeze_step = freeze_step;
+          a.step = step;
+          a.lr_ptr = lr_ptr;
+          a.stream = stream;
+          a.key_state = key_state;
+          a.key_seed = key_seed;
+          a.key_rank = key_rank;
+          if (op == 0) ew_sign_decode_lamb_stage(a);
+          else if (op == 1) ew_lamb_onebit_apply(a);
+          else throw std::runtime_error("ewdml 1-bit LAMB: unknown op");
+        });
+
   m.def("sign_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
            int bits_off, uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,

@@ -139,6 +139,29 @@ struct SignOnebitArgs {
   long long slot_end;  // nranks must be 1
 };
 
+// 1-bit LAMB's receive side (sign_codec.hip k_sign_decode_lamb_stage / k_lamb_onebit_apply): both
+// launches take the same arguments.  tensors / adapt / r_frozen / ratio hold num_tensors entries
+// in the order of the bucket's tensor table, last_factor two such rows lf_stride entries apart
+// (indexed by the step's parity), partials one fp32 per chunk row.
+struct SignLambArgs {
+  uintptr_t recv, chunks, tensors, stream;
+  uintptr_t param, exp_avg, exp_avg_sq, exp_avg_sq_fresh, shadow;  // exp_avg_sq is read only
+  uintptr_t adapt, partials, r_frozen, last_factor, ratio;
+  long long stride;
+  int nranks, num_chunks, num_tensors, lf_stride;
+  int scales_off, bits_off;
+  double beta1, beta2;
+  float lr, inv_n, eps, weight_decay;
+  float bc1;   // 1 - beta1^t of the host's t (derived on the device when step is set)
+  float bc2w;  // 1 - beta2^freeze_step
+  float factor_min, factor_max, factor_threshold;
+  int t, freeze_step;  // the host's 1-based step (replaced by *step + 1 when step is set)
+  uintptr_t step;      // nullable int32 device step counter
+  uintptr_t lr_ptr;    // nullable device fp32 lr (overrides lr)
+  uintptr_t key_state;  // see TopkDecodeArgs; advanced by the apply launch
+  uint32_t key_seed, key_rank;
+};
+
 struct SignDecodeArgs {
   uintptr_t recv, chunks, param, mom, grad_out, shadow, stream;  // mom 0: a step without momentum
   long long stride;
@@ -312,6 +335,8 @@ void ew_qsgd_decode_apply(const QsgdDecodeArgs& a);
 void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
+void ew_sign_decode_lamb_stage(const SignLambArgs& a);
+void ew_lamb_onebit_apply(const SignLambArgs& a);
 void ew_sign_reduce_encode(const SignReduceArgs& a);
 
 void ew_psgd_project(const PsgdArgs& a);

@@ -17,7 +17,9 @@
 // 1-bit Adam's compressed stage (Tang et al. 2021; optim/flat.py FlatOnebitAdam) reuses both sides:
 // k_sign_encode<true, true> forms the momentum candidate in front of the same encode, and
 // k_sign_decode_onebit writes the averaged momentum and takes the frozen-variance step
-// (compress/oracle.py encode_sign_momentum / onebit_adam_apply, bit for bit).
+// (compress/oracle.py encode_sign_momentum / onebit_adam_apply, bit for bit).  1-bit LAMB (Li et
+// al. 2021; FlatOnebitLamb) takes the same encode with weight decay 0 and a two-launch receive
+// side, k_sign_decode_lamb_stage / k_lamb_onebit_apply (onebit_lamb_apply, bit for bit).
 //
 // The two-stage sign all-reduce (parallel/twostage.py) adds a slot-addressed form of all three:
 // `slots` (nullable int2 per chunk) holds the byte offsets of the chunk's scale and of its 256
@@ -329,6 +331,196 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_onebit(
   }
 }
 
+// 1-bit LAMB's receive side (Li et al. 2021; optim/flat.py FlatOnebitLamb; compress/oracle.py
+// onebit_lamb_apply, bit for bit): two launches per bucket, one block per chunk row.
+//
+//   k_sign_decode_lamb_stage  m = mean of the decoded momenta, the gradient it implies
+//                             g = (m - m_old * beta1) / (1 - beta1), the fresh variance
+//                             vf = vf * beta2 + (1 - beta2) * g * g; stores m and vf and, per
+//                             chunk, max q with q = (sqrtf(v) + eps) / (sqrtf(vf) + eps) over the
+//                             coordinates whose frozen v > 0;
+//   k_lamb_onebit_apply       every block takes the maximum over its tensor's chunk partials (all
+//                             blocks of a tensor compute the same factor and ratio: no grid
+//                             barrier, no float atomic, no finalize launch), then
+//                             p -= lr * r * u where v > 0; the tensor's first block stores r and
+//                             the new last_factor.
+//
+// last_factor holds two rows, lf_stride entries apart.  Step t (1-based) reads row (t - 1) & 1 and
+// writes row t & 1, and writes every tensor's entry (the old value where the factor stays): other
+// blocks of the same launch read the row that no block of that launch writes.
+struct LambOnebitArgs {
+  float* param;
+  float* mom;        // exp_avg
+  const float* var;  // the frozen exp_avg_sq: read only
+  float* varf;       // exp_avg_sq_fresh
+  uint16_t* shadow;
+  const TensorRow* tensors;
+  const int* adapt;
+  float* partials;  // one fp32 per chunk row: the chunk's max q
+  const float* r_frozen;
+  float* last_factor;  // two rows, lf_stride apart
+  float* ratio;
+  const int* step;      // nullable device step counter: t = *step + 1
+  const float* lr_ptr;  // nullable device lr
+  double beta1d;
+  float lr, inv_n, beta1, beta2, omb1, omb2, eps, weight_decay;
+  float bc1;   // 1 - beta1^t (host value, replaced when step is set)
+  float bc2w;  // 1 - beta2^freeze_step
+  float factor_min, factor_max, factor_threshold;
+  int t, lf_stride;
+};
+
+// lr, t and bc1(t) read once per block from device memory (layerwise.hip lw_resolve)
+__device__ __forceinline__ void ew_lamb1_resolve(LambOnebitArgs& a) {
+  if (a.lr_ptr) a.lr = *a.lr_ptr;
+  if (a.step) {
+    const int s = *a.step;
+    a.t = s + 1;
+    a.bc1 = (float)(1.0 - pow(a.beta1d, (double)(s + 1)));
+  }
+}
+
+__device__ __forceinline__ float ew_wave_fmax(float v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_down(v, d, 64));
+  return v;  // valid in lane 0
+}
+
+// Block maximum (fmaxf: a NaN never enters, the start is the caller's 0); valid in thread 0
+__device__ __forceinline__ float ew_block_fmax(float v, float* ws) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  v = ew_wave_fmax(v);
+  if (lane == 0) ws[w] = v;
+  __syncthreads();
+  float s = 0.0f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < EW_WAVES; ++i) s = fmaxf(s, ws[i]);
+  }
+  return s;
+}
+
+// one element of the stage pass: vf is updated, q joins the thread's maximum where v > 0
+__device__ __forceinline__ void ew_lamb1_stage(float m, float m_old, float v, float& vf,
+                                               float& qmax, const LambOnebitArgs& a) {
+  const float g = (m - m_old * a.beta1) / a.omb1;
+  vf = vf * a.beta2 + a.omb2 * (g * g);
+  if (v > 0.0f) qmax = fmaxf(qmax, (sqrtf(v) + a.eps) / (sqrtf(vf) + a.eps));
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_lamb_stage(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, LambOnebitArgs a) {
+  __shared__ float ws[EW_WAVES];
+  const ChunkRow c = chunks[blockIdx.x];
+  size_t scale_at, words_at;
+  ew_sign_where(nullptr, scales_off, bits_off, scale_at, words_at);
+  float acc[EW_CU][4];
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
+  float* b = a.mom + c.start;
+  float* vf = a.varf + c.start;
+  const float* vq = a.var + c.start;
+  float qmax = 0.0f;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const int i = ew_chunk_idx(u);
+    if (i >= c.len) continue;
+    float mv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mv[j] = acc[u][j] * a.inv_n;
+    if (i + 3 < c.len) {
+      const float4 o4 = *reinterpret_cast<const float4*>(b + i);
+      const float4 v4 = *reinterpret_cast<const float4*>(vq + i);
+      const float4 f4 = *reinterpret_cast<const float4*>(vf + i);
+      const float ov[4] = {o4.x, o4.y, o4.z, o4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+      float fv[4] = {f4.x, f4.y, f4.z, f4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ew_lamb1_stage(mv[j], ov[j], vv[j], fv[j], qmax, a);
+      *reinterpret_cast<float4*>(b + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      *reinterpret_cast<float4*>(vf + i) = make_float4(fv[0], fv[1], fv[2], fv[3]);
+    } else {  // the last elements of a tensor
+      for (int j = 0; j < 4 && i + j < c.len; ++j) {
+        float fv = vf[i + j];
+        ew_lamb1_stage(mv[j], b[i + j], vq[i + j], fv, qmax, a);
+        b[i + j] = mv[j];
+        vf[i + j] = fv;
+      }
+    }
+  }
+  const float cmax = ew_block_fmax(qmax, ws);
+  if (threadIdx.x == 0) a.partials[blockIdx.x] = cmax;
+}
+
+// LAMB's update direction with the variance's bias correction held at the freeze step
+__device__ __forceinline__ void ew_lamb1_step(float& p, float m, float v, float step,
+                                              const LambOnebitArgs& a) {
+  if (v > 0.0f) {
+    float u = (m / a.bc1) / (sqrtf(v / a.bc2w) + a.eps);
+    if (a.weight_decay != 0.0f) u = u + a.weight_decay * p;
+    p = p - step * u;
+  }
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void k_lamb_onebit_apply(
+    const ChunkRow* __restrict__ chunks, LambOnebitArgs a, SgdArgs key) {
+  __shared__ float ws[EW_WAVES];
+  __shared__ float rs;
+  ew_lamb1_resolve(a);
+  ew_key_advance(key);
+  const ChunkRow c = chunks[blockIdx.x];
+  const TensorRow T = a.tensors[c.tensor];
+  float fm = 0.0f;
+  for (int j = threadIdx.x; j < T.nchunks; j += EW_BLOCK) fm = fmaxf(fm, a.partials[T.chunk0 + j]);
+  const float f_raw = ew_block_fmax(fm, ws);
+  if (threadIdx.x == 0) {
+    const float lf = a.last_factor[((a.t - 1) & 1) * a.lf_stride + c.tensor];
+    float r = 1.0f, f_new = lf;
+    if (a.adapt[c.tensor]) {
+      r = a.r_frozen[c.tensor];
+      if (f_raw != 0.0f) {
+        float f = fminf(fmaxf(f_raw, a.factor_min), a.factor_max);
+        f = fminf(fmaxf(f, lf * (1.0f - a.factor_threshold)), lf * (1.0f + a.factor_threshold));
+        r = r * f;
+        f_new = f;
+      }
+    }
+    rs = r;
+    if (c.local == 0) {
+      a.ratio[c.tensor] = r;
+      a.last_factor[(a.t & 1) * a.lf_stride + c.tensor] = f_new;
+    }
+  }
+  __syncthreads();
+  const float step = a.lr * rs;
+  float* p = a.param + c.start;
+  const float* b = a.mom + c.start;
+  const float* vq = a.var + c.start;
+  uint16_t* sh = a.shadow ? a.shadow + c.start : nullptr;
+#pragma unroll 2
+  for (int u = 0; u < EW_CU; ++u) {
+    const int i = ew_chunk_idx(u);
+    if (i >= c.len) break;
+    if (i + 3 < c.len) {
+      const float4 p4 = *reinterpret_cast<const float4*>(p + i);
+      const float4 m4 = *reinterpret_cast<const float4*>(b + i);
+      const float4 v4 = *reinterpret_cast<const float4*>(vq + i);
+      float pv[4] = {p4.x, p4.y, p4.z, p4.w};
+      const float mv[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ew_lamb1_step(pv[j], mv[j], vv[j], step, a);
+      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+      if (sh) ew_st4_bf16(sh + i, 4, pv);
+    } else {  // the last elements of a tensor
+      for (int j = 0; j < 4 && i + j < c.len; ++j) {
+        float pv = p[i + j];
+        ew_lamb1_step(pv, b[i + j], vq[i + j], step, a);
+        p[i + j] = pv;
+        if (sh) sh[i + j] = ew_f2bf(pv);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 #define EW_LAUNCH(kern, grid, stream, ...) \
@@ -412,6 +604,69 @@ void ew_sign_decode_onebit(const SignOnebitArgs& a) {
             reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.exp_avg),
             reinterpret_cast<const float*>(a.exp_avg_sq), reinterpret_cast<uint16_t*>(a.shadow),
             oa, key, reinterpret_cast<const int2*>(a.slots));
+  EW_CHECK_LAUNCH();
+}
+
+static LambOnebitArgs ew_lamb1_args(const SignLambArgs& h) {
+  if (h.num_chunks <= 0 || h.num_tensors <= 0 || h.lf_stride < h.num_tensors)
+    throw std::runtime_error("ewdml 1-bit LAMB: nothing to step");
+  if (!h.chunks || !h.tensors || !h.adapt || !h.partials || !h.r_frozen || !h.last_factor ||
+      !h.ratio)
+    throw std::runtime_error("ewdml 1-bit LAMB: missing table");
+  if (!h.param || !h.exp_avg || !h.exp_avg_sq || !h.exp_avg_sq_fresh)
+    throw std::runtime_error("ewdml 1-bit LAMB: the step needs param, exp_avg, exp_avg_sq and "
+                             "exp_avg_sq_fresh");
+  if ((h.param | h.exp_avg | h.exp_avg_sq | h.exp_avg_sq_fresh) % 16 || h.shadow % 8 ||
+      (h.partials | h.r_frozen | h.last_factor | h.ratio | h.adapt | h.step | h.lr_ptr) % 4)
+    throw std::runtime_error("ewdml 1-bit LAMB: misaligned operand");
+  if (h.freeze_step < 1 || (!h.step && h.t <= h.freeze_step))
+    throw std::runtime_error("ewdml 1-bit LAMB: the compressed stage starts after freeze_step >= 1");
+  LambOnebitArgs a{};
+  a.param = reinterpret_cast<float*>(h.param);
+  a.mom = reinterpret_cast<float*>(h.exp_avg);
+  a.var = reinterpret_cast<const float*>(h.exp_avg_sq);
+  a.varf = reinterpret_cast<float*>(h.exp_avg_sq_fresh);
+  a.shadow = reinterpret_cast<uint16_t*>(h.shadow);
+  a.tensors = reinterpret_cast<const TensorRow*>(h.tensors);
+  a.adapt = reinterpret_cast<const int*>(h.adapt);
+  a.partials = reinterpret_cast<float*>(h.partials);
+  a.r_frozen = reinterpret_cast<const float*>(h.r_frozen);
+  a.last_factor = reinterpret_cast<float*>(h.last_factor);
+  a.ratio = reinterpret_cast<float*>(h.ratio);
+  a.step = reinterpret_cast<const int*>(h.step);
+  a.lr_ptr = reinterpret_cast<const float*>(h.lr_ptr);
+  a.beta1d = h.beta1;
+  a.lr = h.lr; a.inv_n = h.inv_n; a.eps = h.eps; a.weight_decay = h.weight_decay;
+  a.beta1 = (float)h.beta1; a.beta2 = (float)h.beta2;
+  a.omb1 = 1.0f - a.beta1; a.omb2 = 1.0f - a.beta2;  // formed in fp32, as the momentum encode's
+  a.bc1 = h.bc1;
+  a.bc2w = h.bc2w;
+  a.factor_min = h.factor_min; a.factor_max = h.factor_max;
+  a.factor_threshold = h.factor_threshold;
+  a.t = h.t; a.lf_stride = h.lf_stride;
+  return a;
+}
+
+void ew_sign_decode_lamb_stage(const SignLambArgs& h) {
+  if (h.nranks <= 0) throw std::runtime_error("ewdml 1-bit LAMB: nothing to decode");
+  if (!h.recv || h.recv % 16 || h.stride % 16)
+    throw std::runtime_error("ewdml 1-bit LAMB: the received rows must be 16-byte aligned");
+  ew_sign_fit("ewdml 1-bit LAMB", 0, 0, h.scales_off, h.bits_off, h.num_chunks, h.stride);
+  const LambOnebitArgs a = ew_lamb1_args(h);
+  EW_LAUNCH(k_sign_decode_lamb_stage, h.num_chunks, h.stream,
+            reinterpret_cast<const uint8_t*>(h.recv), h.nranks, h.stride,
+            reinterpret_cast<const ChunkRow*>(h.chunks), h.scales_off, h.bits_off, a);
+  EW_CHECK_LAUNCH();
+}
+
+void ew_lamb_onebit_apply(const SignLambArgs& h) {
+  const LambOnebitArgs a = ew_lamb1_args(h);
+  SgdArgs key{};
+  key.key_state = reinterpret_cast<uint32_t*>(h.key_state);
+  key.key_seed = h.key_seed;
+  key.key_rank = h.key_rank;
+  EW_LAUNCH(k_lamb_onebit_apply, h.num_chunks, h.stream,
+            reinterpret_cast<const ChunkRow*>(h.chunks), a, key);
   EW_CHECK_LAUNCH();
 }
 

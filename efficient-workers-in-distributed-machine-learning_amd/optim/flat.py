@@ -477,8 +477,123 @@ class FlatLAMB(_Layerwise):
         self._load_common(sd)
 
 
+class FlatOnebitLamb(FlatLAMB):
+    """1-bit LAMB (Li et al., 2021; DeepSpeed ``OnebitLamb``).  Steps 1..``freeze_step`` are
+    :class:`FlatLAMB` on the dense averaged gradient; :meth:`end_step` also keeps per tensor
+    ``coeff_ema = coeff_beta * coeff_ema + (1 - coeff_beta) * ratio``.  From then on (``frozen``)
+    ``exp_avg_sq`` is never written again and the exchange, not :meth:`step_range`, runs the
+    step (``Codec.encode_momentum`` with weight decay 0 / ``decode_apply_onebit_lamb``,
+    ``compress/oracle.py onebit_lamb_apply``): the decode writes the averaged momentum into
+    ``exp_avg``, moves ``exp_avg_sq_fresh`` with the gradient the momentum implies, and steps with
+    ``ratio = r_frozen * factor``, the factor following ``max (sqrt(v) + eps) / (sqrt(v_fresh) +
+    eps)`` inside ``[factor_min, factor_max]`` and within ``factor_threshold`` of the last one.
+
+    The freeze (``exp_avg_sq_fresh = exp_avg_sq``, ``r_frozen = coeff_ema / (1 - coeff_beta^
+    freeze_step)``, ``last_factor = 1``) is written at the end of *every* warm-up step, with
+    stream-ordered copies and no branch on the step count: a captured warm-up step replays it,
+    and what step ``freeze_step`` leaves is the freeze.  ``last_factor`` is kept as two rows: step
+    ``t`` reads row ``(t - 1) & 1`` and writes row ``t & 1``.  The state is the same on every
+    rank; the error-feedback residual lives in the exchange."""
+    onebit = True
+    onebit_kind = "lamb"
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 freeze_step=None, coeff_beta=0.9, factor_min=0.5, factor_max=4.0,
+                 factor_threshold=0.1):
+        if freeze_step is None or int(freeze_step) < 1:
+            raise ValueError("1-bit LAMB needs freeze_step >= 1 (the dense warm-up's length)")
+        if not (0.0 <= coeff_beta < 1.0 and 0.0 < factor_min <= 1.0 <= factor_max
+                and 0.0 <= factor_threshold < 1.0):
+            raise ValueError("1-bit LAMB needs coeff_beta in [0, 1), factor_min <= 1 <= "
+                             "factor_max and factor_threshold in [0, 1)")
+        super().__init__(flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.freeze_step = int(freeze_step)
+        self.coeff_beta = float(coeff_beta)
+        self.factor_min, self.factor_max = float(factor_min), float(factor_max)
+        self.factor_threshold = float(factor_threshold)
+        self.exp_avg_sq_fresh = torch.zeros_like(flat.data)
+        self.coeff_ema = torch.zeros_like(self.ratio)
+        self.r_frozen = torch.zeros_like(self.ratio)
+        self._factors = torch.ones(2, self.ratio.numel(), dtype=torch.float32,
+                                   device=self.ratio.device)
+        self._tables = {}
+
+    @property
+    def frozen(self) -> bool:
+        """The next step is a compressed-stage step."""
+        return self.steps >= self.freeze_step
+
+    @property
+    def last_factor(self) -> torch.Tensor:
+        """The factors the last step left (the row of its parity)."""
+        return self._factors[self.steps & 1]
+
+    def hparams(self, start=None, length=None) -> dict:
+        """The decode's arguments; with a bucket's range also its per-tensor state: the
+        ``(offset, numel, adapts)`` rows, views of ``r_frozen`` / ``ratio`` / the two factor rows,
+        and (GPU) ``tables(dp)``, the device tables over the codec's decode plan."""
+        hp = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                  freeze_step=self.freeze_step, t=self.steps + 1, factor_min=self.factor_min,
+                  factor_max=self.factor_max, factor_threshold=self.factor_threshold,
+                  step_t=self.step_t, lr_t=self.lr_t)
+        if start is not None:
+            t0, tensors = self._tensors(start, length)
+            sl = slice(t0, t0 + len(tensors))
+            hp.update(tensors=tensors, r_frozen=self.r_frozen[sl], ratio=self.ratio[sl],
+                      factors=self._factors[:, sl],
+                      tables=lambda dp: self._bucket_tables(dp, start, length))
+        return hp
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        if self.frozen:
+            raise RuntimeError("1-bit LAMB is past its freeze step: the sign exchange runs the "
+                               "step (a dense step would write exp_avg_sq)")
+        super().step_range(start, length, grad, grad_scale)
+
+    def _bucket_tables(self, dp, start, length):
+        lt = self._tables.get((start, length))
+        if lt is None:
+            t0, nt = self._range(start, length)
+            c0 = self._chunk0[t0]
+            lt = ops.OnebitLambTables(dp, self._adapt_t[t0:t0 + nt], self.r_frozen[t0:t0 + nt],
+                                      self._factors[:, t0:t0 + nt], self.ratio[t0:t0 + nt],
+                                      self._partials[c0:c0 + dp.plan.num_chunks])
+            self._tables[(start, length)] = lt
+        return lt
+
+    def end_step(self):
+        if not self.frozen:  # a warm-up step just ran: self.ratio holds its trust ratios
+            self.coeff_ema.mul_(self.coeff_beta).add_(self.ratio * (1.0 - self.coeff_beta))
+            torch.div(self.coeff_ema, 1.0 - self.coeff_beta ** self.freeze_step,
+                      out=self.r_frozen)
+            self.exp_avg_sq_fresh.copy_(self.exp_avg_sq)
+        super().end_step()
+
+    def state_dict(self):
+        return dict(super().state_dict(), kind="onebit_lamb", freeze_step=self.freeze_step,
+                    exp_avg_sq_fresh=self.exp_avg_sq_fresh, coeff_ema=self.coeff_ema,
+                    r_frozen=self.r_frozen, last_factor=self._factors,
+                    coeff_beta=self.coeff_beta, factor_min=self.factor_min,
+                    factor_max=self.factor_max, factor_threshold=self.factor_threshold)
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self.exp_avg_sq_fresh.copy_(sd["exp_avg_sq_fresh"])
+        self.coeff_ema.copy_(sd["coeff_ema"])
+        self.r_frozen.copy_(sd["r_frozen"])
+        self._factors.copy_(sd["last_factor"])
+        self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
+        for k in ("coeff_beta", "factor_min", "factor_max", "factor_threshold"):
+            if k in sd:
+                setattr(self, k, float(sd[k]))
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "onebit_lamb":
+        return FlatOnebitLamb(flat, lr=kw.get("lr", 1e-3),
+                              weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),
+                              freeze_step=kw.get("freeze_step"))
     if name == "lars":
         return FlatLARS(flat, eta=kw.get("eta", 0.001),
                         **{k: v for k, v in kw.items()

@@ -107,9 +107,12 @@ class GradientExchange:
         # the frozen-variance step.  The optimizer's dense warm-up runs through an all-reduce
         # exchange of its own (runtime/trainer.py switches between the two)
         self.onebit = bool(getattr(optimizer, "onebit", False)) and not codec.allreduce
+        # 1-bit LAMB (FlatOnebitLamb): the same encode with weight decay 0 (LAMB's is decoupled
+        # and enters on the receiver) and the two-launch trust-ratio decode
+        self.onebit_lamb = self.onebit and getattr(optimizer, "onebit_kind", "adam") == "lamb"
         if self.onebit and (codec.kind != "sign" or self.resid is None or predivide != 1.0):
-            raise ValueError("1-bit Adam's compressed stage needs the sign codec with error "
-                             "feedback and predivide 1")
+            raise ValueError("1-bit Adam's and 1-bit LAMB's compressed stage needs the sign codec "
+                             "with error feedback and predivide 1")
         # Distributed Lion (optim/flat.py FlatLion under the vote codec): the encode sends the sign
         # of this rank's own update direction and moves this rank's own momentum, the apply
         # counts the votes and steps.  No residual, no velocity; opt.exp_avg is per-rank state
@@ -369,7 +372,8 @@ class GradientExchange:
             o = self.opt
             self.codec.encode_momentum(bi, g, self.payload[bi], resid,
                                        o.exp_avg[b.start:b.start + b.length], o.betas[0],
-                                       o.weight_decay, self.flat.data_view(b))
+                                       0.0 if self.onebit_lamb else o.weight_decay,
+                                       self.flat.data_view(b))
             return
         dgc = None
         if self.dgc:
@@ -499,6 +503,14 @@ class GradientExchange:
                                                  opt.hparams(), shadow=self.flat.shadow_view(b),
                                                  key_state=self.key_state if adv else None,
                                                  rank=self.comm.rank)
+                elif self.onebit_lamb:  # ... and the fresh variance, the factor, r_frozen * f
+                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
+                    sl = slice(b.start, b.start + b.length)
+                    self.codec.decode_apply_onebit_lamb(
+                        b.index, recv, scale, self.flat.data_view(b), opt.exp_avg[sl],
+                        opt.exp_avg_sq[sl], opt.exp_avg_sq_fresh[sl],
+                        opt.hparams(b.start, b.length), shadow=self.flat.shadow_view(b),
+                        key_state=self.key_state if adv else None, rank=self.comm.rank)
                 elif self.onebit:  # exp_avg = mean of the decoded momenta; frozen-variance step
                     adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     sl = slice(b.start, b.start + b.length)

@@ -260,12 +260,12 @@ class Trainer:
             self.exchange = TwoStageSignExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt,
                                                  clipper=self.clipper)
-        elif cfg.optimizer == "onebit_adam":
-            # 1-bit Adam: two exchanges over the same flat model and optimizer -- the dense fp32
-            # all-reduce of the warm-up (steps 1..T_w: FlatAdam's step) and the sign exchange of
-            # the compressed stage (momentum encode, fused decode + frozen-variance step).  An
-            # exchange's hooks are inert unless its begin() ran; _select_stage picks the one of
-            # the next step
+        elif cfg.optimizer in ("onebit_adam", "onebit_lamb"):
+            # 1-bit Adam / 1-bit LAMB: two exchanges over the same flat model and optimizer -- the
+            # dense fp32 all-reduce of the warm-up (steps 1..T_w: FlatAdam's / FlatLAMB's step)
+            # and the sign exchange of the compressed stage (momentum encode, fused decode +
+            # frozen-variance step).  An exchange's hooks are inert unless its begin() ran;
+            # _select_stage picks the one of the next step
             side = (self.cuda and not cfg.phase_timing
                     and (cfg.hip_graph == "off" or os.environ.get("EWDML_SIDE_STREAM") == "1"))
             self._stages = tuple(
