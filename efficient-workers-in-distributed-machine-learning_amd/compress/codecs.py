@@ -8,7 +8,9 @@
   * ``topk``  -- top-k sparsification, fp32 values (``TopKCompressor``)
   * ``topk_qsgd`` -- top-k then QSGD (Method 5); the flagship codec
   * ``sign``  -- scaled sign, 1 bit per element plus one fp32 scale per 8192-element chunk
-    (1-bit SGD / EF-signSGD); meant to run with error feedback, which the all-gather exchange keeps
+    (1-bit SGD / EF-signSGD); meant to run with error feedback, which the all-gather exchange keeps.
+    ``rotate="hadamard"`` (``codec.rotate``; DRIVE / EDEN): the signs are taken of a randomised
+    Hadamard rotation of every chunk, the same payload, one inverse transform on the receiver
   * ``vote``  -- Distributed Lion's 1-bit majority vote (Liu et al. 2024): one bit per element, the
     sign of the rank's own Lion update direction; no scale, no residual (``encode_vote`` /
     ``decode_apply_vote``; needs ``optim/flat.py FlatLion``)
@@ -34,12 +36,13 @@ from .rng import stream_key
 
 KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote")
 VOTE_AGGREGATES = ("majority", "average")
+SIGN_ROTATIONS = ("none", "hadamard")
 
 
 class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
-                 rank: int = 4, aggregate: str = "majority"):
+                 rank: int = 4, aggregate: str = "majority", rotate: str = "none"):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
@@ -50,6 +53,11 @@ class Codec:
         if aggregate != "majority" and kind != "vote":
             raise ValueError("the aggregate belongs to the vote codec")
         self.aggregate = aggregate
+        if rotate not in SIGN_ROTATIONS:
+            raise ValueError(f"sign rotation must be one of {SIGN_ROTATIONS}, not {rotate!r}")
+        if rotate != "none" and kind != "sign":
+            raise ValueError("the rotation belongs to the sign codec")
+        self.rotate = rotate
         # the sign, vote and low-rank codecs have neither bits nor levels
         if kind not in ("sign", "powersgd", "vote") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
@@ -85,7 +93,7 @@ class Codec:
         if self.kind == "topk":
             return f"topk{self.ratio:g}"
         if self.kind == "sign":
-            return "sign1b"
+            return "sign1b-h" if self.rotate == "hadamard" else "sign1b"
         if self.kind == "powersgd":
             return f"powersgd-r{self.rank}"
         if self.kind == "vote":
@@ -150,6 +158,16 @@ class Codec:
     def key(self, step: int, rank: int) -> int:
         return stream_key(self.seed, step, rank)
 
+    def rot_key(self, b: int):
+        """The rotated sign codec's key of bucket ``b`` (the same on every rank and every step);
+        None without a rotation."""
+        return oracle.hsign_rot_key(self.seed, b) if self.rotate == "hadamard" else None
+
+    def _unrotated(self, what: str):
+        if self.rotate != "none":
+            raise ValueError(f"{what} is not rotated: it does not run with rotate="
+                             f"{self.rotate!r}")
+
     # -- encode / decode ----------------------------------------------------------------------
     def encode(self, b: int, grad: torch.Tensor, payload: torch.Tensor, step: int, rank: int,
                resid: torch.Tensor = None, key_tensor: torch.Tensor = None, dgc: dict = None,
@@ -174,7 +192,8 @@ class Codec:
             if ef21:
                 raise NotImplementedError("EF21 encode on the GPU: run with EWDML_ORACLE=1")
             if self.kind == "sign":
-                ops.sign_encode(self.dplans[b], grad, payload, lay, resid)
+                ops.sign_encode(self.dplans[b], grad, payload, lay, resid,
+                                rot_key=self.rot_key(b))
             elif self.kind == "qsgd":
                 ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
                                 resid, key_tensor)
@@ -187,7 +206,7 @@ class Codec:
         if isinstance(grad, (list, tuple)):
             raise TypeError("CPU encode takes the bucket's flat gradient view")
         if self.kind == "sign":
-            out = oracle.encode_sign(grad, plan, lay, resid)
+            out = oracle.encode_sign(grad, plan, lay, resid, self.rot_key(b))
         elif self.kind == "qsgd":
             out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
         else:
@@ -203,6 +222,7 @@ class Codec:
         ``param`` are that bucket's views and are only read."""
         if self.kind != "sign":
             raise ValueError("the momentum encode needs the sign codec")
+        self._unrotated("the momentum encode")
         if resid is None:
             raise ValueError("the momentum encode needs the residual (error feedback)")
         plan, lay = self.plans[b], self.layouts[b]
@@ -262,6 +282,8 @@ class Codec:
         if self.kind not in ("sign", "vote"):
             raise ValueError("the two-stage exchange needs the sign codec (or, for the two-stage "
                              "vote, the vote codec)")
+        self._unrotated("the two-stage exchange (its owner re-encode would need a transform pair "
+                        "of its own)")
         if self.kind == "vote" and self.aggregate != "majority":
             raise ValueError("the two-stage vote returns one bit per element: a mean does not "
                              "fit it (aggregate must be majority)")
@@ -512,6 +534,7 @@ class Codec:
         on the GPU ``step_t`` / ``lr_t`` make the kernel derive it)."""
         if self.kind != "sign":
             raise ValueError("the 1-bit Adam step needs the sign codec")
+        self._unrotated("1-bit Adam's fused decode")
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
             b1, b2 = hp["betas"]
@@ -535,6 +558,7 @@ class Codec:
         make the kernels read the step and the lr from device memory)."""
         if self.kind != "sign":
             raise ValueError("the 1-bit LAMB step needs the sign codec")
+        self._unrotated("1-bit LAMB's fused decode")
         plan, lay = self.plans[b], self.layouts[b]
         kw = dict(lr=hp["lr"], eps=hp["eps"], freeze_step=hp["freeze_step"],
                   factor_min=hp["factor_min"], factor_max=hp["factor_max"],
@@ -564,12 +588,14 @@ class Codec:
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
             if self.kind == "sign":
-                ops.sign_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
+                ops.sign_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale,
+                                      rot_key=self.rot_key(b))
                 return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, grad_out=out, grad_scale=scale)
             return
-        out[:plan.length].copy_(oracle.decode_sum(recv, plan, lay, self.levels, scale))
+        out[:plan.length].copy_(oracle.decode_sum(recv, plan, lay, self.levels, scale,
+                                                  self.rot_key(b)))
 
     def decode_apply_sgd(self, b: int, recv: torch.Tensor, scale: float, param: torch.Tensor,
                          mom: torch.Tensor, hp: dict, first: bool, grad_out=None, shadow=None,
@@ -588,12 +614,12 @@ class Codec:
                       first=first, shadow=shadow, key_state=key_state, key_seed=self.seed,
                       key_rank=rank, lr_tensor=hp.get("lr_t"))
             if self.kind == "sign":
-                ops.sign_decode_apply(self.dplans[b], recv, lay, **kw)
+                ops.sign_decode_apply(self.dplans[b], recv, lay, rot_key=self.rot_key(b), **kw)
                 return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, **kw)
             return
-        g = oracle.decode_sum(recv, plan, lay, self.levels, scale)
+        g = oracle.decode_sum(recv, plan, lay, self.levels, scale, self.rot_key(b))
         if grad_out is not None:
             grad_out[:plan.length].copy_(g)
         for off, n in zip(plan.offsets, plan.numels):

@@ -18,7 +18,9 @@ Reference semantics being reproduced:
   * Scaled sign with error feedback (no reference counterpart; 1-bit SGD, Seide et al. 2014, and
     EF-signSGD, Karimireddy et al. 2019): per 8192-element chunk the mean |g + residual| and one
     bit per element.  The chunk sum is written in the kernel's own order (``_sign_chunk_sums``),
-    so scales, bits and residuals are bitwise the kernel's.
+    so scales, bits and residuals are bitwise the kernel's.  With ``rot_key`` the signs are taken
+    of a randomised Hadamard rotation of every chunk (DRIVE / EDEN, Vargaftik et al. 2021 / 2022;
+    ``fwht``, ``hsign_flip``): the butterfly stages run in the kernel's order, bitwise again.
   * 1-bit Adam's compressed stage (no reference counterpart; Tang et al., ICML 2021):
     ``encode_sign_momentum`` (the sign encode of the error-compensated momentum candidate) and
     ``onebit_adam_apply`` (averaged momentum, frozen-variance step), bitwise the kernels'.
@@ -286,14 +288,71 @@ def _sign_gather(plan: BucketPlan, device):
     return pos, valid, ln.to(torch.float32)
 
 
+# The rotated form (``--sign-rotate hadamard``; DRIVE / EDEN, Vargaftik et al. 2021 / 2022): every
+# chunk row, always over all CHUNK positions (0 past its length), is rotated by y = H(D e) before
+# the signs are taken, and the decoded row is rotated back by D(H(.)) * 2^-13.
+#
+#   * D flips sign bits (an xor of bit 31, so NaN and +/-0 agree with the kernel): word w of chunk
+#     row c is ``mix32((c * 256 + w) ^ rot_key)`` and its bit k belongs to element 32 w + k, the
+#     addressing of the packed sign words.  ``rot_key = hsign_rot_key(seed, bucket)`` depends on no
+#     step and no rank: the rotation is the same on every rank, so it is linear across them.
+#   * H is the unnormalised Walsh-Hadamard transform, one butterfly stage per index bit b in the
+#     order HSIGN_STAGE_BITS: new[i] = x[i] + x[i | 1 << b], new[i | 1 << b] = x[i] - x[i | 1 << b],
+#     every one a separately rounded fp32 operation.  The order is the kernel's (``ops/csrc/
+#     sign_codec.hip ew_fwht``): with i = u << 10 | wave << 8 | lane << 2 | j the register-local
+#     bits (j: 0, 1; u: 10, 11, 12) come first, then the lane bits 2..7, then the wave bits 8, 9.
+#     H H = 2^13 I, so the same stages run in both directions.
+HSIGN_STAGE_BITS = (0, 1, 10, 11, 12, 2, 3, 4, 5, 6, 7, 8, 9)
+HSIGN_INV = 2.0 ** -13
+ROT_TAG = 0x48534731  # "HSG1": the rank slot of stream_key, so no QSGD stream shares the key
+
+
+def hsign_rot_key(seed: int, bucket: int) -> int:
+    """The rotation key of bucket ``bucket``: a host constant, passed to the kernels as a uint32."""
+    return rng.stream_key(seed, bucket, ROT_TAG)
+
+
+def fwht(x: torch.Tensor) -> torch.Tensor:
+    """H of the rows of ``x`` (fp32 ``[C, CHUNK]``), stage by stage in HSIGN_STAGE_BITS order."""
+    C = x.shape[0]
+    for b in HSIGN_STAGE_BITS:
+        v = x.reshape(C, CHUNK >> (b + 1), 2, 1 << b)
+        lo, hi = v[:, :, 0], v[:, :, 1]
+        x = torch.stack((lo + hi, lo - hi), dim=2).reshape(C, CHUNK)
+    return x
+
+
+def hsign_flip(x: torch.Tensor, rot_key: int, row0: int = 0) -> torch.Tensor:
+    """D of the rows of ``x`` (fp32 ``[C, CHUNK]``; row r is chunk row ``row0 + r``)."""
+    C = x.shape[0]
+    w = torch.arange(row0 * (CHUNK // 32), (row0 + C) * (CHUNK // 32), dtype=torch.int64,
+                     device=x.device)
+    words = rng.mix32(w ^ (rot_key & rng.M32))
+    sh = torch.arange(32, dtype=torch.int64, device=x.device)
+    flip = ((words[:, None] >> sh) & 1).reshape(C, CHUNK)
+    bits = x.contiguous().view(torch.int32).to(torch.int64) ^ (flip << 31)
+    bits = ((bits + (1 << 31)) % (1 << 32)) - (1 << 31)
+    return bits.to(torch.int32).view(torch.float32)
+
+
+def hsign_unrotate(a: torch.Tensor, rot_key: int) -> torch.Tensor:
+    """``D(H(a)) * 2^-13`` of the rows of ``a``: the inverse of ``H(D .)``."""
+    return hsign_flip(fwht(a), rot_key) * torch.tensor(HSIGN_INV, dtype=torch.float32)
+
+
 def encode_sign(g: torch.Tensor, plan: BucketPlan, layout: Layout,
-                residual: torch.Tensor = None) -> torch.Tensor:
+                residual: torch.Tensor = None, rot_key: int = None) -> torch.Tensor:
     """Scaled sign of one bucket -> uint8 payload (``scales f32[C] | bits u32[256 C]``).
 
     Per chunk: ``e = g + residual`` (``e = g`` without error feedback), ``scale = sum|e| / len``
     (the fixed-order fp32 sum of :func:`_sign_chunk_sums`, one fp32 divide), ``bit = e < 0``
     (+0, -0 and NaN give 0), decoded value ``d = -scale if bit else scale``, and ``residual = e -
-    d``.  Bits past the chunk's length are 0."""
+    d``.  Bits past the chunk's length are 0.
+
+    ``rot_key`` (:func:`hsign_rot_key`): the rotated form.  The same quantiser runs on ``y = H(D
+    e)`` with length CHUNK for every chunk (``scale = sum|y| / 8192``, all 8192 bits meaningful),
+    and ``residual = D(H(y - d)) * 2^-13`` on the chunk's own positions: the residual stays in the
+    original domain."""
     if layout.kind != "sign":
         raise ValueError(f"encode_sign given a {layout.kind!r} layout")
     g = g.to(torch.float32)
@@ -301,6 +360,9 @@ def encode_sign(g: torch.Tensor, plan: BucketPlan, layout: Layout,
     C = plan.num_chunks
     pos, valid, lens = _sign_gather(plan, g.device)
     E = torch.where(valid, e[pos], torch.zeros((), dtype=torch.float32, device=g.device))
+    if rot_key is not None:
+        E = fwht(hsign_flip(E, rot_key))
+        lens = torch.full_like(lens, float(CHUNK))
     scale = _sign_chunk_sums(E.abs()) / lens
     neg = E < 0
     out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=g.device)
@@ -312,7 +374,10 @@ def encode_sign(g: torch.Tensor, plan: BucketPlan, layout: Layout,
         words.to(torch.int32).flatten())
     if residual is not None:
         d = torch.where(neg, -scale[:, None], scale[:, None])
-        residual[pos[valid]] = (E - d)[valid]
+        R = E - d
+        if rot_key is not None:
+            R = hsign_unrotate(R, rot_key)
+        residual[pos[valid]] = R[valid]
     return out
 
 
@@ -457,17 +522,36 @@ def onebit_lr_step(lr: float, beta1: float, beta2: float, step: int, freeze_step
     return lr * math.sqrt(1 - b2 ** freeze_step) / (1 - b1 ** step)
 
 
-def _sign_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+def _sign_rows(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    """``+/- scale`` of every position of every chunk row of one payload: fp32 ``[C, CHUNK]``."""
     C = plan.num_chunks
     scale = _section(pay, layout.scales, C, torch.float32)
     words = _section(pay, layout.codes, C * (CHUNK // 32), torch.int32).to(torch.int64)
     sh = torch.arange(32, dtype=torch.int64, device=pay.device)
     neg = ((words[:, None] >> sh) & 1).reshape(C, CHUNK).bool()
-    d = torch.where(neg, -scale[:, None], scale[:, None])
-    pos, valid, _ = _sign_gather(plan, pay.device)
-    out = torch.zeros(plan.length, dtype=torch.float32, device=pay.device)
+    return torch.where(neg, -scale[:, None], scale[:, None])
+
+
+def _sign_scatter(d: torch.Tensor, plan: BucketPlan) -> torch.Tensor:
+    pos, valid, _ = _sign_gather(plan, d.device)
+    out = torch.zeros(plan.length, dtype=torch.float32, device=d.device)
     out[pos[valid]] = d[valid]
     return out
+
+
+def _sign_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    return _sign_scatter(_sign_rows(pay, plan, layout), plan)
+
+
+def _hsign_decoded_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout,
+                       rot_key: int) -> torch.Tensor:
+    """The rotated codec's receive side: the rank-ordered sum from 0 of ``+/- scale_r`` over all
+    CHUNK positions of every row (the rotation is shared, so the sum commutes with it), one
+    inverse transform ``D(H(.)) * 2^-13``, and the chunk's own positions of the result."""
+    a = torch.zeros(plan.num_chunks, CHUNK, dtype=torch.float32, device=recv.device)
+    for r in range(recv.shape[0]):
+        a = a + _sign_rows(recv[r], plan, layout)
+    return _sign_scatter(hsign_unrotate(a, rot_key), plan)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -510,8 +594,14 @@ def _decoded_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout, levels
 
 
 def decode_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int,
-               scale: float) -> torch.Tensor:
-    """``recv``: uint8 [N, nbytes].  Returns fp32 [plan.length] = scale * sum_r decode(r)."""
+               scale: float, rot_key: int = None) -> torch.Tensor:
+    """``recv``: uint8 [N, nbytes].  Returns fp32 [plan.length] = scale * sum_r decode(r).
+    ``rot_key``: the rotated sign codec (``scale`` multiplies the inverse transform's output)."""
+    if rot_key is not None:
+        if layout.kind != "sign":
+            raise ValueError(f"only the sign codec is rotated, not {layout.kind!r}")
+        return (_hsign_decoded_sum(recv, plan, layout, rot_key)
+                * torch.tensor(scale, dtype=torch.float32))
     acc = torch.zeros(plan.length, dtype=torch.float32, device=recv.device)
     for r in range(recv.shape[0]):
         if layout.kind in ("topk", "topk_qsgd"):

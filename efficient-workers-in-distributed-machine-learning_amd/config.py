@@ -61,6 +61,9 @@ class Config:
     # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
+    # --compress sign: none | hadamard (the signs of a randomised Hadamard rotation of every chunk,
+    # DRIVE / EDEN; the same payload, one inverse transform on the receiver)
+    sign_rotate: str = "none"
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
     qsgd_levels: int = 127
@@ -201,6 +204,22 @@ class Config:
                     c.sync_mode = "model"
         if c.compress_grad.lower() == "none":
             c.compress = "none"
+        if c.sign_rotate not in ("none", "hadamard"):
+            raise ValueError("--sign-rotate must be none or hadamard")
+        if c.sign_rotate != "none":
+            # the rotated sign codec (compress/oracle.py encode_sign, rot_key): the all-gather
+            # exchange's encode and decode are rotated, nothing else is
+            why = None
+            if c.compress != "sign":
+                why = f"rotates the sign codec: it needs --compress sign, not {c.compress!r}"
+            elif c.topology == "twostage":
+                why = ("does not run with --topology twostage: the owner re-encode would need a "
+                       "transform pair of its own (the natural next step)")
+            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
+                why = (f"does not run with --optimizer {c.optimizer}: its fused decode is not "
+                       f"rotated")
+            if why is not None:
+                raise ValueError("--sign-rotate " + c.sign_rotate + " " + why)
         if c.compress == "vote":
             # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
             # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
@@ -470,6 +489,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])
     a("--vote-exchange", type=str, default=None, choices=["allgather", "twostage"])
     a("--powersgd-rank", type=int, default=d.powersgd_rank)
+    a("--sign-rotate", type=str, default=d.sign_rotate, choices=["none", "hadamard"])
     a("--topk-ratio", type=float, default=d.topk_ratio)
     a("--topk-dense-below", type=int, default=d.topk_dense_below)
     a("--qsgd-levels", type=int, default=d.qsgd_levels)

@@ -449,19 +449,31 @@ def _sign_payload(dp, payload, layout, slots):
     return layout.nbytes, layout.scales, layout.codes, 0, 0
 
 
-def sign_encode(dp, grad, payload, layout, resid=None, slots=None):
+def _rot(rot_key, slots):
+    """(rotate, rot_key) of the sign wrappers: ``rot_key`` None is the unrotated codec."""
+    if rot_key is None:
+        return 0, 0
+    if slots is not None:
+        raise ValueError("the rotated sign codec has no slot-addressed (two-stage) form")
+    return 1, int(rot_key) & 0xFFFFFFFF
+
+
+def sign_encode(dp, grad, payload, layout, resid=None, slots=None, rot_key=None):
     """Scaled sign of one bucket (``csrc/sign_codec.hip``): per chunk the mean ``|e|`` and one bit
     per element, ``e = grad + resid`` with ``resid`` (error feedback) overwritten by what was not
     sent.  One launch, no scratch; bitwise ``compress/oracle.py encode_sign``.  ``slots``
     (:class:`SignSlots`, also ``dp``): ``payload`` is the two-stage exchange's ``[N, P]`` row
-    buffer and every chunk is written to its slot (``layout`` unused; pads are not written)."""
+    buffer and every chunk is written to its slot (``layout`` unused; pads are not written).
+    ``rot_key`` (``oracle.hsign_rot_key``): the Hadamard-rotated form, ``k_hsign_encode``."""
     C = require()
+    rotate, rot_key = _rot(rot_key, slots)
     ptrs, mask = grad_pointers(dp, grad)
     nbytes, so, bo, sp, end = _sign_payload(dp, payload, layout, slots)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
     C.sign_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), nbytes,
-                  dp.plan.num_tensors, dp.plan.num_chunks, so, bo, _stream(), sp, end)
+                  dp.plan.num_tensors, dp.plan.num_chunks, so, bo, _stream(), sp, end,
+                  rotate, rot_key)
 
 
 def sign_reduce_encode(dp, recv, layout, inv_n, sresid, out):
@@ -505,12 +517,15 @@ def _sign_recv(dp, recv, layout, slots):
 def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
                       momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
                       nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
-                      key_rank=0, lr_tensor=None, slots=None):
+                      key_rank=0, lr_tensor=None, slots=None, rot_key=None):
     """``grad_out = grad_scale * sum over the rows of recv (rank order) of +/- scale`` and / or the
     fused SGD step on ``param`` (``mom`` None: a step without momentum).  ``slots``
     (:class:`SignSlots`, also ``dp``): ``recv`` is the two-stage exchange's gathered ``[N, P]``
-    buffer, every chunk read once from its slot (``layout`` unused)."""
+    buffer, every chunk read once from its slot (``layout`` unused).  ``rot_key``: the rotated
+    form, ``k_hsign_decode_apply`` (the summed rows go through one inverse transform; bitwise
+    ``oracle.decode_sum(..., rot_key=rot_key)``)."""
     C = require()
+    rotate, rot_key = _rot(rot_key, slots)
     nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
     apply = param is not None
     if apply:
@@ -529,7 +544,7 @@ def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=
                         _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
                         grad_scale, int(nesterov), int(first), int(apply), _stream(),
                         _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
-                        _lrp(lr_tensor), sp, end)
+                        _lrp(lr_tensor), sp, end, rotate, rot_key)
 
 
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,

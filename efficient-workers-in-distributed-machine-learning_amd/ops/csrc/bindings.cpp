@@ -211,8 +211,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("sign_encode",
         [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
            uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
-           int bits_off, uintptr_t stream, uintptr_t slots, long long slot_end) {
+           int bits_off, uintptr_t stream, uintptr_t slots, long long slot_end, int rotate,
+           uint32_t rot_key) {
           SignEncodeArgs a{};
+          a.rotate = rotate;
+          a.rot_key = rot_key;
           a.slots = slots;
           a.slot_end = slot_end;
           a.grad_ptrs = grads.data();
@@ -377,8 +380,10 @@ PYBIND11_MODULE(_C, m) {
            float lr, float momentum, float dampening, float weight_decay, float grad_scale,
            int nesterov, int first, int apply, uintptr_t stream, uintptr_t key_state,
            uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr, uintptr_t slots,
-           long long slot_end) {
+           long long slot_end, int rotate, uint32_t rot_key) {
           SignDecodeArgs a{};
+          a.rotate = rotate;
+          a.rot_key = rot_key;
           a.slots = slots;
           a.slot_end = slot_end;
           a.lr_ptr = lr_ptr;

@@ -109,6 +109,11 @@ struct SignEncodeArgs {
   // = the largest offset a slot reaches.  scales_off / bits_off are unused and no pad is written
   uintptr_t slots;
   long long slot_end;
+  // the rotated form (rotate != 0; --sign-rotate hadamard): the signs are taken of H(D e) over all
+  // 8192 positions of every chunk row and the residual is rotated back; rot_key picks D.  No
+  // slot-addressed and no momentum form
+  int rotate;
+  uint32_t rot_key;
 };
 
 // the two-stage exchange's owner step (sign_codec.hip k_sign_reduce_encode): the rows of recv
@@ -174,6 +179,8 @@ struct SignDecodeArgs {
   uintptr_t lr_ptr;
   uintptr_t slots;  // see SignOnebitArgs
   long long slot_end;
+  int rotate;  // see SignEncodeArgs: one inverse transform of the summed rows (slots must be 0)
+  uint32_t rot_key;
 };
 
 // PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /

@@ -148,6 +148,160 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_encode(GradPtrs gp, float* __
   if (EF) ew_st_chunk(resid + c.start, c.len, e);
 }
 
+// ---- the rotated form (--sign-rotate hadamard; DRIVE / EDEN, Vargaftik et al. 2021 / 2022) -----
+// The chunk row, always all EW_CHUNK positions of it, is rotated by y = H(D e) before the signs
+// are taken and the decoded row is rotated back by D(H(.)) * 2^-13 (compress/oracle.py fwht /
+// hsign_flip, bit for bit).  D flips sign bits chosen by rot_key, a host constant of the bucket
+// that is the same on every rank and every step; H is the unnormalised Walsh-Hadamard transform
+// of the 8192 values held across the block's registers, one butterfly stage per index bit.  With
+// element i = u << 10 | wave << 8 | lane << 2 | j (ew_chunk_idx) the stages run in the order
+// oracle.HSIGN_STAGE_BITS: bits 0, 1 (j) and 10..12 (u) inside a thread, bits 2..7 across the
+// lanes of a wave, bits 8, 9 across the four waves through LDS.  Every butterfly is one fp32 add:
+// the upper element's x[i] - x[i | bit] is formed as x[i] + (-x[i | bit]), which rounds the same.
+
+// D: word w = u * 32 + (t >> 3) of chunk row c is mix32((c * 256 + w) ^ rot_key); thread t's four
+// elements of slab u are bits 4 (t & 7) .. + 3 of it, the nibble ew_sign_pack writes
+__device__ __forceinline__ float ew_flip(float x, uint32_t bit) {
+  return __uint_as_float(__float_as_uint(x) ^ (bit << 31));
+}
+__device__ __forceinline__ void ew_hs_flip(float4 (&e)[EW_CU], uint32_t rot_key) {
+  const uint32_t w0 = blockIdx.x * EW_BM_WORDS + (threadIdx.x >> 3);
+  const int shift = 4 * (threadIdx.x & 7);
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const uint32_t nib = ew_mix32((w0 + u * (EW_BLOCK / 8)) ^ rot_key) >> shift;
+    e[u] = make_float4(ew_flip(e[u].x, nib & 1u), ew_flip(e[u].y, (nib >> 1) & 1u),
+                       ew_flip(e[u].z, (nib >> 2) & 1u), ew_flip(e[u].w, (nib >> 3) & 1u));
+  }
+}
+
+// one butterfly between two values of the same thread
+__device__ __forceinline__ void ew_bfly(float& a, float& b) {
+  const float s = a + b, d = a - b;
+  a = s;
+  b = d;
+}
+
+// the value lane ^ D holds: quad permutes (DPP, no LDS crossbar) inside a quad, ds_bpermute beyond
+template <int D>
+__device__ __forceinline__ float ew_lane_xor(float x) {
+  if (D == 1)  // quad_perm [1, 0, 3, 2]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));
+  if (D == 2)  // quad_perm [2, 3, 0, 1]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, false));
+  return __shfl_xor(x, D, 64);
+}
+
+// the stage of lane bit D: the lower lane keeps x + other, the upper lane other - x
+template <int D>
+__device__ __forceinline__ void ew_fwht_lanes(float4 (&e)[EW_CU]) {
+  const uint32_t up = ((threadIdx.x & D) != 0) ? 1u : 0u;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    e[u].x = ew_flip(e[u].x, up) + ew_lane_xor<D>(e[u].x);
+    e[u].y = ew_flip(e[u].y, up) + ew_lane_xor<D>(e[u].y);
+    e[u].z = ew_flip(e[u].z, up) + ew_lane_xor<D>(e[u].z);
+    e[u].w = ew_flip(e[u].w, up) + ew_lane_xor<D>(e[u].w);
+  }
+}
+
+// H of the block's chunk, in place.  xch: EW_CU * EW_BLOCK float4 of LDS (32 KiB), free again on
+// return.  Every thread of the block must call it.
+__device__ __forceinline__ void ew_fwht(float4 (&e)[EW_CU], float4* xch) {
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {  // bits 0, 1
+    ew_bfly(e[u].x, e[u].y);
+    ew_bfly(e[u].z, e[u].w);
+    ew_bfly(e[u].x, e[u].z);
+    ew_bfly(e[u].y, e[u].w);
+  }
+#pragma unroll
+  for (int m = 1; m < EW_CU; m <<= 1)  // bits 10, 11, 12
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u)
+      if (!(u & m)) {
+        ew_bfly(e[u].x, e[u | m].x);
+        ew_bfly(e[u].y, e[u | m].y);
+        ew_bfly(e[u].z, e[u | m].z);
+        ew_bfly(e[u].w, e[u | m].w);
+      }
+  ew_fwht_lanes<1>(e);  // bits 2 .. 7
+  ew_fwht_lanes<2>(e);
+  ew_fwht_lanes<4>(e);
+  ew_fwht_lanes<8>(e);
+  ew_fwht_lanes<16>(e);
+  ew_fwht_lanes<32>(e);
+  // bits 8, 9: the same lane of the four waves.  After bit 8 wave w holds v0 +/- v1 (w < 2) or
+  // v2 +/- v3, minus in the odd waves; bit 9 pairs waves w and w ^ 2, minus in waves 2 and 3
+  const int lane = threadIdx.x & 63;
+  const uint32_t odd = (threadIdx.x >> 6) & 1u, top = (threadIdx.x >> 7) & 1u;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) xch[u * EW_BLOCK + threadIdx.x] = e[u];
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const float4 v0 = xch[u * EW_BLOCK + lane], v1 = xch[u * EW_BLOCK + 64 + lane];
+    const float4 v2 = xch[u * EW_BLOCK + 128 + lane], v3 = xch[u * EW_BLOCK + 192 + lane];
+    const float4 lo = make_float4(v0.x + ew_flip(v1.x, odd), v0.y + ew_flip(v1.y, odd),
+                                  v0.z + ew_flip(v1.z, odd), v0.w + ew_flip(v1.w, odd));
+    const float4 hi = make_float4(v2.x + ew_flip(v3.x, odd), v2.y + ew_flip(v3.y, odd),
+                                  v2.z + ew_flip(v3.z, odd), v2.w + ew_flip(v3.w, odd));
+    e[u] = make_float4(lo.x + ew_flip(hi.x, top), lo.y + ew_flip(hi.y, top),
+                       lo.z + ew_flip(hi.z, top), lo.w + ew_flip(hi.w, top));
+  }
+  __syncthreads();
+}
+
+// the inverse rotation of a row held in e: D(H(e)) * 2^-13
+__device__ __forceinline__ void ew_hs_unrotate(float4 (&e)[EW_CU], uint32_t rot_key, float4* xch) {
+  ew_fwht(e, xch);
+  ew_hs_flip(e, rot_key);
+  const float inv = 1.0f / (float)EW_CHUNK;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u)
+    e[u] = make_float4(e[u].x * inv, e[u].y * inv, e[u].z * inv, e[u].w * inv);
+}
+
+// The rotated encode: one block per chunk row, one launch per bucket.  The quantiser is
+// ew_sign_pack over all EW_CHUNK positions of y (scale = sum|y| / 8192, every bit meaningful); with
+// error feedback the residual goes back through the inverse rotation and only the chunk's own
+// positions are stored, so the residual buffer keeps its meaning
+template <bool EF>
+__global__ __launch_bounds__(EW_BLOCK) void k_hsign_encode(GradPtrs gp, float* __restrict__ resid,
+                                                           const ChunkRow* __restrict__ chunks,
+                                                           uint8_t* __restrict__ payload,
+                                                           int scales_off, int bits_off,
+                                                           uint32_t rot_key) {
+  __shared__ float4 xch[EW_CU * EW_BLOCK];
+  __shared__ float wsf[EW_WAVES];
+  __shared__ float s_scale;
+  const ChunkRow c = chunks[blockIdx.x];
+  float4 e[EW_CU];
+  ew_ld_chunk(gp, nullptr, c, e);  // positions past c.len read as 0
+  if (EF) {
+    float4 r[EW_CU];
+    ew_ld_chunk(gp, resid, c, r);
+#pragma unroll
+    for (int u = 0; u < EW_CU; ++u)
+      e[u] = make_float4(e[u].x + r[u].x, e[u].y + r[u].y, e[u].z + r[u].z, e[u].w + r[u].w);
+  }
+  if (blockIdx.x == 0) {  // the scales section's alignment pad: payloads compare bytewise
+    const int nslots = (bits_off - scales_off) >> 2;
+    for (int i = (int)gridDim.x + (int)threadIdx.x; i < nslots; i += EW_BLOCK)
+      reinterpret_cast<float*>(payload + scales_off)[i] = 0.0f;
+  }
+  ew_hs_flip(e, rot_key);
+  ew_fwht(e, xch);
+  size_t scale_at, words_at;
+  ew_sign_where(nullptr, scales_off, bits_off, scale_at, words_at);
+  ew_sign_pack(e, EW_CHUNK, reinterpret_cast<float*>(payload + scale_at),
+               reinterpret_cast<uint32_t*>(payload + words_at), wsf, &s_scale);
+  if (EF) {
+    ew_hs_unrotate(e, rot_key, xch);
+    ew_st_chunk(resid + c.start, c.len, e);
+  }
+}
+
 // The rank-ordered sum, from 0.0f, of +/- scale_r over the rows of recv for this block's chunk:
 // acc[u][j] is element ew_chunk_idx(u) + j, which is the encode's e[u] layout.
 __device__ __forceinline__ void ew_sign_acc(const uint8_t* __restrict__ recv, int nranks,
@@ -214,18 +368,13 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_reduce_encode(
   ew_st_chunk(sresid + c.start, c.len, e);
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
-    const uint8_t* __restrict__ recv, int nranks, long long stride,
-    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
-    float* __restrict__ mom, float* __restrict__ grad_out, uint16_t* __restrict__ shadow,
-    SgdArgs sa, int apply, const int2* __restrict__ slots) {
-  const ChunkRow c = chunks[blockIdx.x];
-  ew_sgd_resolve(sa);
-  ew_key_advance(sa);
-  size_t scale_at, words_at;
-  ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
-  float acc[EW_CU][4];
-  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
+// What the decodes do with the chunk's decoded sum (acc, the ew_sign_acc layout): * grad_scale,
+// then grad_out and / or the fused SGD step with its bf16 shadow, on the chunk's own positions
+__device__ __forceinline__ void ew_sign_apply(const float (&acc)[EW_CU][4], const ChunkRow& c,
+                                              float* __restrict__ param, float* __restrict__ mom,
+                                              float* __restrict__ grad_out,
+                                              uint16_t* __restrict__ shadow, const SgdArgs& sa,
+                                              int apply) {
   float* p = param + c.start;
   float* b = mom ? mom + c.start : nullptr;
   float* go = grad_out ? grad_out + c.start : nullptr;
@@ -262,6 +411,48 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
       }
     }
   }
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
+    float* __restrict__ mom, float* __restrict__ grad_out, uint16_t* __restrict__ shadow,
+    SgdArgs sa, int apply, const int2* __restrict__ slots) {
+  const ChunkRow c = chunks[blockIdx.x];
+  ew_sgd_resolve(sa);
+  ew_key_advance(sa);
+  size_t scale_at, words_at;
+  ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
+  float acc[EW_CU][4];
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
+  ew_sign_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
+}
+
+// The rotated decode: the N ranks' +/- scale are summed in the rotated domain over all EW_CHUNK
+// positions (the rotation is shared, so it commutes with the sum), then one inverse transform
+// whatever N is, then k_sign_decode_apply's tail
+__global__ __launch_bounds__(EW_BLOCK) void k_hsign_decode_apply(
+    const uint8_t* __restrict__ recv, int nranks, long long stride,
+    const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
+    float* __restrict__ mom, float* __restrict__ grad_out, uint16_t* __restrict__ shadow,
+    SgdArgs sa, int apply, uint32_t rot_key) {
+  __shared__ float4 xch[EW_CU * EW_BLOCK];
+  const ChunkRow c = chunks[blockIdx.x];
+  ew_sgd_resolve(sa);
+  ew_key_advance(sa);
+  size_t scale_at, words_at;
+  ew_sign_where(nullptr, scales_off, bits_off, scale_at, words_at);
+  float acc[EW_CU][4];
+  ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
+  float4 e[EW_CU];
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) e[u] = make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+  ew_hs_unrotate(e, rot_key, xch);
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    acc[u][0] = e[u].x; acc[u][1] = e[u].y; acc[u][2] = e[u].z; acc[u][3] = e[u].w;
+  }
+  ew_sign_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
 }
 
 // 1-bit Adam's receive side: m = (sum over ranks of +/- scale, rank order, from 0) * inv_n for
@@ -552,7 +743,20 @@ void ew_sign_encode(const SignEncodeArgs& a) {
   auto* pay = reinterpret_cast<uint8_t*>(a.payload);
   const SignMom mo{reinterpret_cast<const float*>(a.mom_exp_avg),
                    reinterpret_cast<const float*>(a.mom_param), a.mom_beta1, a.mom_wd};
-  if (mo.m) {  // 1-bit Adam's momentum encode: error feedback always on
+  if (a.rotate) {
+    if (slots || mo.m)
+      throw std::runtime_error("ewdml sign: the rotated encode has no slot-addressed and no "
+                               "momentum form");
+    if (!chunks || !pay) throw std::runtime_error("ewdml sign: missing table");
+    if ((a.payload | a.resid) % 16 || a.chunks % 4)
+      throw std::runtime_error("ewdml sign: misaligned operand");
+    if (resid)
+      EW_LAUNCH((k_hsign_encode<true>), C, a.stream, g, resid, chunks, pay, a.scales_off,
+                a.bits_off, a.rot_key);
+    else
+      EW_LAUNCH((k_hsign_encode<false>), C, a.stream, g, resid, chunks, pay, a.scales_off,
+                a.bits_off, a.rot_key);
+  } else if (mo.m) {  // 1-bit Adam's momentum encode: error feedback always on
     if (!resid) throw std::runtime_error("ewdml sign: the momentum encode needs the residual");
     if (mo.wd != 0.0f && !mo.p)
       throw std::runtime_error("ewdml sign: weight decay needs the parameters");
@@ -683,6 +887,21 @@ void ew_sign_decode_apply(const SignDecodeArgs& a) {
   SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
              reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
   sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
+  if (a.rotate) {
+    if (a.slots)
+      throw std::runtime_error("ewdml sign decode: the rotated decode has no slot-addressed form");
+    if (!a.recv || !a.chunks) throw std::runtime_error("ewdml sign decode: missing table");
+    if ((a.param | a.mom | a.grad_out) % 16 || a.shadow % 8 || a.recv % 16 || a.stride % 4 ||
+        (a.chunks | a.key_state | a.lr_ptr) % 4)
+      throw std::runtime_error("ewdml sign decode: misaligned operand");
+    EW_LAUNCH(k_hsign_decode_apply, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv),
+              a.nranks, a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off,
+              a.bits_off, reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
+              reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
+              a.apply, a.rot_key);
+    EW_CHECK_LAUNCH();
+    return;
+  }
   EW_LAUNCH(k_sign_decode_apply, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv), a.nranks,
             a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
             reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),

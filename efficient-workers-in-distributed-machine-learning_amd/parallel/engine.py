@@ -113,6 +113,9 @@ class GradientExchange:
         if self.onebit and (codec.kind != "sign" or self.resid is None or predivide != 1.0):
             raise ValueError("1-bit Adam's and 1-bit LAMB's compressed stage needs the sign codec "
                              "with error feedback and predivide 1")
+        if self.onebit and getattr(codec, "rotate", "none") != "none":
+            raise ValueError("1-bit Adam's and 1-bit LAMB's fused decodes are not rotated: they "
+                             "do not run with a rotated sign codec")
         # Distributed Lion (optim/flat.py FlatLion under the vote codec): the encode sends the sign
         # of this rank's own update direction and moves this rank's own momentum, the apply
         # counts the votes and steps.  No residual, no velocity; opt.exp_avg is per-rank state

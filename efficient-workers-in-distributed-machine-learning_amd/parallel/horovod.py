@@ -148,9 +148,10 @@ class Compression:
         return Codec("topk_qsgd", ratio=ratio, levels=levels, bits=bits, norm=norm)
 
     @staticmethod
-    def sign():
-        """Scaled sign, 1 bit per element; the optimizer wrapper keeps its error feedback."""
-        return Codec("sign")
+    def sign(rotate: str = "none"):
+        """Scaled sign, 1 bit per element; the optimizer wrapper keeps its error feedback.
+        ``rotate="hadamard"``: the signs of a randomised Hadamard rotation of every chunk."""
+        return Codec("sign", rotate=rotate)
 
     @staticmethod
     def powersgd(rank: int = 4):

@@ -235,6 +235,8 @@ class Trainer:
                    norm=cfg.qsgd_norm, seed=cfg.seed, dense_below=cfg.topk_dense_below)
         if cfg.compress == "vote":
             ckw["aggregate"] = cfg.vote_aggregate
+        if cfg.sign_rotate != "none":
+            ckw["rotate"] = cfg.sign_rotate
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
         self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
