@@ -14,6 +14,9 @@
   * ``vote``  -- Distributed Lion's 1-bit majority vote (Liu et al. 2024): one bit per element, the
     sign of the rank's own Lion update direction; no scale, no residual (``encode_vote`` /
     ``decode_apply_vote``; needs ``optim/flat.py FlatLion``)
+  * ``mx``    -- OCP Microscaling block floating point (``fmt``: ``fp8`` = MXFP8, E4M3 elements;
+    ``fp4`` = MXFP4, E2M1): every 32 elements share one power-of-two scale byte; runs with error
+    feedback on the all-gather exchange, one encode and one fused decode launch per bucket
   * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
     al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
     methods below)
@@ -34,15 +37,17 @@ from . import oracle
 from .plan import POWERSGD_RANKS, BucketPlan, Layout
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote")
+KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx")
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
+MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
 
 
 class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
-                 rank: int = 4, aggregate: str = "majority", rotate: str = "none"):
+                 rank: int = 4, aggregate: str = "majority", rotate: str = "none",
+                 fmt: str = None):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
@@ -58,6 +63,14 @@ class Codec:
         if rotate != "none" and kind != "sign":
             raise ValueError("the rotation belongs to the sign codec")
         self.rotate = rotate
+        if fmt is not None and kind != "mx":
+            raise ValueError("the element format belongs to the mx codec")
+        if kind == "mx":  # the element width is the format's, whatever `bits` says
+            fmt = "fp8" if fmt is None else fmt
+            if fmt not in MX_FORMATS:
+                raise ValueError(f"mx format must be one of {MX_FORMATS}, not {fmt!r}")
+            bits = oracle.MX_NAMES[fmt]
+        self.fmt = fmt
         # the sign, vote and low-rank codecs have neither bits nor levels
         if kind not in ("sign", "powersgd", "vote") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
@@ -98,6 +111,8 @@ class Codec:
             return f"powersgd-r{self.rank}"
         if self.kind == "vote":
             return "vote1b"
+        if self.kind == "mx":
+            return "mx" + self.fmt
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -178,8 +193,8 @@ class Codec:
         (``ops.topk_encode``), so no decode launch follows."""
         if dgc is not None and (resid is None or self.kind not in ("topk", "topk_qsgd")):
             raise ValueError("momentum correction needs a top-k codec and a residual")
-        if self.kind == "sign" and apply is not None:
-            raise ValueError("the sign codec has no encode-side apply")
+        if self.kind in ("sign", "mx") and apply is not None:
+            raise ValueError(f"the {self.kind} codec has no encode-side apply")
         if self.kind == "vote":
             raise ValueError("the vote codec sends the sign of Lion's update direction: "
                              "encode_vote, with the rank's momentum")
@@ -194,6 +209,8 @@ class Codec:
             if self.kind == "sign":
                 ops.sign_encode(self.dplans[b], grad, payload, lay, resid,
                                 rot_key=self.rot_key(b))
+            elif self.kind == "mx":
+                ops.mx_encode(self.dplans[b], grad, payload, lay, resid)
             elif self.kind == "qsgd":
                 ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
                                 resid, key_tensor)
@@ -207,6 +224,8 @@ class Codec:
             raise TypeError("CPU encode takes the bucket's flat gradient view")
         if self.kind == "sign":
             out = oracle.encode_sign(grad, plan, lay, resid, self.rot_key(b))
+        elif self.kind == "mx":
+            out = oracle.encode_mx(grad, plan, lay, resid)
         elif self.kind == "qsgd":
             out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
         else:
@@ -591,6 +610,9 @@ class Codec:
                 ops.sign_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale,
                                       rot_key=self.rot_key(b))
                 return
+            if self.kind == "mx":
+                ops.mx_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
+                return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, grad_out=out, grad_scale=scale)
             return
@@ -615,6 +637,9 @@ class Codec:
                       key_rank=rank, lr_tensor=hp.get("lr_t"))
             if self.kind == "sign":
                 ops.sign_decode_apply(self.dplans[b], recv, lay, rot_key=self.rot_key(b), **kw)
+                return
+            if self.kind == "mx":
+                ops.mx_decode_apply(self.dplans[b], recv, lay, **kw)
                 return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, **kw)

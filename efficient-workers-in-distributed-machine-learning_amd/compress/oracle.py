@@ -27,6 +27,9 @@ Reference semantics being reproduced:
   * 1-bit LAMB's compressed stage (no reference counterpart; Li et al., 2021): the same sender
     with weight decay 0 and ``onebit_lamb_apply`` (averaged momentum, fresh variance, per-tensor
     factor on the frozen trust ratio), bitwise the kernels'.
+  * Block floating point (no reference counterpart; OCP Microscaling v1.0, Rouhani et al. 2023):
+    ``encode_mx`` -- one power-of-two scale byte per 32 elements, FP8 E4M3 or FP4 E2M1 elements
+    rounded to nearest even and saturated, with error feedback; bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -555,6 +558,127 @@ def _hsign_decoded_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout,
 
 
 # ---------------------------------------------------------------------------------------------
+# block floating point: OCP Microscaling (MX) v1.0, 32 elements per power-of-two E8M0 scale
+# ---------------------------------------------------------------------------------------------
+# bits -> (exponent bits, mantissa bits, exponent bias, largest finite value, emax)
+MX_FORMATS = {8: (4, 3, 7, 448.0, 8), 4: (2, 1, 1, 6.0, 2)}
+MX_NAMES = {"fp8": 8, "fp4": 4}  # FP8 E4M3 | FP4 E2M1
+
+
+def _pow2(k: torch.Tensor) -> torch.Tensor:
+    """fp64 ``2^k`` of an int64 tensor, built from the exponent field (|k| <= 1022)."""
+    return ((k + 1023) << 52).view(torch.float64)
+
+
+def mx_scale_bytes(e: torch.Tensor, bits: int) -> torch.Tensor:
+    """The E8M0 scale byte (int64) of every row of ``e`` (fp32 ``[B, 32]``): with ``em`` the
+    exponent field of the largest ``bits(e) & 0x7fffffff`` of the block (an unsigned integer
+    maximum, so a NaN is not dropped), ``s = clamp(em - emax, 0, 254)``, and ``0xFF`` where ``em
+    == 255`` (the block holds an inf or a NaN)."""
+    emax = MX_FORMATS[bits][4]
+    mag = e.contiguous().view(torch.int32).to(torch.int64) & 0x7FFFFFFF
+    em = mag.max(dim=1).values >> 23
+    return torch.where(em == 255, torch.full_like(em, 255), (em - emax).clamp(0, 254))
+
+
+def mx_quantize(e: torch.Tensor, s: torch.Tensor, bits: int) -> torch.Tensor:
+    """Element codes (uint8 ``[B, 32]``) of the blocks ``e`` (fp32 ``[B, 32]``) under the scale
+    bytes ``s`` (:func:`mx_scale_bytes`): ``q = e / 2^(s - 127)`` exactly (fp64), rounded to
+    nearest even on the format's grid and saturated to its largest finite value (448, code 0x7E,
+    for E4M3; 6, code 0x7, for E2M1).  The code's sign bit is ``e``'s sign bit, so a negative
+    value that rounds to zero and -0.0 itself give the code of -0.  A block with ``s == 0xFF``
+    gets codes 0."""
+    _, mb, bias, top, _ = MX_FORMATS[bits]
+    dead = (s == 255)[:, None]
+    a = e.abs().to(torch.float64) * _pow2(127 - s.clamp(max=254))[:, None]
+    a = torch.where(dead, torch.zeros_like(a), a).clamp(max=top)
+    ex = ((a.view(torch.int64) >> 52) & 0x7FF) - 1023  # floor(log2 a); -1023 for 0
+    ex = ex.clamp(min=1 - bias)  # below the smallest normal the grid keeps its spacing
+    n = torch.round(a * _pow2(mb - ex)).to(torch.int64)  # half to even; 0 .. 2^(mb + 1)
+    # n < 2^mb: a subnormal code; n == 2^(mb + 1) carries into the exponent field
+    mag = ((ex + bias - 1) << mb) + n
+    neg = (e.contiguous().view(torch.int32).to(torch.int64) >> 31) & 1
+    code = torch.where(dead, torch.zeros_like(mag), mag | (neg << (bits - 1)))
+    return code.to(torch.uint8)
+
+
+def mx_dequantize(codes: torch.Tensor, s: torch.Tensor, bits: int) -> torch.Tensor:
+    """fp32 ``value(code) * 2^(s - 127)`` of every element of the blocks ``codes`` (uint8 ``[B,
+    32]``): exact in fp32 for every code the encode writes (at most 4 significant bits, no smaller
+    than 2^-136).  A block with ``s == 0xFF`` is NaN (0x7FC00000) on all 32 positions, and so are
+    E4M3's own NaN codes 0x7F / 0xFF, which no encode writes."""
+    _, mb, bias, _, _ = MX_FORMATS[bits]
+    c = codes.to(torch.int64)
+    mag = c & ((1 << (bits - 1)) - 1)
+    ef, m = mag >> mb, mag & ((1 << mb) - 1)
+    val = torch.where(ef == 0, m.to(torch.float64) * 2.0 ** (1 - bias - mb),
+                      ((1 << mb) + m).to(torch.float64) * _pow2(ef - bias - mb))
+    d = (val * _pow2(s.clamp(max=254) - 127)[:, None]).to(torch.float32)
+    d = torch.where((c >> (bits - 1)) == 1, -d, d)
+    nan = (s == 255)[:, None]
+    if bits == 8:
+        nan = nan | (mag == 0x7F)
+    return torch.where(nan, torch.full_like(d, float("nan")), d)
+
+
+def _mx_mask(plan: BucketPlan, device) -> torch.Tensor:
+    """True on the positions of the padded bucket that belong to a tensor."""
+    own = torch.zeros(plan.length, dtype=torch.bool, device=device)
+    for off, n in zip(plan.offsets, plan.numels):
+        own[off:off + n] = True
+    return own
+
+
+def encode_mx(g: torch.Tensor, plan: BucketPlan, layout: Layout,
+              residual: torch.Tensor = None) -> torch.Tensor:
+    """MXFP8 / MXFP4 of one bucket -> uint8 payload (``scales u8[L / 32] | codes``; ``L =
+    plan.length``, ``layout.bits`` 8: one E4M3 byte per position, 4: E2M1 nibbles, the low nibble
+    the even position).
+
+    ``e = g + residual`` (``e = g`` without error feedback) on the tensors' positions and 0 on the
+    pads between them; every 32 consecutive positions of the bucket are one block
+    (:func:`mx_scale_bytes`, :func:`mx_quantize`); ``residual = e - d`` with ``d`` the decoded
+    value (:func:`mx_dequantize`), one fp32 subtract, NaN on every position of a block that held
+    an inf or a NaN.  Pads encode as scale 0 and code 0, so every byte of the payload is written.
+
+    Where the OCP text is silent the gfx950 conversion instructions were measured to agree with
+    the choices made here (``profiles/validation/mx.md``): the sign of a zero code is the input's
+    and the low nibble of an FP4 byte is the even element; a non-finite block decodes to the quiet
+    NaN 0x7FC00000, which the kernels form themselves.  Saturation is this function's, not the
+    E4M3 instruction's: that one answers its NaN code above 464 and the kernel clamps first."""
+    if layout.kind != "mx":
+        raise ValueError(f"encode_mx given a {layout.kind!r} layout")
+    bits, L = layout.bits, plan.length
+    g = g.to(torch.float32)[:L]
+    e = g + residual[:L] if residual is not None else g
+    own = _mx_mask(plan, g.device)
+    E = torch.where(own, e, torch.zeros((), dtype=torch.float32, device=g.device)).reshape(-1, 32)
+    s = mx_scale_bytes(E, bits)
+    codes = mx_quantize(E, s, bits)
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=g.device)
+    out[layout.scales:layout.scales + L // 32] = s.to(torch.uint8)
+    flat = codes.flatten()
+    if bits == 4:
+        flat = flat[0::2] | (flat[1::2] << 4)
+    out[layout.codes:layout.codes + flat.numel()] = flat
+    if residual is not None:
+        R = (E - mx_dequantize(codes, s, bits)).flatten()
+        residual[:L][own] = R[own]
+    return out
+
+
+def _mx_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    """One payload decoded on the tensors' positions (0 on the pads): fp32 ``[plan.length]``."""
+    bits, L = layout.bits, plan.length
+    s = pay[layout.scales:layout.scales + L // 32].to(torch.int64)
+    c = pay[layout.codes:layout.codes + L * bits // 8]
+    if bits == 4:
+        c = torch.stack([c & 0xF, c >> 4], 1).flatten()
+    d = mx_dequantize(c.reshape(-1, 32), s, bits).flatten()
+    return torch.where(_mx_mask(plan, pay.device), d, torch.zeros_like(d))
+
+
+# ---------------------------------------------------------------------------------------------
 # decode: sum over ranks (in rank order) of the dequantised payloads, times ``scale``
 # ---------------------------------------------------------------------------------------------
 def _decoded_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int):
@@ -609,6 +733,8 @@ def decode_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int
             acc.index_add_(0, pos, vals)
         elif layout.kind == "sign":
             acc += _sign_decoded(recv[r], plan, layout)
+        elif layout.kind == "mx":
+            acc += _mx_decoded(recv[r], plan, layout)
         else:
             acc += _dense_decoded(recv[r], plan, layout, levels)
     return acc * torch.tensor(scale, dtype=torch.float32)

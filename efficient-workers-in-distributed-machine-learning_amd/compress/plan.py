@@ -26,6 +26,9 @@ exchange is a fixed-size all-gather with no size handshake):
                256 c + 256), element i of the chunk is bit i & 31 of word i >> 5, padding bits 0)
 ``vote``     : bits u32[256 C]  (Distributed Lion: the words and bit addressing of ``sign``, no
                scales section; exactly 1024 C bytes)
+``mx``       : scales u8[L / 32] | codes u8[L] (bits=8, FP8 E4M3) or nibbles u8[L / 2] (bits=4, FP4
+               E2M1; the low nibble is the even element).  L = the bucket's padded length; element
+               i of the bucket is code i and its E8M0 scale is byte i >> 5; pads are written as 0
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -36,6 +39,7 @@ import torch
 
 CHUNK = 8192
 BM_WORDS = CHUNK // 32  # bitmap words per chunk
+MX_BLOCK = 32  # positions sharing one scale byte (OCP Microscaling v1.0)
 # predictive top-k encode (ops/csrc/topk_codec.hip): a tensor keeps at most this many candidates
 # (elements at or above its predicted threshold) per step: CAND_K_MULT * k + CAND_SLACK, capped at
 # numel; more (or fewer than k) and that tensor takes the exact full-pass path for the step
@@ -217,6 +221,22 @@ class Layout:
             bits = 1
             scales = counts = idx = codes = 0
             off = 4 * BM_WORDS * C
+        elif kind == "mx":
+            # one E8M0 scale byte per 32 positions of the padded bucket, then one FP8 / FP4 code
+            # per position (`codes` is their byte offset); addressed by the bucket's flat index
+            if bits not in (4, 8):
+                raise ValueError("the mx codec sends 8-bit (E4M3) or 4-bit (E2M1) elements")
+            # every chunk row owns the positions up to the next row's start (the kernels write the
+            # pad's zeros from there): tensors packed at the next multiple of 64, as
+            # parallel/flat.py lays them out
+            L = plan.length
+            ends = [_align(o + n, 64) for o, n in zip(plan.offsets, plan.numels)]
+            if list(plan.offsets) + [L] != [0] + ends:
+                raise ValueError("the mx codec needs a bucket of tensors packed at multiples of 64 "
+                                 "elements from offset 0")
+            off = _align(L // MX_BLOCK)
+            counts = idx = codes = off
+            off += L * bits // 8
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)

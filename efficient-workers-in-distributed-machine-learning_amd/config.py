@@ -58,12 +58,15 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote
+    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     # --compress sign: none | hadamard (the signs of a randomised Hadamard rotation of every chunk,
     # DRIVE / EDEN; the same payload, one inverse transform on the receiver)
     sign_rotate: str = "none"
+    # --compress mx (OCP Microscaling block floating point, one power-of-two scale byte per 32
+    # elements): fp8 (MXFP8, E4M3 elements) | fp4 (MXFP4, E2M1) (None: fp8)
+    mx_format: Optional[str] = None
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
     qsgd_levels: int = 127
@@ -220,6 +223,36 @@ class Config:
                        f"rotated")
             if why is not None:
                 raise ValueError("--sign-rotate " + c.sign_rotate + " " + why)
+        if c.compress == "mx":
+            # MXFP8 / MXFP4 (compress/oracle.py encode_mx): the all-gather exchange's encode and
+            # fused decode, with that exchange's residual; nothing else has an mx form
+            if c.mx_format is None:
+                c.mx_format = "fp8"
+            why = None
+            if c.mx_format not in ("fp8", "fp4"):
+                why = f"sends fp8 or fp4 elements: --mx-format {c.mx_format!r} is neither"
+            elif c.topology != "allgather":
+                why = (f"runs the all-gather exchange, which keeps its residual: it does not run "
+                       f"with --topology {c.topology} (no ps, sharded or two-stage form is built)")
+            elif c.sync_every > 1:
+                why = ("keeps its residual in the all-gather exchange: it does not run with "
+                       "--sync-every > 1")
+            elif c.select_best:
+                why = ("keeps its residual in the all-gather exchange: it does not run with "
+                       "--select-best")
+            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
+                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
+                       f"sign-compressed momentum (--compress sign)")
+            elif c.pull_compress is not None:
+                why = ("has no parameter-server form: --pull-compress belongs to --topology ps")
+            if why is not None:
+                raise ValueError("--compress mx " + why)
+            if c.error_feedback is None:  # block floating point rounds to nearest: biased
+                c.error_feedback = True
+        elif c.mx_format is not None:
+            raise ValueError("--mx-format belongs to --compress mx")
+        if c.pull_compress == "mx":
+            raise ValueError("--pull-compress mx: the mx codec has no parameter-server form")
         if c.compress == "vote":
             # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
             # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
@@ -485,7 +518,9 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # exchange
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
-      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote"])
+      choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote",
+               "mx"])
+    a("--mx-format", type=str, default=None, choices=["fp8", "fp4"])
     a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])
     a("--vote-exchange", type=str, default=None, choices=["allgather", "twostage"])
     a("--powersgd-rank", type=int, default=d.powersgd_rank)

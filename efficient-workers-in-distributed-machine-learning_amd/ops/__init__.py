@@ -547,6 +547,70 @@ def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=
                         _lrp(lr_tensor), sp, end, rotate, rot_key)
 
 
+def _check_mx_layout(dp, layout):
+    """The layout must be the one the plan gives (the kernels take the packing rule it checks
+    for granted); built once per plan and element width."""
+    if layout.kind != "mx":
+        raise ValueError(f"mx codec given a {layout.kind!r} layout")
+    known = dp.__dict__.setdefault("_mx_layouts", {})
+    if layout.bits not in known:
+        from ..compress.plan import Layout
+        known[layout.bits] = Layout.build("mx", dp.plan, layout.bits)
+    if layout != known[layout.bits]:
+        raise ValueError("mx layout does not match the bucket plan")
+
+
+def mx_encode(dp, grad, payload, layout, resid=None, soft=False):
+    """MXFP8 / MXFP4 of one bucket (``csrc/mx_codec.hip``; ``layout.bits`` 8 or 4): one E8M0 scale
+    byte per 32 elements and one FP8 E4M3 / FP4 E2M1 code per element of ``e = grad + resid``, with
+    ``resid`` (error feedback) overwritten by what was not sent.  One launch, no scratch; every
+    byte of the payload is written; bitwise ``compress/oracle.py encode_mx``.  ``soft``: the
+    software conversions instead of the hardware's (the same bytes: a cross-check for tests)."""
+    C = require()
+    _check_mx_layout(dp, layout)
+    ptrs, mask = grad_pointers(dp, grad)
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+    if resid is not None:
+        _check_bucket(dp, resid, "resid")
+    C.mx_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
+                dp.plan.length, dp.plan.num_tensors, dp.plan.num_chunks, layout.scales,
+                layout.codes, layout.bits, int(bool(soft)), _stream())
+
+
+def mx_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
+                    momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
+                    nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
+                    key_rank=0, lr_tensor=None, soft=False):
+    """``grad_out = grad_scale * sum over the rows of recv (rank order) of the decoded MX
+    payloads`` and / or the fused SGD step on ``param`` (``mom`` None: a step without momentum);
+    bitwise ``oracle.decode_sum``.  ``soft``: as in :func:`mx_encode`."""
+    C = require()
+    _check_mx_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 64:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}] with 1 <= nranks <= 64")
+    apply = param is not None
+    if apply:
+        _check_bucket(dp, param, "param")
+        if mom is not None:
+            _check_bucket(dp, mom, "mom")
+        elif momentum != 0.0 or nesterov:
+            raise ValueError("a momentum step needs the momentum buffer")
+    if grad_out is not None:
+        _check_bucket(dp, grad_out, "grad_out")
+    if not apply and grad_out is None:
+        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    _check_shadow(dp, shadow)
+    C.mx_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, dp.plan.length, _ptr(dp.chunks),
+                      dp.plan.num_chunks, layout.scales, layout.codes, layout.bits,
+                      int(bool(soft)), _ptr(param), _ptr(mom), _ptr(grad_out), _ptr(shadow), lr,
+                      momentum, dampening, weight_decay, grad_scale, int(nesterov), int(first),
+                      int(apply), _stream(), _keyp(key_state), key_seed & 0xFFFFFFFF,
+                      key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
+
+
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
                          weight_decay=0.0, param=None, slots=None):
     """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad

@@ -183,6 +183,32 @@ struct SignDecodeArgs {
   uint32_t rot_key;
 };
 
+// MXFP8 / MXFP4 block floating point with error feedback (mx_codec.hip): scales u8[length / 32] |
+// codes u8[length * bits / 8], length = the bucket's padded length.  soft != 0: the conversions in
+// software instead of v_cvt_scalef32_pk_* (the same bytes; the tests' cross-check)
+struct MxEncodeArgs {
+  const uintptr_t* grad_ptrs;
+  int n_grad_ptrs;
+  const uint32_t* bf16_mask;
+  int n_bf16_mask;
+  uintptr_t resid, chunks, payload, stream;  // resid 0: no error feedback
+  long long payload_bytes, length;
+  int num_tensors, num_chunks;
+  int scales_off, codes_off, bits, soft;
+};
+
+struct MxDecodeArgs {
+  uintptr_t recv, chunks, param, mom, grad_out, shadow, stream;  // mom 0: a step without momentum
+  long long stride, length;
+  int nranks, num_chunks;
+  int scales_off, codes_off, bits, soft;
+  float lr, momentum, dampening, weight_decay, grad_scale;
+  int nesterov, first, apply;
+  uintptr_t key_state;  // see TopkDecodeArgs
+  uint32_t key_seed, key_rank;
+  uintptr_t lr_ptr;
+};
+
 // PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /
 // dense / items are the plan's device tables; p / q the factor buffers of p_floats / q_floats
 // fp32.  The bucket views (grad, resid, param, mom, grad_out, shadow) hold bucket_len elements.
@@ -341,6 +367,8 @@ void ew_qsgd_decode_apply(const QsgdDecodeArgs& a);
 
 void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
+void ew_mx_encode(const MxEncodeArgs& a);
+void ew_mx_decode_apply(const MxDecodeArgs& a);
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
 void ew_sign_decode_lamb_stage(const SignLambArgs& a);
 void ew_lamb_onebit_apply(const SignLambArgs& a);

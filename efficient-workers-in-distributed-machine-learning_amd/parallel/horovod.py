@@ -154,6 +154,13 @@ class Compression:
         return Codec("sign", rotate=rotate)
 
     @staticmethod
+    def mx(fmt: str = "fp8"):
+        """OCP Microscaling block floating point: ``fp8`` (MXFP8, E4M3 elements) or ``fp4``
+        (MXFP4, E2M1), one power-of-two scale byte per 32 elements; the optimizer wrapper keeps
+        its error feedback."""
+        return Codec("mx", fmt=fmt)
+
+    @staticmethod
     def powersgd(rank: int = 4):
         """PowerSGD rank-r factors.  Its two dependent all-reduces do not fit this wrapper's
         exchange: ``DistributedOptimizer`` refuses it (use ``--compress powersgd`` on the
@@ -264,8 +271,9 @@ class _DistributedOptimizer:
                              "with --compress powersgd on the trainer (distributed_nn.py)")
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
-                                         # scaled sign is biased without its residual
-                                         error_feedback=codec.kind == "sign",
+                                         # scaled sign and round-to-nearest block floating
+                                         # point are biased without their residual
+                                         error_feedback=codec.kind in ("sign", "mx"),
                                          predivide=gradient_predivide_factor)
         self._synced = False
         self.exchange.begin()

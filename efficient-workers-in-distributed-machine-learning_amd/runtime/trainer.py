@@ -200,7 +200,8 @@ class Trainer:
             self.graph_plan = plan_graph_mode(
                 plan_world, self.comm.kind, cfg.compress,
                 sum(p.numel() for p in model.parameters() if p.requires_grad),
-                bits=cfg.qsgd_bits, overlap=cfg.overlap, bucket_bytes=bucket_bytes,
+                bits={"fp8": 8, "fp4": 4}[cfg.mx_format] if cfg.compress == "mx" else cfg.qsgd_bits,
+                overlap=cfg.overlap, bucket_bytes=bucket_bytes,
                 model=cfg.network, topk_ratio=cfg.topk_ratio,
                 dtype="fp32" if self.amp_kept_fp32 else
                 {"bf16": "bf16", "fp16": "fp16"}.get(cfg.amp, "fp32"),
@@ -237,6 +238,8 @@ class Trainer:
             ckw["aggregate"] = cfg.vote_aggregate
         if cfg.sign_rotate != "none":
             ckw["rotate"] = cfg.sign_rotate
+        if cfg.compress == "mx":
+            ckw["fmt"] = cfg.mx_format
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
         self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
