@@ -17,6 +17,12 @@
   * ``mx``    -- OCP Microscaling block floating point (``fmt``: ``fp8`` = MXFP8, E4M3 elements;
     ``fp4`` = MXFP4, E2M1): every 32 elements share one power-of-two scale byte; runs with error
     feedback on the all-gather exchange, one encode and one fused decode launch per bucket
+  * ``tern``  -- TernGrad (Wen et al. 2017): stochastic ternary codes {-1, 0, +1} at 2 bits per
+    element and one fp32 scaler per tensor, ``min(max|g|, clip * rms(g))`` (``clip``, default 2.5;
+    0 = no clipping, then unbiased).  ``rms`` is taken about zero, not about the mean, and every
+    rank's codes are decoded with that rank's own scaler (no scaler sharing).  Runs on the
+    all-gather exchange, error feedback optional (off by default); three encode launches and one
+    fused decode launch per bucket
   * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
     al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
     methods below)
@@ -37,7 +43,8 @@ from . import oracle
 from .plan import POWERSGD_RANKS, BucketPlan, Layout
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx")
+KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx",
+         "tern")
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
 MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
@@ -47,7 +54,7 @@ class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
                  rank: int = 4, aggregate: str = "majority", rotate: str = "none",
-                 fmt: str = None):
+                 fmt: str = None, clip: float = 2.5):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
@@ -71,8 +78,14 @@ class Codec:
                 raise ValueError(f"mx format must be one of {MX_FORMATS}, not {fmt!r}")
             bits = oracle.MX_NAMES[fmt]
         self.fmt = fmt
-        # the sign, vote and low-rank codecs have neither bits nor levels
-        if kind not in ("sign", "powersgd", "vote") and bits not in (4, 8):
+        clip = float(clip)
+        if clip != oracle.TERN_CLIP and kind != "tern":
+            raise ValueError("the clipping constant belongs to the tern codec")
+        if not clip >= 0.0:
+            raise ValueError("tern clip must be >= 0 (0: no clipping)")
+        self.clip = clip
+        # the sign, vote and low-rank codecs have neither bits nor levels; tern's are fixed
+        if kind not in ("sign", "powersgd", "vote", "tern") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -113,6 +126,8 @@ class Codec:
             return "vote1b"
         if self.kind == "mx":
             return "mx" + self.fmt
+        if self.kind == "tern":
+            return f"tern2b(c={self.clip:g})" if self.clip > 0 else "tern2b"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -193,7 +208,7 @@ class Codec:
         (``ops.topk_encode``), so no decode launch follows."""
         if dgc is not None and (resid is None or self.kind not in ("topk", "topk_qsgd")):
             raise ValueError("momentum correction needs a top-k codec and a residual")
-        if self.kind in ("sign", "mx") and apply is not None:
+        if self.kind in ("sign", "mx", "tern") and apply is not None:
             raise ValueError(f"the {self.kind} codec has no encode-side apply")
         if self.kind == "vote":
             raise ValueError("the vote codec sends the sign of Lion's update direction: "
@@ -211,6 +226,9 @@ class Codec:
                                 rot_key=self.rot_key(b))
             elif self.kind == "mx":
                 ops.mx_encode(self.dplans[b], grad, payload, lay, resid)
+            elif self.kind == "tern":
+                ops.tern_encode(self.dplans[b], grad, payload, lay, self.clip, key, resid,
+                                key_tensor)
             elif self.kind == "qsgd":
                 ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
                                 resid, key_tensor)
@@ -226,6 +244,8 @@ class Codec:
             out = oracle.encode_sign(grad, plan, lay, resid, self.rot_key(b))
         elif self.kind == "mx":
             out = oracle.encode_mx(grad, plan, lay, resid)
+        elif self.kind == "tern":
+            out = oracle.encode_tern(grad, plan, lay, self.clip, key, resid)
         elif self.kind == "qsgd":
             out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
         else:
@@ -613,6 +633,9 @@ class Codec:
             if self.kind == "mx":
                 ops.mx_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
                 return
+            if self.kind == "tern":
+                ops.tern_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
+                return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, grad_out=out, grad_scale=scale)
             return
@@ -640,6 +663,9 @@ class Codec:
                 return
             if self.kind == "mx":
                 ops.mx_decode_apply(self.dplans[b], recv, lay, **kw)
+                return
+            if self.kind == "tern":
+                ops.tern_decode_apply(self.dplans[b], recv, lay, **kw)
                 return
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(self.dplans[b], recv, lay, self.levels, **kw)

@@ -30,6 +30,11 @@ Reference semantics being reproduced:
   * Block floating point (no reference counterpart; OCP Microscaling v1.0, Rouhani et al. 2023):
     ``encode_mx`` -- one power-of-two scale byte per 32 elements, FP8 E4M3 or FP4 E2M1 elements
     rounded to nearest even and saturated, with error feedback; bitwise the kernels'.
+  * TernGrad (no reference counterpart: ``SURVEY.md`` section 4 records an attempt that did not
+    build; Wen et al., NeurIPS 2017): ``encode_tern`` -- stochastic ternary codes at 2 bits per
+    element, one fp32 scaler per tensor clipped at ``clip`` times the tensor's root mean square
+    (about zero, not about the mean); the sum of squares runs in the kernel's order
+    (``_tern_sumsq``), so scalers, codes and residuals are bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -679,6 +684,137 @@ def _mx_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Te
 
 
 # ---------------------------------------------------------------------------------------------
+# TernGrad (Wen et al., NeurIPS 2017): ternary codes, one clipped fp32 scaler per tensor
+# ---------------------------------------------------------------------------------------------
+TERN_CLIP = 2.5  # the paper's clipping constant c: |g| is capped at c * sigma per layer
+
+
+def _tern_sumsq(x: torch.Tensor) -> float:
+    """The fp32 sum of ``x * x`` over one tensor in the order of ``ops/csrc/tern_codec.hip``,
+    every product and every add rounded to fp32:
+
+    * per 8192-chunk the order of :func:`_sign_chunk_sums` (``k_tern_stats``; positions past the
+      tensor's end add +0);
+    * across the tensor's chunks (``k_tern_scale``, one block per tensor) thread t (0..255) adds,
+      from 0, the chunk partials ``t, t + 256, t + 512, ...``; then the same wave shuffle tree
+      over the 256 threads and ``(((0 + w0) + w1) + w2) + w3`` over the four waves.  A tensor of
+      up to 256 chunks therefore adds its partials by the tree alone."""
+    n = x.numel()
+    nch = (n + CHUNK - 1) // CHUNK
+    rows = torch.zeros(nch * CHUNK, dtype=torch.float32, device=x.device)
+    rows[:n] = x * x
+    part = _sign_chunk_sums(rows.reshape(nch, CHUNK))
+    u = (nch + _SIGN_THREADS - 1) // _SIGN_THREADS
+    p = torch.zeros(u * _SIGN_THREADS, dtype=torch.float32, device=x.device)
+    p[:nch] = part
+    p = p.reshape(u, _SIGN_THREADS)
+    s = torch.zeros(_SIGN_THREADS, dtype=torch.float32, device=x.device)
+    for k in range(u):
+        s = s + p[k]
+    w = s.reshape(_SIGN_THREADS // 64, 64)
+    d = 32
+    while d:
+        w = w[:, :d] + w[:, d:2 * d]
+        d >>= 1
+    tot = torch.zeros((), dtype=torch.float32, device=x.device)
+    for i in range(w.shape[0]):
+        tot = tot + w[i, 0]
+    return float(tot)
+
+
+def tern_scale(x: torch.Tensor, clip: float) -> float:
+    """The clipped scaler of one tensor: ``min(max|x|, clip * rms)`` with ``rms = sqrtf(sumsq /
+    n)`` -- :func:`_tern_sumsq`, one fp32 divide, one correctly rounded fp32 square root, one fp32
+    product, ``fminf``; ``clip == 0``: ``max|x|``."""
+    f32 = np.float32
+    n = x.numel()
+    if n == 0:
+        return 0.0
+    absmax = f32(float(x.abs().max()))
+    if not clip > 0:
+        return float(absmax)
+    rms = np.sqrt(f32(_tern_sumsq(x)) / f32(n))
+    return float(np.fmin(absmax, f32(clip) * rms))
+
+
+def _pack2(codes: torch.Tensor) -> torch.Tensor:
+    """int32 codes in {-1, 0, 1} (a multiple of 16 of them) -> uint32 words as int32: element i is
+    bits ``2 (i & 15) .. + 1`` of word ``i >> 4``, 2-bit two's complement (0, 1, 3 = -1)."""
+    sh = 2 * torch.arange(16, dtype=torch.int64, device=codes.device)
+    words = ((codes.to(torch.int64) & 3).reshape(-1, 16) << sh).sum(-1)
+    words = ((words + (1 << 31)) % (1 << 32)) - (1 << 31)
+    return words.to(torch.int32)
+
+
+def _unpack2(words: torch.Tensor) -> torch.Tensor:
+    sh = 2 * torch.arange(16, dtype=torch.int64, device=words.device)
+    c = ((words.to(torch.int64)[:, None] >> sh) & 3).flatten()
+    return ((c ^ 2) - 2).to(torch.int32)
+
+
+def encode_tern(g: torch.Tensor, plan: BucketPlan, layout: Layout, clip: float, key: int,
+                residual: torch.Tensor = None) -> torch.Tensor:
+    """TernGrad of one bucket -> uint8 payload (``scales f32[T] | codes u32[D' / 16]``, 2 bits per
+    element; ``D' = plan.total_codes``, pad codes 0).
+
+    Per tensor, with ``x = g`` (``g + residual`` under error feedback): ``scale`` =
+    :func:`tern_scale` ``(x, clip)``, the codes are ``quantize(x, scale, 1, gidx, key)`` -- QSGD's
+    stochastic rule at one level on QSGD's streams (``gidx = bucket_offset + off + i``): ``|x| /
+    scale`` is the probability of a non-zero code, capped at 1, so an element above the clipped
+    scaler codes ``sign(x)`` -- and the decoded value is ``code * dequant_step(1, scale)``.  A zero
+    scale gives zero codes.  ``residual = x - decoded`` with the unclipped ``x``: what clipping
+    removes is fed back.  Without clipping (``clip == 0``) the codec is unbiased and equals
+    ``encode_qsgd(levels=1, norm="max")`` code for code.
+
+    Two deliberate deviations from the paper.  ``rms`` is the second moment about zero, not the
+    standard deviation about the mean: the paper models a layer's gradient as a zero-mean
+    Gaussian, and the centred form would give sigma = 0 (a zeroed tensor, every step) for a
+    one-element or constant tensor and cancels catastrophically in fp32.  And every rank sends
+    its own scaler, which the all-gather decode applies to that rank's codes: the paper's scaler
+    sharing (for summing ternaries on a parameter server) is not implemented.
+
+    Inputs are taken to be finite; a non-finite gradient behaves as in the QSGD codec (the
+    integer maximum keeps a NaN or an inf as the scale and the decoded values are not finite)."""
+    if layout.kind != "tern":
+        raise ValueError(f"encode_tern given a {layout.kind!r} layout")
+    g = g.to(torch.float32)
+    if residual is not None:
+        g = g + residual
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=g.device)
+    T = plan.num_tensors
+    scales = _section(out, layout.scales, T, torch.float32)
+    codes = torch.zeros(plan.total_codes, dtype=torch.int32, device=g.device)
+    sent = torch.zeros_like(g) if residual is not None else None
+    for t in range(T):
+        off, n, d0 = plan.offsets[t], plan.numels[t], plan.tensor_code0[t]
+        x = g[off:off + n]
+        scale = tern_scale(x, clip)
+        scales[t] = scale
+        gidx = plan.bucket_offset + off + torch.arange(n, device=g.device)
+        q = quantize(x, scale, 1, gidx, key)
+        codes[d0:d0 + n] = q
+        if sent is not None:
+            sent[off:off + n] = q.to(torch.float32) * dequant_step(1, scale)
+    _section(out, layout.codes, plan.total_codes // 16, torch.int32).copy_(_pack2(codes))
+    if residual is not None:
+        residual.copy_(g - sent)
+    return out
+
+
+def _tern_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.Tensor:
+    """One payload decoded on the tensors' positions (0 between them): fp32 ``[plan.length]``."""
+    T = plan.num_tensors
+    scales = _section(pay, layout.scales, T, torch.float32)
+    codes = _unpack2(_section(pay, layout.codes, plan.total_codes // 16, torch.int32)).to(
+        torch.float32)
+    out = torch.zeros(plan.length, dtype=torch.float32, device=pay.device)
+    for t in range(T):
+        off, n, d0 = plan.offsets[t], plan.numels[t], plan.tensor_code0[t]
+        out[off:off + n] = codes[d0:d0 + n] * dequant_step(1, float(scales[t]))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # decode: sum over ranks (in rank order) of the dequantised payloads, times ``scale``
 # ---------------------------------------------------------------------------------------------
 def _decoded_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int):
@@ -735,6 +871,8 @@ def decode_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int
             acc += _sign_decoded(recv[r], plan, layout)
         elif layout.kind == "mx":
             acc += _mx_decoded(recv[r], plan, layout)
+        elif layout.kind == "tern":
+            acc += _tern_decoded(recv[r], plan, layout)
         else:
             acc += _dense_decoded(recv[r], plan, layout, levels)
     return acc * torch.tensor(scale, dtype=torch.float32)

@@ -29,6 +29,9 @@ exchange is a fixed-size all-gather with no size handshake):
 ``mx``       : scales u8[L / 32] | codes u8[L] (bits=8, FP8 E4M3) or nibbles u8[L / 2] (bits=4, FP4
                E2M1; the low nibble is the even element).  L = the bucket's padded length; element
                i of the bucket is code i and its E8M0 scale is byte i >> 5; pads are written as 0
+``tern``     : scales f32[T] | codes u32[D' / 16]  (TernGrad; D' as for ``qsgd``, so every tensor
+               starts on a word; element i of a tensor is bits 2 (i & 15) .. 2 (i & 15) + 1 of word
+               code0 / 16 + (i >> 4); 0 = 0, 1 = +1, 3 = -1, 2 is never written, pad codes are 0)
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -237,6 +240,11 @@ class Layout:
             off = _align(L // MX_BLOCK)
             counts = idx = codes = off
             off += L * bits // 8
+        elif kind == "tern":
+            # one scaler per tensor, then 2-bit codes, 16 to a word (`codes` is their byte offset)
+            bits = 2
+            counts = idx = codes = off
+            off += plan.total_codes // 4
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)

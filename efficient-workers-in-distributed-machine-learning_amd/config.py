@@ -58,7 +58,7 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx
+    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     # --compress sign: none | hadamard (the signs of a randomised Hadamard rotation of every chunk,
@@ -67,6 +67,9 @@ class Config:
     # --compress mx (OCP Microscaling block floating point, one power-of-two scale byte per 32
     # elements): fp8 (MXFP8, E4M3 elements) | fp4 (MXFP4, E2M1) (None: fp8)
     mx_format: Optional[str] = None
+    # --compress tern (TernGrad: ternary codes, one scaler per tensor): the scaler is min(max|g|,
+    # tern_clip * rms(g)); 0 = no clipping (None: 2.5, the paper's constant)
+    tern_clip: Optional[float] = None
     topk_ratio: float = 0.01
     topk_dense_below: int = 0  # tensors of <= N elements go whole (k = numel) through top-k codecs
     qsgd_levels: int = 127
@@ -253,6 +256,37 @@ class Config:
             raise ValueError("--mx-format belongs to --compress mx")
         if c.pull_compress == "mx":
             raise ValueError("--pull-compress mx: the mx codec has no parameter-server form")
+        if c.compress == "tern":
+            # TernGrad (compress/oracle.py encode_tern): the all-gather exchange's encode and fused
+            # decode, every rank's codes decoded with its own scaler; nothing else has a tern form
+            if c.tern_clip is None:
+                c.tern_clip = 2.5
+            why = None
+            if not float(c.tern_clip) >= 0.0:
+                why = f"clips at a multiple of the rms: --tern-clip {c.tern_clip!r} must be >= 0"
+            elif c.topology != "allgather":
+                why = (f"decodes every rank's codes with that rank's scaler in the all-gather "
+                       f"exchange: it does not run with --topology {c.topology} (no ps, sharded or "
+                       f"two-stage form is built)")
+            elif c.sync_every > 1:
+                why = ("is built into the all-gather exchange's every-step path: it does not run "
+                       "with --sync-every > 1")
+            elif c.select_best:
+                why = ("is built into the all-gather exchange's every-step path: it does not run "
+                       "with --select-best")
+            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
+                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
+                       f"sign-compressed momentum (--compress sign)")
+            elif c.pull_compress is not None:
+                why = ("has no parameter-server form: --pull-compress belongs to --topology ps")
+            if why is not None:
+                raise ValueError("--compress tern " + why)
+            if c.error_feedback is None:  # unbiased apart from clipping; the paper runs without
+                c.error_feedback = False
+        elif c.tern_clip is not None:
+            raise ValueError("--tern-clip belongs to --compress tern")
+        if c.pull_compress == "tern":
+            raise ValueError("--pull-compress tern: the tern codec has no parameter-server form")
         if c.compress == "vote":
             # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
             # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
@@ -519,8 +553,9 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote",
-               "mx"])
+               "mx", "tern"])
     a("--mx-format", type=str, default=None, choices=["fp8", "fp4"])
+    a("--tern-clip", type=float, default=None)
     a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])
     a("--vote-exchange", type=str, default=None, choices=["allgather", "twostage"])
     a("--powersgd-rank", type=int, default=d.powersgd_rank)

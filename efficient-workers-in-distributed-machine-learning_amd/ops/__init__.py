@@ -611,6 +611,77 @@ def mx_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.
                       key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
 
 
+def _check_tern_layout(dp, layout):
+    """The layout must be the one the plan gives (the kernels derive every code word's address
+    from the plan's tables); built once per plan."""
+    if layout.kind != "tern":
+        raise ValueError(f"tern codec given a {layout.kind!r} layout")
+    known = dp.__dict__.get("_tern_layout")
+    if known is None:
+        from ..compress.plan import Layout
+        known = dp.__dict__["_tern_layout"] = Layout.build("tern", dp.plan)
+    if layout != known:
+        raise ValueError("tern layout does not match the bucket plan")
+
+
+def tern_encode(dp: DevicePlan, grad, payload, layout, clip: float, key: int, resid=None,
+                key_tensor=None):
+    """TernGrad of one bucket (``csrc/tern_codec.hip``): one fp32 scaler per tensor, ``min(max|x|,
+    clip * rms(x))`` (``clip == 0``: ``max|x|``), and one stochastic 2-bit code per element of ``x =
+    grad + resid``, with ``resid`` (error feedback) overwritten by what was not sent.  ``key``: the
+    step's stream key (``key_tensor``: read from device memory instead, for captured graphs).
+    Three launches; every byte of the payload is written; bitwise ``compress/oracle.py
+    encode_tern``."""
+    C = require()
+    _check_tern_layout(dp, layout)
+    ptrs, mask = grad_pointers(dp, grad)
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+    if resid is not None:
+        _check_bucket(dp, resid, "resid")
+    if not float(clip) >= 0.0:
+        raise ValueError("tern clip must be >= 0")
+    C.tern_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(dp.tensors), _ptr(dp.scratch),
+                  _ptr(payload), layout.nbytes, dp.plan.total_codes, dp.plan.num_tensors,
+                  dp.plan.num_chunks, layout.scales, layout.codes, float(clip),
+                  key & 0xFFFFFFFF, dp.plan.bucket_offset & 0xFFFFFFFF, _keyp(key_tensor),
+                  _stream())
+
+
+def tern_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
+                      momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
+                      nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
+                      key_rank=0, lr_tensor=None):
+    """``grad_out = grad_scale * sum over the rows of recv (rank order) of code * that row's
+    scaler`` and / or the fused SGD step on ``param`` (``mom`` None: a step without momentum);
+    bitwise ``oracle.decode_sum``."""
+    C = require()
+    _check_tern_layout(dp, layout)
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 64:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}] with 1 <= nranks <= 64")
+    apply = param is not None
+    if apply:
+        _check_bucket(dp, param, "param")
+        if mom is not None:
+            _check_bucket(dp, mom, "mom")
+        elif momentum != 0.0 or nesterov:
+            raise ValueError("a momentum step needs the momentum buffer")
+    if grad_out is not None:
+        _check_bucket(dp, grad_out, "grad_out")
+    if not apply and grad_out is None:
+        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    _check_shadow(dp, shadow)
+    C.tern_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, dp.plan.total_codes,
+                        _ptr(dp.chunks), _ptr(dp.tensors), dp.plan.num_tensors,
+                        dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param), _ptr(mom),
+                        _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
+                        grad_scale, int(nesterov), int(first), int(apply), _stream(),
+                        _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
+                        _lrp(lr_tensor))
+
+
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
                          weight_decay=0.0, param=None, slots=None):
     """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad

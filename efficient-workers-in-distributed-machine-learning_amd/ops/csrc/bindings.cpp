@@ -475,6 +475,73 @@ PYBIND11_MODULE(_C, m) {
           ew_mx_decode_apply(a);
         });
 
+  m.def("tern_encode",
+        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
+           uintptr_t tensors, uintptr_t scratch, uintptr_t payload, long long payload_bytes,
+           long long total_codes, int T, int C, int scales_off, int codes_off, float clip,
+           uint32_t key, uint32_t bucket_offset, uintptr_t key_ptr, uintptr_t stream) {
+          TernEncodeArgs a{};
+          a.grad_ptrs = grads.data();
+          a.n_grad_ptrs = (int)grads.size();
+          a.bf16_mask = mask.data();
+          a.n_bf16_mask = (int)mask.size();
+          a.resid = resid;
+          a.chunks = chunks;
+          a.tensors = tensors;
+          a.scratch = scratch;
+          a.payload = payload;
+          a.stream = stream;
+          a.payload_bytes = payload_bytes;
+          a.total_codes = total_codes;
+          a.num_tensors = T;
+          a.num_chunks = C;
+          a.scales_off = scales_off;
+          a.codes_off = codes_off;
+          a.clip = clip;
+          a.key = key;
+          a.bucket_offset = bucket_offset;
+          a.key_ptr = key_ptr;
+          ew_tern_encode(a);
+        });
+
+  m.def("tern_decode_apply",
+        [](uintptr_t recv, int nranks, long long stride, long long total_codes, uintptr_t chunks,
+           uintptr_t tensors, int T, int C, int scales_off, int codes_off, uintptr_t param,
+           uintptr_t mom, uintptr_t grad_out, uintptr_t shadow, float lr, float momentum,
+           float dampening, float weight_decay, float grad_scale, int nesterov, int first,
+           int apply, uintptr_t stream, uintptr_t key_state, uint32_t key_seed,
+           uint32_t key_rank, uintptr_t lr_ptr) {
+          TernDecodeArgs a{};
+          a.recv = recv;
+          a.chunks = chunks;
+          a.tensors = tensors;
+          a.param = param;
+          a.mom = mom;
+          a.grad_out = grad_out;
+          a.shadow = shadow;
+          a.stream = stream;
+          a.stride = stride;
+          a.total_codes = total_codes;
+          a.nranks = nranks;
+          a.num_tensors = T;
+          a.num_chunks = C;
+          a.scales_off = scales_off;
+          a.codes_off = codes_off;
+          a.lr = lr;
+          a.momentum = momentum;
+          a.dampening = dampening;
+          a.weight_decay = weight_decay;
+          a.grad_scale = grad_scale;
+          a.nesterov = nesterov;
+          a.first = first;
+          a.apply = apply;
+          a.key_state = key_state;
+          a.key_seed = key_seed;
+          a.key_rank = key_rank;
+          a.lr_ptr = lr_ptr;
+          ew_tern_decode_apply(a);
+        });
+
   // PowerSGD (powersgd.hip): op 0 = project, 1 = orth, 2 = backproject, 3 = decode_apply
   m.def("psgd",
         [](int op, int rank, uintptr_t mats, int num_mats, uintptr_t dense, int num_dense,

@@ -209,6 +209,35 @@ struct MxDecodeArgs {
   uintptr_t lr_ptr;
 };
 
+// TernGrad ternary codes with a clipped per-tensor scaler (tern_codec.hip): scales f32[T] | codes
+// u32[total_codes / 16], 2 bits per element.  scratch: ew_qsgd_scratch_bytes(T, C) bytes.  clip:
+// scale = min(max|x|, clip * rms(x)); 0 = no clipping
+struct TernEncodeArgs {
+  const uintptr_t* grad_ptrs;
+  int n_grad_ptrs;
+  const uint32_t* bf16_mask;
+  int n_bf16_mask;
+  uintptr_t resid, chunks, tensors, scratch, payload, stream;  // resid 0: no error feedback
+  long long payload_bytes, total_codes;
+  int num_tensors, num_chunks;
+  int scales_off, codes_off;
+  float clip;
+  uint32_t key, bucket_offset;
+  uintptr_t key_ptr;  // nullable device uint32 key (overrides key)
+};
+
+struct TernDecodeArgs {
+  uintptr_t recv, chunks, tensors, param, mom, grad_out, shadow, stream;  // mom 0: no momentum
+  long long stride, total_codes;
+  int nranks, num_tensors, num_chunks;
+  int scales_off, codes_off;
+  float lr, momentum, dampening, weight_decay, grad_scale;
+  int nesterov, first, apply;
+  uintptr_t key_state;  // see TopkDecodeArgs
+  uint32_t key_seed, key_rank;
+  uintptr_t lr_ptr;
+};
+
 // PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /
 // dense / items are the plan's device tables; p / q the factor buffers of p_floats / q_floats
 // fp32.  The bucket views (grad, resid, param, mom, grad_out, shadow) hold bucket_len elements.
@@ -369,6 +398,8 @@ void ew_sign_encode(const SignEncodeArgs& a);
 void ew_sign_decode_apply(const SignDecodeArgs& a);
 void ew_mx_encode(const MxEncodeArgs& a);
 void ew_mx_decode_apply(const MxDecodeArgs& a);
+void ew_tern_encode(const TernEncodeArgs& a);
+void ew_tern_decode_apply(const TernDecodeArgs& a);
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
 void ew_sign_decode_lamb_stage(const SignLambArgs& a);
 void ew_lamb_onebit_apply(const SignLambArgs& a);

@@ -823,7 +823,7 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
                 "reason": "PowerSGD: collectives between two graphs"}
     # mx: one code of `bits` bits per element and one scale byte per 32 (33/32 and 17/32 bytes)
     per_elem ={"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
-                "sign": 1.0 / 8.0, "vote": 1.0 / 8.0,
+                "sign": 1.0 / 8.0, "vote": 1.0 / 8.0, "tern": 0.25,
                 "mx": bits / 8.0 + 1.0 / 32.0}.get(codec_kind)
     payload = grad_numel * (per_elem or 0.0)
     # top-k payload per rank (estimate): k entries of one code byte (4-bit: half) + a 2-byte index

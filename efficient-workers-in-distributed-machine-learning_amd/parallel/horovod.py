@@ -161,6 +161,13 @@ class Compression:
         return Codec("mx", fmt=fmt)
 
     @staticmethod
+    def tern(clip: float = 2.5):
+        """TernGrad: stochastic ternary codes at 2 bits per element, one scaler per tensor clipped
+        at ``clip`` times the tensor's root mean square (0: no clipping).  Unbiased apart from the
+        clipping: the optimizer wrapper runs it without error feedback, as the paper does."""
+        return Codec("tern", clip=clip)
+
+    @staticmethod
     def powersgd(rank: int = 4):
         """PowerSGD rank-r factors.  Its two dependent all-reduces do not fit this wrapper's
         exchange: ``DistributedOptimizer`` refuses it (use ``--compress powersgd`` on the

@@ -240,6 +240,8 @@ class Trainer:
             ckw["rotate"] = cfg.sign_rotate
         if cfg.compress == "mx":
             ckw["fmt"] = cfg.mx_format
+        if cfg.compress == "tern":
+            ckw["clip"] = cfg.tern_clip
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
         self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
