@@ -406,14 +406,9 @@ class Codec:
         ts = self.ts[b]
         if self._ts_kernel(rows):
             sl = self.ts_dev[b]
-            kw = dict(grad_out=grad_out, grad_scale=1.0, key_state=key_state, key_seed=self.seed,
-                      key_rank=rank, slots=sl)
-            if param is not None:
-                kw.update(param=param, mom=mom, lr=hp["lr"], momentum=hp["momentum"],
-                          dampening=hp["dampening"], weight_decay=hp["weight_decay"],
-                          nesterov=hp["nesterov"], first=first, shadow=shadow,
-                          lr_tensor=hp.get("lr_t"))
-            ops.sign_decode_apply(sl, rows, None, **kw)
+            ops.sign_decode_apply(sl, rows, None, grad_out=grad_out, grad_scale=1.0,
+                                  key_state=key_state, key_seed=self.seed, key_rank=rank,
+                                  slots=sl, **_sgd_kw(hp, first, shadow, param, mom))
             return
         g = self._ts_decoded(b, rows)
         if grad_out is not None:
@@ -552,13 +547,8 @@ class Codec:
         if param is not None and mom is None and hp["momentum"] != 0:
             raise ValueError("a momentum step needs the momentum buffer")
         if self._ts_kernel(p):
-            kw = dict(grad_out=grad_out)
-            if param is not None:
-                kw.update(param=param, mom=mom, lr=hp["lr"], momentum=hp["momentum"],
-                          dampening=hp["dampening"], weight_decay=hp["weight_decay"],
-                          nesterov=hp["nesterov"], first=first, shadow=shadow,
-                          lr_tensor=hp.get("lr_t"))
-            ops.psgd_decode_apply(self.lr_dev[b], resid, p, q, q_out, inv_n, **kw)
+            ops.psgd_decode_apply(self.lr_dev[b], resid, p, q, q_out, inv_n, grad_out=grad_out,
+                                  **_sgd_kw(hp, first, shadow, param, mom))
             return
         lrp = self.lr_plans[b]
         qa = oracle.powersgd_reconstruct_apply(resid, p, q, lrp, inv_n, param, mom, hp, first,
@@ -619,6 +609,19 @@ class Codec:
         hp["ratio"].copy_(ratios)
         fac[t & 1].copy_(factors)
 
+    def _gpu_decode(self, b: int, recv: torch.Tensor, **kw):
+        """The codec's ``ops.*_decode_apply`` on bucket ``b``; ``kw``: what to do with the mean."""
+        dp, lay = self.dplans[b], self.layouts[b]
+        if self.kind == "sign":
+            ops.sign_decode_apply(dp, recv, lay, rot_key=self.rot_key(b), **kw)
+        elif self.kind == "mx":
+            ops.mx_decode_apply(dp, recv, lay, **kw)
+        elif self.kind == "tern":
+            ops.tern_decode_apply(dp, recv, lay, **kw)
+        else:
+            fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
+            fn(dp, recv, lay, self.levels, **kw)
+
     def decode(self, b: int, recv: torch.Tensor, out: torch.Tensor, scale: float):
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""
         if self.kind == "vote":
@@ -626,18 +629,7 @@ class Codec:
                              "(decode_apply_vote steps the parameters)")
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
-            if self.kind == "sign":
-                ops.sign_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale,
-                                      rot_key=self.rot_key(b))
-                return
-            if self.kind == "mx":
-                ops.mx_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
-                return
-            if self.kind == "tern":
-                ops.tern_decode_apply(self.dplans[b], recv, lay, grad_out=out, grad_scale=scale)
-                return
-            fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
-            fn(self.dplans[b], recv, lay, self.levels, grad_out=out, grad_scale=scale)
+            self._gpu_decode(b, recv, grad_out=out, grad_scale=scale)
             return
         out[:plan.length].copy_(oracle.decode_sum(recv, plan, lay, self.levels, scale,
                                                   self.rot_key(b)))
@@ -653,22 +645,9 @@ class Codec:
             raise ValueError("a momentum step needs the momentum buffer")
         plan, lay = self.plans[b], self.layouts[b]
         if recv.is_cuda and not _FORCE_ORACLE:
-            kw = dict(param=param, mom=mom, grad_out=grad_out, lr=hp["lr"],
-                      momentum=hp["momentum"], dampening=hp["dampening"],
-                      weight_decay=hp["weight_decay"], grad_scale=scale, nesterov=hp["nesterov"],
-                      first=first, shadow=shadow, key_state=key_state, key_seed=self.seed,
-                      key_rank=rank, lr_tensor=hp.get("lr_t"))
-            if self.kind == "sign":
-                ops.sign_decode_apply(self.dplans[b], recv, lay, rot_key=self.rot_key(b), **kw)
-                return
-            if self.kind == "mx":
-                ops.mx_decode_apply(self.dplans[b], recv, lay, **kw)
-                return
-            if self.kind == "tern":
-                ops.tern_decode_apply(self.dplans[b], recv, lay, **kw)
-                return
-            fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
-            fn(self.dplans[b], recv, lay, self.levels, **kw)
+            self._gpu_decode(b, recv, grad_out=grad_out, grad_scale=scale, key_state=key_state,
+                             key_seed=self.seed, key_rank=rank,
+                             **_sgd_kw(hp, first, shadow, param, mom))
             return
         g = oracle.decode_sum(recv, plan, lay, self.levels, scale, self.rot_key(b))
         if grad_out is not None:
@@ -678,6 +657,16 @@ class Codec:
                              g[off:off + n], hp["lr"],
                              hp["momentum"], hp["dampening"], hp["weight_decay"],
                              hp["nesterov"], first)
+
+
+def _sgd_kw(hp: dict, first: bool, shadow, param, mom) -> dict:
+    """The fused SGD step's keywords of ``ops.*_decode_apply`` from ``FlatSGD.hparams()``
+    (``param`` None: no step, the decoded mean goes to ``grad_out`` only)."""
+    if param is None:
+        return {}
+    return dict(param=param, mom=mom, lr=hp["lr"], momentum=hp["momentum"],
+                dampening=hp["dampening"], weight_decay=hp["weight_decay"],
+                nesterov=hp["nesterov"], first=first, shadow=shadow, lr_tensor=hp.get("lr_t"))
 
 
 def make_codec(kind: str = "topk_qsgd", **kw) -> Codec:

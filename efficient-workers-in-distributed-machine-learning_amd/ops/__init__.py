@@ -207,6 +207,45 @@ def _keyp(key_tensor):
     return key_tensor.data_ptr()
 
 
+def _encode_dst(payload, layout):
+    """An encode's destination: a uint8 buffer of at least the layout's bytes."""
+    _check(payload, torch.uint8, "payload")
+    if payload.numel() < layout.nbytes:
+        raise ValueError("payload too small")
+
+
+def _recv_rows(recv, layout) -> int:
+    """A decode's source: the gathered ``[nranks, layout.nbytes]`` payloads; returns nranks."""
+    _check(recv, torch.uint8, "recv")
+    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 64:
+        raise ValueError(f"recv must be [nranks, {layout.nbytes}] with 1 <= nranks <= 64")
+    return recv.shape[0]
+
+
+def _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay, grad_scale,
+          nesterov, first, key_state, key_seed, key_rank, lr_tensor, need_mom=False):
+    """The receive-side step every ``*_decode_apply`` ends in, checked against the bucket of
+    ``dp`` and packed for the extension: the decoded mean to ``grad_out`` and / or the fused SGD
+    step on ``param`` (``mom`` None: a step without momentum, unless the kernel reads the buffer
+    regardless: ``need_mom``)."""
+    apply = param is not None
+    if apply:
+        _check_bucket(dp, param, "param")
+        if mom is not None:
+            _check_bucket(dp, mom, "mom")
+        elif need_mom or momentum != 0.0 or nesterov:
+            raise ValueError("a momentum step needs the momentum buffer")
+    if grad_out is not None:
+        _check_bucket(dp, grad_out, "grad_out")
+    if not apply and grad_out is None:
+        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    _check_shadow(dp, shadow)
+    return require().StepArgs(_ptr(param), _ptr(mom) if apply else 0, _ptr(grad_out),
+                              _ptr(shadow), lr, momentum, dampening, weight_decay, grad_scale,
+                              int(nesterov), int(first), int(apply), _keyp(key_state),
+                              key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
+
+
 def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
                 resid=None, key_tensor=None, dgc=None, apply=None):
     """``dgc``: momentum-corrected error feedback, ``{velocity, momentum, dampening, nesterov,
@@ -219,9 +258,7 @@ def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, k
     the next step; bitwise the decode's result (tests/kernels/test_hip_codecs.py)."""
     C = require()
     ptrs, mask = grad_pointers(dp, grad)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    _encode_dst(payload, layout)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
     if layout.kind == "topk":
@@ -320,40 +357,20 @@ def topk_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
                       grad_scale=1.0, nesterov=False, first=False, shadow=None,
                       key_state=None, key_seed=0, key_rank=0, lr_tensor=None):
     C = require()
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
-    if recv.shape[0] > 64:
-        raise ValueError("at most 64 ranks per decode")
-    apply = param is not None
-    if apply:
-        _check_bucket(dp, param, "param")
-        if mom is not None:
-            _check_bucket(dp, mom, "mom")
-        elif momentum != 0.0 or nesterov:
-            raise ValueError("a momentum step needs the momentum buffer")
-    if grad_out is not None:
-        _check_bucket(dp, grad_out, "grad_out")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
-    _check_shadow(dp, shadow)
+    nranks = _recv_rows(recv, layout)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
     vk = VK_F32 if layout.kind == "topk" else (VK_Q8 if layout.bits == 8 else VK_Q4)
-    C.topk_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
-                        _ptr(dp.tensors), dp.plan.num_chunks, layout.scales, layout.counts,
-                        layout.idx, layout.codes, vk, float(1.0 / levels), _ptr(param), _ptr(mom),
-                        _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
-                        grad_scale, int(nesterov), int(first), int(apply), _stream(),
-                        _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
-                        layout.bitmap, _lrp(lr_tensor))
+    C.topk_decode_apply(_ptr(recv), nranks, layout.nbytes, _ptr(dp.chunks), _ptr(dp.tensors),
+                        dp.plan.num_chunks, layout.scales, layout.counts, layout.idx,
+                        layout.codes, vk, float(1.0 / levels), step, _stream(), layout.bitmap)
 
 
 def qsgd_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
                 resid=None, key_tensor=None):
     C = require()
     ptrs, mask = grad_pointers(dp, grad)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    _encode_dst(payload, layout)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
     if not (1 <= levels <= (127 if layout.bits == 8 else 7)):
@@ -370,24 +387,13 @@ def qsgd_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
                       grad_scale=1.0, nesterov=False, first=False, shadow=None,
                       key_state=None, key_seed=0, key_rank=0, lr_tensor=None):
     C = require()
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
-    apply = param is not None
-    if apply:
-        _check_bucket(dp, param, "param")
-        _check_bucket(dp, mom, "mom")
-    if grad_out is not None:
-        _check_bucket(dp, grad_out, "grad_out")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
-    _check_shadow(dp, shadow)
-    C.qsgd_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, _ptr(dp.chunks),
-                        _ptr(dp.tensors), dp.plan.num_chunks, layout.scales, layout.codes,
-                        layout.bits, float(1.0 / levels), _ptr(param), _ptr(mom), _ptr(grad_out),
-                        _ptr(shadow), lr, momentum, dampening, weight_decay, grad_scale,
-                        int(nesterov), int(first), int(apply), _stream(), _keyp(key_state),
-                        key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
+    nranks = _recv_rows(recv, layout)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor,
+                 need_mom=True)  # k_qsgd_decode_apply reads the buffer whenever it applies
+    C.qsgd_decode_apply(_ptr(recv), nranks, layout.nbytes, _ptr(dp.chunks), _ptr(dp.tensors),
+                        dp.plan.num_chunks, layout.scales, layout.codes, layout.bits,
+                        float(1.0 / levels), step, _stream())
 
 
 class SignTables:
@@ -443,9 +449,7 @@ def _sign_payload(dp, payload, layout, slots):
         sp, end = _check_slots(dp, slots, payload, "payload")
         return payload.numel(), 0, 0, sp, end
     _check_sign_layout(dp, layout)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    _encode_dst(payload, layout)
     return layout.nbytes, layout.scales, layout.codes, 0, 0
 
 
@@ -508,10 +512,7 @@ def _sign_recv(dp, recv, layout, slots):
         sp, end = _check_slots(dp, slots, recv, "recv")
         return 1, recv.numel(), 0, 0, sp, end
     _check_sign_layout(dp, layout)
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or recv.shape[0] < 1:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}]")
-    return recv.shape[0], layout.nbytes, layout.scales, layout.codes, 0, 0
+    return _recv_rows(recv, layout), layout.nbytes, layout.scales, layout.codes, 0, 0
 
 
 def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
@@ -527,24 +528,10 @@ def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=
     C = require()
     rotate, rot_key = _rot(rot_key, slots)
     nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
-    apply = param is not None
-    if apply:
-        _check_bucket(dp, param, "param")
-        if mom is not None:
-            _check_bucket(dp, mom, "mom")
-        elif momentum != 0.0 or nesterov:
-            raise ValueError("a momentum step needs the momentum buffer")
-    if grad_out is not None:
-        _check_bucket(dp, grad_out, "grad_out")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
-    _check_shadow(dp, shadow)
-    C.sign_decode_apply(_ptr(recv), nranks, stride, _ptr(dp.chunks),
-                        dp.plan.num_chunks, so, bo, _ptr(param), _ptr(mom),
-                        _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
-                        grad_scale, int(nesterov), int(first), int(apply), _stream(),
-                        _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
-                        _lrp(lr_tensor), sp, end, rotate, rot_key)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
+    C.sign_decode_apply(_ptr(recv), nranks, stride, _ptr(dp.chunks), dp.plan.num_chunks, so, bo,
+                        step, _stream(), sp, end, rotate, rot_key)
 
 
 def _check_mx_layout(dp, layout):
@@ -569,9 +556,7 @@ def mx_encode(dp, grad, payload, layout, resid=None, soft=False):
     C = require()
     _check_mx_layout(dp, layout)
     ptrs, mask = grad_pointers(dp, grad)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    _encode_dst(payload, layout)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
     C.mx_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
@@ -588,27 +573,12 @@ def mx_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.
     bitwise ``oracle.decode_sum``.  ``soft``: as in :func:`mx_encode`."""
     C = require()
     _check_mx_layout(dp, layout)
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 64:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}] with 1 <= nranks <= 64")
-    apply = param is not None
-    if apply:
-        _check_bucket(dp, param, "param")
-        if mom is not None:
-            _check_bucket(dp, mom, "mom")
-        elif momentum != 0.0 or nesterov:
-            raise ValueError("a momentum step needs the momentum buffer")
-    if grad_out is not None:
-        _check_bucket(dp, grad_out, "grad_out")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
-    _check_shadow(dp, shadow)
-    C.mx_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, dp.plan.length, _ptr(dp.chunks),
+    nranks = _recv_rows(recv, layout)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
+    C.mx_decode_apply(_ptr(recv), nranks, layout.nbytes, dp.plan.length, _ptr(dp.chunks),
                       dp.plan.num_chunks, layout.scales, layout.codes, layout.bits,
-                      int(bool(soft)), _ptr(param), _ptr(mom), _ptr(grad_out), _ptr(shadow), lr,
-                      momentum, dampening, weight_decay, grad_scale, int(nesterov), int(first),
-                      int(apply), _stream(), _keyp(key_state), key_seed & 0xFFFFFFFF,
-                      key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
+                      int(bool(soft)), step, _stream())
 
 
 def _check_tern_layout(dp, layout):
@@ -635,9 +605,7 @@ def tern_encode(dp: DevicePlan, grad, payload, layout, clip: float, key: int, re
     C = require()
     _check_tern_layout(dp, layout)
     ptrs, mask = grad_pointers(dp, grad)
-    _check(payload, torch.uint8, "payload")
-    if payload.numel() < layout.nbytes:
-        raise ValueError("payload too small")
+    _encode_dst(payload, layout)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
     if not float(clip) >= 0.0:
@@ -658,28 +626,12 @@ def tern_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_o
     bitwise ``oracle.decode_sum``."""
     C = require()
     _check_tern_layout(dp, layout)
-    _check(recv, torch.uint8, "recv")
-    if recv.dim() != 2 or recv.shape[1] != layout.nbytes or not 1 <= recv.shape[0] <= 64:
-        raise ValueError(f"recv must be [nranks, {layout.nbytes}] with 1 <= nranks <= 64")
-    apply = param is not None
-    if apply:
-        _check_bucket(dp, param, "param")
-        if mom is not None:
-            _check_bucket(dp, mom, "mom")
-        elif momentum != 0.0 or nesterov:
-            raise ValueError("a momentum step needs the momentum buffer")
-    if grad_out is not None:
-        _check_bucket(dp, grad_out, "grad_out")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
-    _check_shadow(dp, shadow)
-    C.tern_decode_apply(_ptr(recv), recv.shape[0], layout.nbytes, dp.plan.total_codes,
-                        _ptr(dp.chunks), _ptr(dp.tensors), dp.plan.num_tensors,
-                        dp.plan.num_chunks, layout.scales, layout.codes, _ptr(param), _ptr(mom),
-                        _ptr(grad_out), _ptr(shadow), lr, momentum, dampening, weight_decay,
-                        grad_scale, int(nesterov), int(first), int(apply), _stream(),
-                        _keyp(key_state), key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF,
-                        _lrp(lr_tensor))
+    nranks = _recv_rows(recv, layout)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
+    C.tern_decode_apply(_ptr(recv), nranks, layout.nbytes, dp.plan.total_codes, _ptr(dp.chunks),
+                        _ptr(dp.tensors), dp.plan.num_tensors, dp.plan.num_chunks, layout.scales,
+                        layout.codes, step, _stream())
 
 
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
@@ -851,25 +803,21 @@ def _psgd_buf(t, n, name):
 
 
 def _psgd(op, lt, items, num_items, grad=None, resid=None, p=None, q=None, inv_n=1.0, q_out=None,
-          param=None, mom=None, grad_out=None, shadow=None, lr_tensor=None, lr=0.0, momentum=0.0,
-          dampening=0.0, weight_decay=0.0, nesterov=False, first=False, apply=False):
+          step=None):
+    C = require()
     lrp = lt.lrp
     _psgd_buf(p, lrp.p_floats, "p")
-    for t, nm in ((grad, "grad"), (resid, "resid"), (param, "param"), (mom, "mom"),
-                  (grad_out, "grad_out")):
+    for t, nm in ((grad, "grad"), (resid, "resid")):
         if t is not None:
             _check_bucket(lt, t, nm)
     for t, nm in ((q, "q"), (q_out, "q_out")):
         if t is not None:
             _psgd_buf(t, lrp.q_floats, nm)
-    _check_shadow(lt, shadow)
-    require().psgd(op, lrp.rank, _ptr(lt.mats), len(lrp.mats), _ptr(lt.dense), len(lrp.dense),
-                   _ptr(items), num_items, lrp.plan.length, lrp.p_floats, lrp.q_floats,
-                   _ptr(grad), _ptr(resid), _ptr(p), _ptr(q), _ptr(lt.slabs), lrp.slab_floats,
-                   _ptr(lt.tickets), lrp.num_tickets, float(inv_n), _ptr(q_out), _ptr(param),
-                   _ptr(mom), _ptr(grad_out), _ptr(shadow), _lrp(lr_tensor), float(lr),
-                   float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)),
-                   int(bool(first)), int(bool(apply)), _stream())
+    C.psgd(op, lrp.rank, _ptr(lt.mats), len(lrp.mats), _ptr(lt.dense), len(lrp.dense),
+           _ptr(items), num_items, lrp.plan.length, lrp.p_floats, lrp.q_floats, _ptr(grad),
+           _ptr(resid), _ptr(p), _ptr(q), _ptr(lt.slabs), lrp.slab_floats, _ptr(lt.tickets),
+           lrp.num_tickets, float(inv_n), _ptr(q_out), C.StepArgs() if step is None else step,
+           _stream())
 
 
 def psgd_project(lt: LowRankTables, grad, resid, q, p):
@@ -904,15 +852,10 @@ def psgd_decode_apply(lt: LowRankTables, resid, p, q, q_out, inv_n, param=None, 
         raise ValueError("the reconstruct launch needs resid, q and q_out")
     if q.data_ptr() == q_out.data_ptr():
         raise ValueError("q_out must not be q: other blocks still read q")
-    apply = param is not None
-    if apply and mom is None and (momentum != 0.0 or nesterov):
-        raise ValueError("a momentum step needs the momentum buffer")
-    if not apply and grad_out is None:
-        raise ValueError("nothing to do: pass param/mom and/or grad_out")
+    step = _step(lt, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay, 1.0,
+                 nesterov, first, None, 0, 0, lr_tensor)
     _psgd(3, lt, lt.tiles, len(lt.lrp.tile_items), resid=resid, p=p, q=q, inv_n=inv_n,
-          q_out=q_out, param=param, mom=mom, grad_out=grad_out, shadow=shadow,
-          lr_tensor=lr_tensor, lr=lr, momentum=momentum, dampening=dampening,
-          weight_decay=weight_decay, nesterov=nesterov, first=first, apply=apply)
+          q_out=q_out, step=step)
 
 
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -1022,9 +965,7 @@ def lion_encode(dp, grad, payload, layout, exp_avg, beta1, beta2, step, rank, st
         nbytes, codes = payload.numel(), 0
     else:
         _check_vote_layout(dp, layout)
-        _check(payload, torch.uint8, "payload")
-        if payload.numel() < layout.nbytes:
-            raise ValueError("payload too small")
+        _encode_dst(payload, layout)
         nbytes, codes, sp, end = layout.nbytes, layout.codes, 0, 0
     _check_bucket(dp, exp_avg, "exp_avg")
     if step_tensor is not None:

@@ -14,9 +14,31 @@ namespace py = pybind11;
 using Ptrs = std::vector<uintptr_t>;
 using Mask = std::vector<uint32_t>;
 
+// the gradient source of an encode, from the pointer list and bf16 mask of ops.grad_pointers
+static GradSrc grad_src(const Ptrs& grads, const Mask& mask) {
+  return GradSrc{grads.data(), (int)grads.size(), mask.data(), (int)mask.size()};
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "ewdml CDNA4 (gfx950) kernels";
   m.attr("arch") = "gfx950";
+
+  // the receive-side step of every *_decode_apply and of psgd (ops._step builds it)
+  py::class_<StepArgs>(m, "StepArgs")
+      .def(py::init([](uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
+                       float lr, float momentum, float dampening, float weight_decay,
+                       float grad_scale, int nesterov, int first, int apply, uintptr_t key_state,
+                       uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr) {
+             return StepArgs{param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                             grad_scale, nesterov, first, apply, key_state, key_seed, key_rank,
+                             lr_ptr};
+           }),
+           py::arg("param") = 0, py::arg("mom") = 0, py::arg("grad_out") = 0,
+           py::arg("shadow") = 0, py::arg("lr") = 0.0f, py::arg("momentum") = 0.0f,
+           py::arg("dampening") = 0.0f, py::arg("weight_decay") = 0.0f,
+           py::arg("grad_scale") = 1.0f, py::arg("nesterov") = 0, py::arg("first") = 0,
+           py::arg("apply") = 0, py::arg("key_state") = 0, py::arg("key_seed") = 0,
+           py::arg("key_rank") = 0, py::arg("lr_ptr") = 0);
 
   m.def("topk_scratch_bytes", &ew_topk_scratch_bytes);
   m.def("topk_lookback_errors", &ew_topk_lookback_errors);
@@ -70,10 +92,7 @@ PYBIND11_MODULE(_C, m) {
           a.dgc_damp1 = dgc_damp1;
           a.dgc_wd = dgc_wd;
           a.dgc_nesterov = dgc_nesterov;
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.tensors = tensors;
@@ -100,23 +119,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("topk_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, uintptr_t tensors,
            int C, int scales_off, int counts_off, int idx_off, int codes_off, int value_kind,
-           float inv_levels, uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
-           float lr, float momentum, float dampening, float weight_decay, float grad_scale,
-           int nesterov, int first, int apply, uintptr_t stream, uintptr_t key_state,
-           uint32_t key_seed, uint32_t key_rank, int bitmap_off, uintptr_t lr_ptr) {
+           float inv_levels, const StepArgs& step, uintptr_t stream, int bitmap_off) {
           TopkDecodeArgs a{};
-          a.lr_ptr = lr_ptr;
+          a.step = step;
           a.bitmap_off = bitmap_off;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
           a.recv = recv;
           a.chunks = chunks;
           a.tensors = tensors;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
           a.stream = stream;
           a.stride = stride;
           a.nranks = nranks;
@@ -127,14 +136,6 @@ PYBIND11_MODULE(_C, m) {
           a.codes_off = codes_off;
           a.value_kind = value_kind;
           a.inv_levels = inv_levels;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
           ew_topk_decode_apply(a);
         });
 
@@ -145,10 +146,7 @@ PYBIND11_MODULE(_C, m) {
            float inv_levels, uint32_t key, uint32_t bucket_offset, uintptr_t key_ptr,
            uintptr_t stream) {
           QsgdEncodeArgs a{};
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.tensors = tensors;
@@ -172,23 +170,13 @@ PYBIND11_MODULE(_C, m) {
 
   m.def("qsgd_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, uintptr_t tensors,
-           int C, int scales_off, int codes_off, int bits, float inv_levels, uintptr_t param,
-           uintptr_t mom, uintptr_t grad_out, uintptr_t shadow, float lr, float momentum,
-           float dampening, float weight_decay, float grad_scale, int nesterov, int first,
-           int apply, uintptr_t stream, uintptr_t key_state, uint32_t key_seed,
-           uint32_t key_rank, uintptr_t lr_ptr) {
+           int C, int scales_off, int codes_off, int bits, float inv_levels,
+           const StepArgs& step, uintptr_t stream) {
           QsgdDecodeArgs a{};
-          a.lr_ptr = lr_ptr;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
+          a.step = step;
           a.recv = recv;
           a.chunks = chunks;
           a.tensors = tensors;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
           a.stream = stream;
           a.stride = stride;
           a.nranks = nranks;
@@ -197,14 +185,6 @@ PYBIND11_MODULE(_C, m) {
           a.codes_off = codes_off;
           a.bits = bits;
           a.inv_levels = inv_levels;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
           ew_qsgd_decode_apply(a);
         });
 
@@ -218,10 +198,7 @@ PYBIND11_MODULE(_C, m) {
           a.rot_key = rot_key;
           a.slots = slots;
           a.slot_end = slot_end;
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.payload = payload;
@@ -242,10 +219,7 @@ PYBIND11_MODULE(_C, m) {
           SignEncodeArgs a{};
           a.slots = slots;
           a.slot_end = slot_end;
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.payload = payload;
@@ -376,40 +350,22 @@ PYBIND11_MODULE(_C, m) {
 
   m.def("sign_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
-           int bits_off, uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
-           float lr, float momentum, float dampening, float weight_decay, float grad_scale,
-           int nesterov, int first, int apply, uintptr_t stream, uintptr_t key_state,
-           uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr, uintptr_t slots,
+           int bits_off, const StepArgs& step, uintptr_t stream, uintptr_t slots,
            long long slot_end, int rotate, uint32_t rot_key) {
           SignDecodeArgs a{};
+          a.step = step;
           a.rotate = rotate;
           a.rot_key = rot_key;
           a.slots = slots;
           a.slot_end = slot_end;
-          a.lr_ptr = lr_ptr;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
           a.recv = recv;
           a.chunks = chunks;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
           a.stream = stream;
           a.stride = stride;
           a.nranks = nranks;
           a.num_chunks = C;
           a.scales_off = scales_off;
           a.bits_off = bits_off;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
           ew_sign_decode_apply(a);
         });
 
@@ -418,10 +374,7 @@ PYBIND11_MODULE(_C, m) {
            uintptr_t payload, long long payload_bytes, long long length, int T, int C,
            int scales_off, int codes_off, int bits, int soft, uintptr_t stream) {
           MxEncodeArgs a{};
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.payload = payload;
@@ -439,18 +392,12 @@ PYBIND11_MODULE(_C, m) {
 
   m.def("mx_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, long long length, uintptr_t chunks, int C,
-           int scales_off, int codes_off, int bits, int soft, uintptr_t param, uintptr_t mom,
-           uintptr_t grad_out, uintptr_t shadow, float lr, float momentum, float dampening,
-           float weight_decay, float grad_scale, int nesterov, int first, int apply,
-           uintptr_t stream, uintptr_t key_state, uint32_t key_seed, uint32_t key_rank,
-           uintptr_t lr_ptr) {
+           int scales_off, int codes_off, int bits, int soft, const StepArgs& step,
+           uintptr_t stream) {
           MxDecodeArgs a{};
+          a.step = step;
           a.recv = recv;
           a.chunks = chunks;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
           a.stream = stream;
           a.stride = stride;
           a.length = length;
@@ -460,18 +407,6 @@ PYBIND11_MODULE(_C, m) {
           a.codes_off = codes_off;
           a.bits = bits;
           a.soft = soft;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
-          a.lr_ptr = lr_ptr;
           ew_mx_decode_apply(a);
         });
 
@@ -481,10 +416,7 @@ PYBIND11_MODULE(_C, m) {
            long long total_codes, int T, int C, int scales_off, int codes_off, float clip,
            uint32_t key, uint32_t bucket_offset, uintptr_t key_ptr, uintptr_t stream) {
           TernEncodeArgs a{};
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.resid = resid;
           a.chunks = chunks;
           a.tensors = tensors;
@@ -506,19 +438,13 @@ PYBIND11_MODULE(_C, m) {
 
   m.def("tern_decode_apply",
         [](uintptr_t recv, int nranks, long long stride, long long total_codes, uintptr_t chunks,
-           uintptr_t tensors, int T, int C, int scales_off, int codes_off, uintptr_t param,
-           uintptr_t mom, uintptr_t grad_out, uintptr_t shadow, float lr, float momentum,
-           float dampening, float weight_decay, float grad_scale, int nesterov, int first,
-           int apply, uintptr_t stream, uintptr_t key_state, uint32_t key_seed,
-           uint32_t key_rank, uintptr_t lr_ptr) {
+           uintptr_t tensors, int T, int C, int scales_off, int codes_off, const StepArgs& step,
+           uintptr_t stream) {
           TernDecodeArgs a{};
+          a.step = step;
           a.recv = recv;
           a.chunks = chunks;
           a.tensors = tensors;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
           a.stream = stream;
           a.stride = stride;
           a.total_codes = total_codes;
@@ -527,18 +453,6 @@ PYBIND11_MODULE(_C, m) {
           a.num_chunks = C;
           a.scales_off = scales_off;
           a.codes_off = codes_off;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
-          a.lr_ptr = lr_ptr;
           ew_tern_decode_apply(a);
         });
 
@@ -548,9 +462,7 @@ PYBIND11_MODULE(_C, m) {
            uintptr_t items, int num_items, long long bucket_len, long long p_floats,
            long long q_floats, uintptr_t grad, uintptr_t resid, uintptr_t p, uintptr_t q,
            uintptr_t slabs, long long slab_floats, uintptr_t tickets, int num_tickets,
-           float inv_n, uintptr_t q_out, uintptr_t param, uintptr_t mom, uintptr_t grad_out,
-           uintptr_t shadow, uintptr_t lr_ptr, float lr, float momentum, float dampening,
-           float weight_decay, int nesterov, int first, int apply, uintptr_t stream) {
+           float inv_n, uintptr_t q_out, const StepArgs& step, uintptr_t stream) {
           PsgdArgs a{};
           a.mats = mats;
           a.dense = dense;
@@ -573,18 +485,7 @@ PYBIND11_MODULE(_C, m) {
           a.num_tickets = num_tickets;
           a.inv_n = inv_n;
           a.q_out = q_out;
-          a.param = param;
-          a.mom = mom;
-          a.grad_out = grad_out;
-          a.shadow = shadow;
-          a.lr_ptr = lr_ptr;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.apply = apply;
+          a.step = step;
           if (op == 0) ew_psgd_project(a);
           else if (op == 1) ew_psgd_orth(a);
           else if (op == 2) ew_psgd_backproject(a);
@@ -673,10 +574,7 @@ PYBIND11_MODULE(_C, m) {
           LionEncodeArgs a{};
           a.slots = slots;
           a.slot_end = slot_end;
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.exp_avg = exp_avg;
           a.chunks = chunks;
           a.payload = payload;
@@ -786,10 +684,7 @@ PYBIND11_MODULE(_C, m) {
            uintptr_t partials, int chunk0, int total_chunks, uintptr_t state, float max_norm,
            uintptr_t stream) {
           ClipArgs a{};
-          a.grad_ptrs = grads.data();
-          a.n_grad_ptrs = (int)grads.size();
-          a.bf16_mask = mask.data();
-          a.n_bf16_mask = (int)mask.size();
+          a.src = grad_src(grads, mask);
           a.num_tensors = T;
           a.chunks = chunks;
           a.num_chunks = C;

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_clip_scale(GradPtrs gp,
 }
 
 void clip_validate(const ClipArgs& a) {
-  if (a.num_chunks < 1 || !a.chunks || !a.partials || !a.grad_ptrs)
+  if (a.num_chunks < 1 || !a.chunks || !a.partials || !a.src.grad_ptrs)
     throw std::runtime_error("ewdml clip: missing operand");
   if (a.chunk0 < 0 || a.total_chunks < 1 || (long long)a.chunk0 + a.num_chunks > a.total_chunks)
     throw std::runtime_error("ewdml clip: the bucket's chunks reach past the model's partials");
@@ -148,7 +148,7 @@ void clip_validate(const ClipArgs& a) {
 void ew_clip_norm(const ClipArgs& a) {
   clip_validate(a);
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, a.num_tensors);
   hipLaunchKernelGGL(k_clip_norm, dim3(a.num_chunks), dim3(EW_BLOCK), 0, (hipStream_t)a.stream, g,
                      reinterpret_cast<const ChunkRow*>(a.chunks),
                      reinterpret_cast<float*>(a.partials) + a.chunk0);
@@ -159,7 +159,7 @@ void ew_clip_scale(const ClipArgs& a) {
   clip_validate(a);
   if (!(a.max_norm > 0.0f)) throw std::runtime_error("ewdml clip: max_norm must be > 0");
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, a.num_tensors);
   // the first bucket's first block stores clip_state
   float* state = a.chunk0 == 0 ? reinterpret_cast<float*>(a.state) : nullptr;
   if (a.chunk0 == 0 && !state) throw std::runtime_error("ewdml clip: missing clip_state");

@@ -15,6 +15,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "ewdml_ops.h"
+
 // Host-side error check: turn a HIP error into a C++ exception (surfaces as a Python RuntimeError).
 #define EW_CHECK(expr)                                                                       \
   do {                                                                                       \
@@ -60,6 +62,9 @@ inline void ew_fill_ptrs(GradPtrs& g, const uintptr_t* ptrs, int n, int T, const
                              std::to_string(EW_MAX_T) + ")");
   for (int i = 0; i < EW_MAX_T; ++i) g.p[i] = i < T ? reinterpret_cast<const void*>(ptrs[i]) : nullptr;
   for (int i = 0; i < EW_MAX_T / 32; ++i) g.bf16[i] = (mask && i < nmask) ? mask[i] : 0u;
+}
+inline void ew_fill_ptrs(GradPtrs& g, const GradSrc& s, int T) {
+  ew_fill_ptrs(g, s.grad_ptrs, s.n_grad_ptrs, T, s.bf16_mask, s.n_bf16_mask);
 }
 
 __device__ __forceinline__ float ew_bf16f(uint32_t v) { return __uint_as_float((v & 0xffffu) << 16); }
@@ -192,6 +197,12 @@ struct SgdArgs {
   // re-capture (the host value is frozen into a captured kernel's arguments)
   const float* lr_ptr;
 };
+// the device form of a host step description (ewdml_ops.h)
+inline SgdArgs ew_sgd_args(const StepArgs& s) {
+  return SgdArgs{s.lr, s.momentum, s.dampening, s.weight_decay, s.grad_scale, s.nesterov, s.first,
+                 reinterpret_cast<uint32_t*>(s.key_state), s.key_seed, s.key_rank,
+                 reinterpret_cast<const float*>(s.lr_ptr)};
+}
 __device__ __forceinline__ void ew_sgd_resolve(SgdArgs& a) {
   if (a.lr_ptr) a.lr = *a.lr_ptr;
 }
@@ -328,4 +339,50 @@ __device__ __forceinline__ void ew_sgd(float& p, float& b, float g, const SgdArg
     d = a.nesterov ? (d + a.momentum * b) : b;
   }
   p = p - a.lr * d;
+}
+
+// What a decode that holds its chunk in registers does with the decoded sum (acc: thread t's
+// elements [4t, 4t + 4) of each of the chunk's EW_CU slabs): * grad_scale, then grad_out and / or
+// the fused SGD step with its bf16 shadow, on the chunk's own positions
+__device__ __forceinline__ void ew_chunk_apply(const float (&acc)[EW_CU][4], const ChunkRow& c,
+                                               float* __restrict__ param, float* __restrict__ mom,
+                                               float* __restrict__ grad_out,
+                                               uint16_t* __restrict__ shadow, const SgdArgs& sa,
+                                               int apply) {
+  float* p = param + c.start;
+  float* b = mom ? mom + c.start : nullptr;
+  float* go = grad_out ? grad_out + c.start : nullptr;
+  uint16_t* sh = shadow ? shadow + c.start : nullptr;
+#pragma unroll
+  for (int u = 0; u < EW_CU; ++u) {
+    const int i = ew_chunk_idx(u);
+    if (i >= c.len) continue;
+    float gv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gv[j] = acc[u][j] * sa.grad_scale;
+    if (i + 3 < c.len) {
+      if (go) *reinterpret_cast<float4*>(go + i) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+      if (apply) {
+        const float4 p4 = *reinterpret_cast<const float4*>(p + i);
+        const float4 b4 = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float pv[4] = {p4.x, p4.y, p4.z, p4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ew_sgd(pv[j], bv[j], gv[j], sa);
+        *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+        if (b) *reinterpret_cast<float4*>(b + i) = make_float4(bv[0], bv[1], bv[2], bv[3]);
+        if (sh) ew_st4_bf16(sh + i, 4, pv);
+      }
+    } else {  // the last elements of a tensor
+      for (int j = 0; j < 4 && i + j < c.len; ++j) {
+        if (go) go[i + j] = gv[j];
+        if (apply) {
+          float pv = p[i + j], bv = b ? b[i + j] : 0.0f;
+          ew_sgd(pv, bv, gv[j], sa);
+          p[i + j] = pv;
+          if (b) b[i + j] = bv;
+          if (sh) sh[i + j] = ew_f2bf(pv);
+        }
+      }
+    }
+  }
 }

@@ -1,16 +1,45 @@
 // Host-side entry points of the ewdml HIP kernels (C++ only, no HIP types), bound to Python in
 // bindings.cpp.  Pointers are device addresses passed as integers; `stream` is a hipStream_t.
 #pragma once
+#include <stdexcept>
 #include <string>
 #include <vector>
 #include <stddef.h>
 #include <stdint.h>
 
-struct TopkEncodeArgs {
+// Where an encode (or the clip) reads a bucket's gradients: one base pointer per tensor.
+struct GradSrc {
   const uintptr_t* grad_ptrs;  // per-tensor gradient base pointers (host array, n_grad_ptrs)
   int n_grad_ptrs;
   const uint32_t* bf16_mask;   // bit t: tensor t's gradient is bf16
   int n_bf16_mask;
+};
+
+// What the receive side of every exchange does with a bucket's decoded mean g * grad_scale: write
+// it to grad_out and / or (apply) take the fused SGD step on param / mom (mom 0: a step without
+// momentum) with the bf16 shadow.  The bucket views hold the bucket's length in elements.
+struct StepArgs {
+  uintptr_t param, mom, grad_out, shadow;
+  float lr, momentum, dampening, weight_decay, grad_scale;
+  int nesterov, first, apply;
+  uintptr_t key_state;  // nullable int32[2] {step, key}: advanced to the next step (HIP graphs)
+  uint32_t key_seed, key_rank;
+  uintptr_t lr_ptr;  // nullable device fp32 learning rate (overrides lr)
+};
+
+// The checks every decode entry point makes before its launch (need_mom: the kernel reads the
+// momentum buffer whatever the momentum is)
+inline void ew_step_check(const std::string& who, const StepArgs& s, bool need_mom) {
+  if (s.apply && !s.param) throw std::runtime_error(who + ": apply needs the parameters");
+  if (!s.apply && !s.grad_out) throw std::runtime_error(who + ": nothing to write");
+  if (s.apply && !s.mom && (need_mom || s.momentum != 0.0f || s.nesterov))
+    throw std::runtime_error(who + ": a momentum step needs the momentum buffer");
+  if ((s.param | s.mom | s.grad_out) % 16 || s.shadow % 8 || (s.key_state | s.lr_ptr) % 4)
+    throw std::runtime_error(who + ": misaligned operand");
+}
+
+struct TopkEncodeArgs {
+  GradSrc src;
   uintptr_t resid, chunks, tensors, scratch, payload, stream;
   long long payload_bytes;
   int num_tensors, num_chunks;
@@ -50,24 +79,17 @@ struct TopkEncodeArgs {
 };
 
 struct TopkDecodeArgs {
-  uintptr_t recv, chunks, tensors, param, mom, grad_out, shadow, stream;
+  uintptr_t recv, chunks, tensors, stream;
   long long stride;
   int nranks, num_chunks;
   int scales_off, counts_off, idx_off, codes_off, bitmap_off;
   int value_kind;
   float inv_levels;
-  float lr, momentum, dampening, weight_decay, grad_scale;
-  int nesterov, first, apply;
-  uintptr_t key_state;  // nullable int32[2] {step, key}: advanced to the next step (HIP graphs)
-  uint32_t key_seed, key_rank;
-  uintptr_t lr_ptr;  // nullable device fp32 learning rate (overrides lr)
+  StepArgs step;
 };
 
 struct QsgdEncodeArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   uintptr_t resid, chunks, tensors, scratch, payload, stream;
   long long payload_bytes;
   int num_tensors, num_chunks;
@@ -78,24 +100,17 @@ struct QsgdEncodeArgs {
 };
 
 struct QsgdDecodeArgs {
-  uintptr_t recv, chunks, tensors, param, mom, grad_out, shadow, stream;
+  uintptr_t recv, chunks, tensors, stream;
   long long stride;
   int nranks, num_chunks;
   int scales_off, codes_off, bits;
   float inv_levels;
-  float lr, momentum, dampening, weight_decay, grad_scale;
-  int nesterov, first, apply;
-  uintptr_t key_state;  // see TopkDecodeArgs
-  uint32_t key_seed, key_rank;
-  uintptr_t lr_ptr;
+  StepArgs step;  // the kernel reads step.mom whenever it applies
 };
 
 // scaled sign with error feedback (sign_codec.hip): scales f32[C] | bits u32[256 * C]
 struct SignEncodeArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   uintptr_t resid, chunks, payload, stream;  // resid 0: no error feedback
   long long payload_bytes;
   int num_tensors, num_chunks;
@@ -138,7 +153,7 @@ struct SignOnebitArgs {
   uintptr_t step;    // nullable int32 device step counter: lr_step derived on the device
   double lr;         // base lr for the device-side lr_step
   uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
-  uintptr_t key_state;  // see TopkDecodeArgs
+  uintptr_t key_state;  // see StepArgs
   uint32_t key_seed, key_rank;
   uintptr_t slots;  // see SignEncodeArgs: recv is the gathered row buffer (stride = its bytes),
   long long slot_end;  // nranks must be 1
@@ -163,20 +178,16 @@ struct SignLambArgs {
   int t, freeze_step;  // the host's 1-based step (replaced by *step + 1 when step is set)
   uintptr_t step;      // nullable int32 device step counter
   uintptr_t lr_ptr;    // nullable device fp32 lr (overrides lr)
-  uintptr_t key_state;  // see TopkDecodeArgs; advanced by the apply launch
+  uintptr_t key_state;  // see StepArgs; advanced by the apply launch
   uint32_t key_seed, key_rank;
 };
 
 struct SignDecodeArgs {
-  uintptr_t recv, chunks, param, mom, grad_out, shadow, stream;  // mom 0: a step without momentum
+  uintptr_t recv, chunks, stream;
   long long stride;
   int nranks, num_chunks;
   int scales_off, bits_off;
-  float lr, momentum, dampening, weight_decay, grad_scale;
-  int nesterov, first, apply;
-  uintptr_t key_state;  // see TopkDecodeArgs
-  uint32_t key_seed, key_rank;
-  uintptr_t lr_ptr;
+  StepArgs step;
   uintptr_t slots;  // see SignOnebitArgs
   long long slot_end;
   int rotate;  // see SignEncodeArgs: one inverse transform of the summed rows (slots must be 0)
@@ -187,10 +198,7 @@ struct SignDecodeArgs {
 // codes u8[length * bits / 8], length = the bucket's padded length.  soft != 0: the conversions in
 // software instead of v_cvt_scalef32_pk_* (the same bytes; the tests' cross-check)
 struct MxEncodeArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   uintptr_t resid, chunks, payload, stream;  // resid 0: no error feedback
   long long payload_bytes, length;
   int num_tensors, num_chunks;
@@ -198,25 +206,18 @@ struct MxEncodeArgs {
 };
 
 struct MxDecodeArgs {
-  uintptr_t recv, chunks, param, mom, grad_out, shadow, stream;  // mom 0: a step without momentum
+  uintptr_t recv, chunks, stream;
   long long stride, length;
   int nranks, num_chunks;
   int scales_off, codes_off, bits, soft;
-  float lr, momentum, dampening, weight_decay, grad_scale;
-  int nesterov, first, apply;
-  uintptr_t key_state;  // see TopkDecodeArgs
-  uint32_t key_seed, key_rank;
-  uintptr_t lr_ptr;
+  StepArgs step;
 };
 
 // TernGrad ternary codes with a clipped per-tensor scaler (tern_codec.hip): scales f32[T] | codes
 // u32[total_codes / 16], 2 bits per element.  scratch: ew_qsgd_scratch_bytes(T, C) bytes.  clip:
 // scale = min(max|x|, clip * rms(x)); 0 = no clipping
 struct TernEncodeArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   uintptr_t resid, chunks, tensors, scratch, payload, stream;  // resid 0: no error feedback
   long long payload_bytes, total_codes;
   int num_tensors, num_chunks;
@@ -227,15 +228,11 @@ struct TernEncodeArgs {
 };
 
 struct TernDecodeArgs {
-  uintptr_t recv, chunks, tensors, param, mom, grad_out, shadow, stream;  // mom 0: no momentum
+  uintptr_t recv, chunks, tensors, stream;
   long long stride, total_codes;
   int nranks, num_tensors, num_chunks;
   int scales_off, codes_off;
-  float lr, momentum, dampening, weight_decay, grad_scale;
-  int nesterov, first, apply;
-  uintptr_t key_state;  // see TopkDecodeArgs
-  uint32_t key_seed, key_rank;
-  uintptr_t lr_ptr;
+  StepArgs step;
 };
 
 // PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /
@@ -252,9 +249,8 @@ struct PsgdArgs {
   int num_tickets;
   // orthogonalise / reconstruct: the all-reduce's 1/N; reconstruct: q_out receives q * inv_n
   float inv_n;
-  uintptr_t q_out, param, mom, grad_out, shadow, lr_ptr;
-  float lr, momentum, dampening, weight_decay;
-  int nesterov, first, apply;
+  uintptr_t q_out;
+  StepArgs step;  // reconstruct only: grad_scale 1, no key advance
 };
 
 struct SgdFlatArgs {
@@ -291,10 +287,7 @@ struct LionFlatArgs {
 // Encode: this rank's exp_avg (the bucket's view) is read and rewritten.  step: the 1-based step
 // of the exact-zero dither, read as *step_ptr + 1 when step_ptr (int32 device counter) is set.
 struct LionEncodeArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   uintptr_t exp_avg, chunks, payload, stream;
   long long payload_bytes;
   int num_tensors, num_chunks;
@@ -320,7 +313,7 @@ struct LionVoteArgs {
   float lr, weight_decay, inv_n;
   int average;
   uintptr_t lr_ptr;
-  uintptr_t key_state;  // see TopkDecodeArgs
+  uintptr_t key_state;  // see StepArgs
   uint32_t key_seed, key_rank;
   uintptr_t slots;  // see LionEncodeArgs: recv is the gathered row buffer (stride = its bytes),
   long long slot_end;  // nranks must be 1 and average 0 (d = 1 - 2 * bit)
@@ -365,10 +358,7 @@ void ew_layerwise_apply(const LayerwiseArgs& a);
 // in which this bucket's rows start at chunk0.  ew_clip_norm of every bucket comes before any
 // ew_clip_scale; the scale of the bucket with chunk0 == 0 stores state fp32[2] = {norm, coef}.
 struct ClipArgs {
-  const uintptr_t* grad_ptrs;
-  int n_grad_ptrs;
-  const uint32_t* bf16_mask;
-  int n_bf16_mask;
+  GradSrc src;
   int num_tensors, num_chunks, chunk0, total_chunks;
   uintptr_t chunks, partials, state, stream;
   float max_norm;

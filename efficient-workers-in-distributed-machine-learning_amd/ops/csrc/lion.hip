@@ -306,7 +306,7 @@ void ew_lion_encode(const LionEncodeArgs& a) {
   if (!a.exp_avg || !a.payload || !a.chunks)
     throw std::runtime_error("ewdml lion encode: needs exp_avg, the payload and the chunk table");
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, a.num_tensors);
   auto* mom = reinterpret_cast<float*>(a.exp_avg);
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
   auto* payload = reinterpret_cast<uint8_t*>(a.payload);

@@ -200,53 +200,8 @@ __global__ __launch_bounds__(EW_BLOCK) void k_mx_encode(GradPtrs gp, float* __re
   if (EF) ew_st_chunk(resid + c.start, c.len, e);
 }
 
-// What the decode does with the chunk's decoded sum: * grad_scale, then grad_out and / or the
-// fused SGD step with its bf16 shadow, on the chunk's own positions (sign_codec.hip ew_sign_apply)
-__device__ __forceinline__ void mx_apply(const float (&acc)[EW_CU][4], const ChunkRow& c,
-                                         float* __restrict__ param, float* __restrict__ mom,
-                                         float* __restrict__ grad_out,
-                                         uint16_t* __restrict__ shadow, const SgdArgs& sa,
-                                         int apply) {
-  float* p = param + c.start;
-  float* b = mom ? mom + c.start : nullptr;
-  float* go = grad_out ? grad_out + c.start : nullptr;
-  uint16_t* sh = shadow ? shadow + c.start : nullptr;
-#pragma unroll
-  for (int u = 0; u < EW_CU; ++u) {
-    const int i = ew_chunk_idx(u);
-    if (i >= c.len) continue;
-    float gv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gv[j] = acc[u][j] * sa.grad_scale;
-    if (i + 3 < c.len) {
-      if (go) *reinterpret_cast<float4*>(go + i) = make_float4(gv[0], gv[1], gv[2], gv[3]);
-      if (apply) {
-        const float4 p4 = *reinterpret_cast<const float4*>(p + i);
-        const float4 b4 = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float pv[4] = {p4.x, p4.y, p4.z, p4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ew_sgd(pv[j], bv[j], gv[j], sa);
-        *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-        if (b) *reinterpret_cast<float4*>(b + i) = make_float4(bv[0], bv[1], bv[2], bv[3]);
-        if (sh) ew_st4_bf16(sh + i, 4, pv);
-      }
-    } else {  // the last elements of a tensor
-      for (int j = 0; j < 4 && i + j < c.len; ++j) {
-        if (go) go[i + j] = gv[j];
-        if (apply) {
-          float pv = p[i + j], bv = b ? b[i + j] : 0.0f;
-          ew_sgd(pv, bv, gv[j], sa);
-          p[i + j] = pv;
-          if (b) b[i + j] = bv;
-          if (sh) sh[i + j] = ew_f2bf(pv);
-        }
-      }
-    }
-  }
-}
-
 // One block per chunk row: the N received rows decoded and summed in rank order from 0.0f
-// (oracle.decode_sum), then mx_apply
+// (oracle.decode_sum), then ew_chunk_apply
 template <int BITS, bool SOFT>
 __global__ __launch_bounds__(EW_BLOCK) void k_mx_decode_apply(
     const uint8_t* __restrict__ recv, int nranks, long long stride,
@@ -288,7 +243,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_mx_decode_apply(
       for (int j = 0; j < 4; ++j) acc[u][j] = acc[u][j] + d[j];
     }
   }
-  mx_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
+  ew_chunk_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
 }
 
 }  // namespace
@@ -328,7 +283,7 @@ void ew_mx_encode(const MxEncodeArgs& a) {
   if ((a.payload | a.resid) % 16 || a.chunks % 4)
     throw std::runtime_error("ewdml mx: misaligned operand");
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, a.num_tensors);
   if (a.bits == 8) {
     if (a.soft) ew_mx_encode_launch<8, true>(a, g);
     else ew_mx_encode_launch<8, false>(a, g);
@@ -344,9 +299,9 @@ static void ew_mx_decode_launch(const MxDecodeArgs& a, const SgdArgs& sa) {
   EW_LAUNCH((k_mx_decode_apply<BITS, SOFT>), a.num_chunks, a.stream,
             reinterpret_cast<const uint8_t*>(a.recv), a.nranks, a.stride,
             reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.codes_off,
-            reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
-            reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
-            a.apply);
+            reinterpret_cast<float*>(a.step.param), reinterpret_cast<float*>(a.step.mom),
+            reinterpret_cast<float*>(a.step.grad_out),
+            reinterpret_cast<uint16_t*>(a.step.shadow), sa, a.step.apply);
 }
 
 void ew_mx_decode_apply(const MxDecodeArgs& a) {
@@ -354,16 +309,10 @@ void ew_mx_decode_apply(const MxDecodeArgs& a) {
     throw std::runtime_error("ewdml mx decode: nothing to decode, or too many ranks");
   ew_mx_fit("ewdml mx decode", a.bits, a.scales_off, a.codes_off, a.length, a.stride);
   if (!a.recv || !a.chunks) throw std::runtime_error("ewdml mx decode: missing table");
-  if (a.apply && !a.param) throw std::runtime_error("ewdml mx decode: apply needs the parameters");
-  if (!a.apply && !a.grad_out) throw std::runtime_error("ewdml mx decode: nothing to write");
-  if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
-    throw std::runtime_error("ewdml mx decode: a momentum step needs the momentum buffer");
-  if ((a.param | a.mom | a.grad_out) % 16 || a.shadow % 8 || a.recv % 16 || a.stride % 4 ||
-      (a.chunks | a.key_state | a.lr_ptr) % 4)
+  ew_step_check("ewdml mx decode", a.step, false);
+  if (a.recv % 16 || a.stride % 4 || a.chunks % 4)
     throw std::runtime_error("ewdml mx decode: misaligned operand");
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
-             reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
+  const SgdArgs sa = ew_sgd_args(a.step);
   if (a.bits == 8) {
     if (a.soft) ew_mx_decode_launch<8, true>(a, sa);
     else ew_mx_decode_launch<8, false>(a, sa);

@@ -431,15 +431,12 @@ void ew_psgd_decode_apply(const PsgdArgs& a) {
   ps_check(a, "decode", true);
   if (!a.resid || (a.num_mats > 0 && (!a.q || !a.q_out)))
     throw std::runtime_error("ewdml powersgd decode: needs resid, q and q_out");
-  if (a.apply && !a.param) throw std::runtime_error("ewdml powersgd decode: apply needs the parameters");
-  if (!a.apply && !a.grad_out) throw std::runtime_error("ewdml powersgd decode: nothing to write");
-  if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
-    throw std::runtime_error("ewdml powersgd decode: a momentum step needs the momentum buffer");
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, 1.0f, a.nesterov, a.first,
-             nullptr, 0u, 0u};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
-  PsgdOut o{reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
-            reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), a.apply};
+  const StepArgs& st = a.step;
+  ew_step_check("ewdml powersgd decode", st, false);
+  const SgdArgs sa = ew_sgd_args(st);
+  PsgdOut o{reinterpret_cast<float*>(st.param), reinterpret_cast<float*>(st.mom),
+            reinterpret_cast<float*>(st.grad_out), reinterpret_cast<uint16_t*>(st.shadow),
+            st.apply};
   PS_LAUNCH(k_psgd_decode_apply, a.num_items, a.stream, reinterpret_cast<float*>(a.resid),
             reinterpret_cast<const float*>(a.p), reinterpret_cast<const float*>(a.q),
             reinterpret_cast<float*>(a.q_out), a.inv_n, o, sa,

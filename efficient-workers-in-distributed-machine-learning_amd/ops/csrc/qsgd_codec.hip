@@ -173,7 +173,7 @@ void ew_qsgd_encode(const QsgdEncodeArgs& a) {
   hipStream_t s = (hipStream_t)a.stream;
   EW_CHECK(hipMemsetAsync(reinterpret_cast<void*>(a.scratch), 0, ew_qsgd_scratch_bytes(T, C), s));
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, T, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, T);
   float* resid = reinterpret_cast<float*>(a.resid);
   auto* pay = reinterpret_cast<uint8_t*>(a.payload);
   if (resid)
@@ -198,19 +198,19 @@ void ew_qsgd_encode(const QsgdEncodeArgs& a) {
 void ew_qsgd_decode_apply(const QsgdDecodeArgs& a) {
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
   auto* tensors = reinterpret_cast<const TensorRow*>(a.tensors);
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
-             reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
+  const StepArgs& st = a.step;
+  ew_step_check("ewdml qsgd decode", st, true);  // the kernel reads mom whenever it applies
+  const SgdArgs sa = ew_sgd_args(st);
   auto* recv = reinterpret_cast<const uint8_t*>(a.recv);
-  auto* p = reinterpret_cast<float*>(a.param);
-  auto* m = reinterpret_cast<float*>(a.mom);
-  auto* go = reinterpret_cast<float*>(a.grad_out);
-  auto* sh = reinterpret_cast<uint16_t*>(a.shadow);
+  auto* p = reinterpret_cast<float*>(st.param);
+  auto* m = reinterpret_cast<float*>(st.mom);
+  auto* go = reinterpret_cast<float*>(st.grad_out);
+  auto* sh = reinterpret_cast<uint16_t*>(st.shadow);
   if (a.bits == 8)
     EW_LAUNCH(k_qsgd_decode_apply<8>, a.num_chunks, a.stream, recv, a.nranks, a.stride, chunks,
-              tensors, a.scales_off, a.codes_off, a.inv_levels, p, m, go, sh, sa, a.apply);
+              tensors, a.scales_off, a.codes_off, a.inv_levels, p, m, go, sh, sa, st.apply);
   else
     EW_LAUNCH(k_qsgd_decode_apply<4>, a.num_chunks, a.stream, recv, a.nranks, a.stride, chunks,
-              tensors, a.scales_off, a.codes_off, a.inv_levels, p, m, go, sh, sa, a.apply);
+              tensors, a.scales_off, a.codes_off, a.inv_levels, p, m, go, sh, sa, st.apply);
   EW_CHECK_LAUNCH();
 }

@@ -368,51 +368,6 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_reduce_encode(
   ew_st_chunk(sresid + c.start, c.len, e);
 }
 
-// What the decodes do with the chunk's decoded sum (acc, the ew_sign_acc layout): * grad_scale,
-// then grad_out and / or the fused SGD step with its bf16 shadow, on the chunk's own positions
-__device__ __forceinline__ void ew_sign_apply(const float (&acc)[EW_CU][4], const ChunkRow& c,
-                                              float* __restrict__ param, float* __restrict__ mom,
-                                              float* __restrict__ grad_out,
-                                              uint16_t* __restrict__ shadow, const SgdArgs& sa,
-                                              int apply) {
-  float* p = param + c.start;
-  float* b = mom ? mom + c.start : nullptr;
-  float* go = grad_out ? grad_out + c.start : nullptr;
-  uint16_t* sh = shadow ? shadow + c.start : nullptr;
-#pragma unroll
-  for (int u = 0; u < EW_CU; ++u) {
-    const int i = ew_chunk_idx(u);
-    if (i >= c.len) continue;
-    float gv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gv[j] = acc[u][j] * sa.grad_scale;
-    if (i + 3 < c.len) {
-      if (go) *reinterpret_cast<float4*>(go + i) = make_float4(gv[0], gv[1], gv[2], gv[3]);
-      if (apply) {
-        const float4 p4 = *reinterpret_cast<const float4*>(p + i);
-        const float4 b4 = b ? *reinterpret_cast<const float4*>(b + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float pv[4] = {p4.x, p4.y, p4.z, p4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ew_sgd(pv[j], bv[j], gv[j], sa);
-        *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-        if (b) *reinterpret_cast<float4*>(b + i) = make_float4(bv[0], bv[1], bv[2], bv[3]);
-        if (sh) ew_st4_bf16(sh + i, 4, pv);
-      }
-    } else {  // the last elements of a tensor
-      for (int j = 0; j < 4 && i + j < c.len; ++j) {
-        if (go) go[i + j] = gv[j];
-        if (apply) {
-          float pv = p[i + j], bv = b ? b[i + j] : 0.0f;
-          ew_sgd(pv, bv, gv[j], sa);
-          p[i + j] = pv;
-          if (b) b[i + j] = bv;
-          if (sh) sh[i + j] = ew_f2bf(pv);
-        }
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
     const uint8_t* __restrict__ recv, int nranks, long long stride,
     const ChunkRow* __restrict__ chunks, int scales_off, int bits_off, float* __restrict__ param,
@@ -425,7 +380,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_sign_decode_apply(
   ew_sign_where(slots, scales_off, bits_off, scale_at, words_at);
   float acc[EW_CU][4];
   ew_sign_acc(recv, nranks, stride, scale_at, words_at, acc);
-  ew_sign_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
+  ew_chunk_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
 }
 
 // The rotated decode: the N ranks' +/- scale are summed in the rotated domain over all EW_CHUNK
@@ -452,7 +407,7 @@ __global__ __launch_bounds__(EW_BLOCK) void k_hsign_decode_apply(
   for (int u = 0; u < EW_CU; ++u) {
     acc[u][0] = e[u].x; acc[u][1] = e[u].y; acc[u][2] = e[u].z; acc[u][3] = e[u].w;
   }
-  ew_sign_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
+  ew_chunk_apply(acc, c, param, mom, grad_out, shadow, sa, apply);
 }
 
 // 1-bit Adam's receive side: m = (sum over ranks of +/- scale, rank order, from 0) * inv_n for
@@ -738,7 +693,7 @@ void ew_sign_encode(const SignEncodeArgs& a) {
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
   auto* slots = reinterpret_cast<const int2*>(a.slots);
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, a.num_tensors, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, a.num_tensors);
   float* resid = reinterpret_cast<float*>(a.resid);
   auto* pay = reinterpret_cast<uint8_t*>(a.payload);
   const SignMom mo{reinterpret_cast<const float*>(a.mom_exp_avg),
@@ -880,32 +835,27 @@ void ew_sign_decode_apply(const SignDecodeArgs& a) {
   if (a.slots && a.nranks != 1)
     throw std::runtime_error("ewdml sign decode: the slot-addressed decode reads one row buffer");
   ew_sign_fit("ewdml sign decode", a.slots, a.slot_end, a.scales_off, a.bits_off, C, a.stride);
-  if (a.apply && !a.param) throw std::runtime_error("ewdml sign decode: apply needs the parameters");
-  if (!a.apply && !a.grad_out) throw std::runtime_error("ewdml sign decode: nothing to write");
-  if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
-    throw std::runtime_error("ewdml sign decode: a momentum step needs the momentum buffer");
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
-             reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
+  const StepArgs& st = a.step;
+  ew_step_check("ewdml sign decode", st, false);
+  const SgdArgs sa = ew_sgd_args(st);
   if (a.rotate) {
     if (a.slots)
       throw std::runtime_error("ewdml sign decode: the rotated decode has no slot-addressed form");
     if (!a.recv || !a.chunks) throw std::runtime_error("ewdml sign decode: missing table");
-    if ((a.param | a.mom | a.grad_out) % 16 || a.shadow % 8 || a.recv % 16 || a.stride % 4 ||
-        (a.chunks | a.key_state | a.lr_ptr) % 4)
+    if (a.recv % 16 || a.stride % 4 || a.chunks % 4)
       throw std::runtime_error("ewdml sign decode: misaligned operand");
     EW_LAUNCH(k_hsign_decode_apply, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv),
               a.nranks, a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off,
-              a.bits_off, reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
-              reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
-              a.apply, a.rot_key);
+              a.bits_off, reinterpret_cast<float*>(st.param), reinterpret_cast<float*>(st.mom),
+              reinterpret_cast<float*>(st.grad_out), reinterpret_cast<uint16_t*>(st.shadow), sa,
+              st.apply, a.rot_key);
     EW_CHECK_LAUNCH();
     return;
   }
   EW_LAUNCH(k_sign_decode_apply, C, a.stream, reinterpret_cast<const uint8_t*>(a.recv), a.nranks,
             a.stride, reinterpret_cast<const ChunkRow*>(a.chunks), a.scales_off, a.bits_off,
-            reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
-            reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
-            a.apply, reinterpret_cast<const int2*>(a.slots));
+            reinterpret_cast<float*>(st.param), reinterpret_cast<float*>(st.mom),
+            reinterpret_cast<float*>(st.grad_out), reinterpret_cast<uint16_t*>(st.shadow), sa,
+            st.apply, reinterpret_cast<const int2*>(a.slots));
   EW_CHECK_LAUNCH();
 }

@@ -205,7 +205,7 @@ void ew_tern_encode(const TernEncodeArgs& a) {
   hipStream_t s = (hipStream_t)a.stream;
   EW_CHECK(hipMemsetAsync(reinterpret_cast<void*>(a.scratch), 0, ew_qsgd_scratch_bytes(T, C), s));
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, T, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, T);
   float* resid = reinterpret_cast<float*>(a.resid);
   auto* pay = reinterpret_cast<uint8_t*>(a.payload);
   auto* keyp = reinterpret_cast<const uint32_t*>(a.key_ptr);
@@ -231,22 +231,15 @@ void ew_tern_decode_apply(const TernDecodeArgs& a) {
               a.total_codes, a.stride);
   if (!a.recv || !a.chunks || !a.tensors)
     throw std::runtime_error("ewdml tern decode: missing table");
-  if (a.apply && !a.param)
-    throw std::runtime_error("ewdml tern decode: apply needs the parameters");
-  if (!a.apply && !a.grad_out) throw std::runtime_error("ewdml tern decode: nothing to write");
-  if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
-    throw std::runtime_error("ewdml tern decode: a momentum step needs the momentum buffer");
-  if ((a.param | a.mom | a.grad_out) % 16 || a.shadow % 8 || a.recv % 16 ||
-      (a.chunks | a.tensors | a.key_state | a.lr_ptr) % 4)
+  const StepArgs& st = a.step;
+  ew_step_check("ewdml tern decode", st, false);
+  if (a.recv % 16 || (a.chunks | a.tensors) % 4)
     throw std::runtime_error("ewdml tern decode: misaligned operand");
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
-             reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
   EW_LAUNCH(k_tern_decode_apply, a.num_chunks, a.stream, reinterpret_cast<const uint8_t*>(a.recv),
             a.nranks, a.stride, reinterpret_cast<const ChunkRow*>(a.chunks),
             reinterpret_cast<const TensorRow*>(a.tensors), a.scales_off, a.codes_off,
-            reinterpret_cast<float*>(a.param), reinterpret_cast<float*>(a.mom),
-            reinterpret_cast<float*>(a.grad_out), reinterpret_cast<uint16_t*>(a.shadow), sa,
-            a.apply);
+            reinterpret_cast<float*>(st.param), reinterpret_cast<float*>(st.mom),
+            reinterpret_cast<float*>(st.grad_out), reinterpret_cast<uint16_t*>(st.shadow),
+            ew_sgd_args(st), st.apply);
   EW_CHECK_LAUNCH();
 }

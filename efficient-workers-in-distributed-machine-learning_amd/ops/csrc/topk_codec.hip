@@ -3004,7 +3004,7 @@ void ew_topk_encode(const TopkEncodeArgs& a) {
   if (a.value_kind == VK_Q4)  // nibbles are OR-ed in; every other section is fully overwritten
     EW_CHECK(hipMemsetAsync(reinterpret_cast<void*>(a.payload), 0, a.payload_bytes, s));
   GradPtrs g;
-  ew_fill_ptrs(g, a.grad_ptrs, a.n_grad_ptrs, T, a.bf16_mask, a.n_bf16_mask);
+  ew_fill_ptrs(g, a.src, T);
   float* resid = reinterpret_cast<float*>(a.resid);
   const float* src_flat = resid;  // passes after hist0 read the staged e = g + r under EF
   // each pass's per-tensor step (select / scan) runs in the tensor's last-arriving chunk block
@@ -3211,19 +3211,17 @@ int ew_topk_lookback_errors(uintptr_t scratch, int T, int C) {
 void ew_topk_decode_apply(const TopkDecodeArgs& a) {
   auto* chunks = reinterpret_cast<const ChunkRow*>(a.chunks);
   auto* tensors = reinterpret_cast<const TensorRow*>(a.tensors);
-  if (a.apply && !a.mom && (a.momentum != 0.0f || a.nesterov))
-    throw std::runtime_error("ewdml topk decode: a momentum step needs the momentum buffer");
-  SgdArgs sa{a.lr, a.momentum, a.dampening, a.weight_decay, a.grad_scale, a.nesterov, a.first,
-             reinterpret_cast<uint32_t*>(a.key_state), a.key_seed, a.key_rank};
-  sa.lr_ptr = reinterpret_cast<const float*>(a.lr_ptr);
+  const StepArgs& st = a.step;
+  ew_step_check("ewdml topk decode", st, false);
+  const SgdArgs sa = ew_sgd_args(st);
   auto* recv = reinterpret_cast<const uint8_t*>(a.recv);
-  auto* p = reinterpret_cast<float*>(a.param);
-  auto* m = reinterpret_cast<float*>(a.mom);
-  auto* go = reinterpret_cast<float*>(a.grad_out);
-  auto* sh = reinterpret_cast<uint16_t*>(a.shadow);
+  auto* p = reinterpret_cast<float*>(st.param);
+  auto* m = reinterpret_cast<float*>(st.mom);
+  auto* go = reinterpret_cast<float*>(st.grad_out);
+  auto* sh = reinterpret_cast<uint16_t*>(st.shadow);
   const int C = a.num_chunks;
   // neither momentum nor weight decay nor an averaged-gradient output: the sparse kernel
-  const bool sparse = a.apply && !m && a.momentum == 0.0f && a.weight_decay == 0.0f && !go;
+  const bool sparse = st.apply && !m && st.momentum == 0.0f && st.weight_decay == 0.0f && !go;
 #define EW_DEC(VK)                                                                                   \
   if (sparse)                                                                                       \
     EW_LAUNCH(k_topk_decode_sparse<VK>, C, a.stream, recv, a.nranks, a.stride, chunks, tensors,      \
@@ -3233,7 +3231,7 @@ void ew_topk_decode_apply(const TopkDecodeArgs& a) {
     EW_LAUNCH(k_topk_decode_apply<VK>, C, a.stream, recv, a.nranks, a.stride, chunks, tensors,         \
             a.scales_off, a.counts_off, a.idx_off, a.codes_off, a.bitmap_off, a.inv_levels, p, m, go, \
             sh, sa,                                                                                  \
-            a.apply)
+            st.apply)
   if (a.value_kind == VK_Q8) EW_DEC(VK_Q8);
   else if (a.value_kind == VK_Q4) EW_DEC(VK_Q4);
   else EW_DEC(VK_F32);

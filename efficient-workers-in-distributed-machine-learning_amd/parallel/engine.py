@@ -219,6 +219,12 @@ class GradientExchange:
             hp.update(lr=1.0, lr_t=None)
         return hp
 
+    def _advance_key(self, bi: int):
+        """The device RNG key state when bucket ``bi``'s receive side is the step's last kernel
+        (it then moves the key on to the next step), else None."""
+        adv = self.dev_key_advance and self.use_dev_key and bi == self.nb - 1
+        return self.key_state if adv else None
+
     def _alloc_payloads(self):
         for b in self.flat.buckets:
             P = self.codec.payload_bytes(b.index)
@@ -389,13 +395,12 @@ class GradientExchange:
                        stamps=self.stamps[bi] if self.stamps is not None else None)
         apply = None
         if self.local_apply:  # world of one: the write pass applies the update (no decode)
-            adv = self.dev_key_advance and self.use_dev_key and bi == self.nb - 1
             o = self.opt
             hp = o.hparams() if self.local_apply_dense else self._apply_hp(bi)
             apply = dict(param=self.flat.data_view(b), shadow=self.flat.shadow_view(b),
                          lr=hp["lr"], lr_tensor=hp.get("lr_t"),
                          grad_scale=self.predivide / self.N,
-                         key_state=self.key_state if adv else None, key_seed=self.codec.seed,
+                         key_state=self._advance_key(bi), key_seed=self.codec.seed,
                          key_rank=self.comm.rank)
             if self.local_apply_dense:  # the receiver's momentum SGD over every element
                 apply.update(mom=o.mom[b.start:b.start + b.length], momentum=hp["momentum"],
@@ -501,41 +506,34 @@ class GradientExchange:
                 elif self.local_apply:
                     continue  # applied by the encode's write pass (enable_local_apply)
                 elif self.vote:  # count the votes; p -= lr * (majority or average + wd * p)
-                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     self.codec.decode_apply_vote(b.index, recv, self.flat.data_view(b),
                                                  opt.hparams(), shadow=self.flat.shadow_view(b),
-                                                 key_state=self.key_state if adv else None,
+                                                 key_state=self._advance_key(b.index),
                                                  rank=self.comm.rank)
                 elif self.onebit_lamb:  # ... and the fresh variance, the factor, r_frozen * f
-                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     sl = slice(b.start, b.start + b.length)
                     self.codec.decode_apply_onebit_lamb(
                         b.index, recv, scale, self.flat.data_view(b), opt.exp_avg[sl],
                         opt.exp_avg_sq[sl], opt.exp_avg_sq_fresh[sl],
                         opt.hparams(b.start, b.length), shadow=self.flat.shadow_view(b),
-                        key_state=self.key_state if adv else None, rank=self.comm.rank)
+                        key_state=self._advance_key(b.index), rank=self.comm.rank)
                 elif self.onebit:  # exp_avg = mean of the decoded momenta; frozen-variance step
-                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
                     sl = slice(b.start, b.start + b.length)
                     self.codec.decode_apply_onebit(b.index, recv, scale, self.flat.data_view(b),
                                                    opt.exp_avg[sl], opt.exp_avg_sq[sl],
                                                    opt.hparams(),
                                                    shadow=self.flat.shadow_view(b),
-                                                   key_state=self.key_state if adv else None,
+                                                   key_state=self._advance_key(b.index),
                                                    rank=self.comm.rank)
                 elif getattr(opt, "fusable", False):
-                    adv = self.dev_key_advance and self.use_dev_key and b.index == self.nb - 1
-                    hp, mom = opt.hparams(), opt.mom[b.start:b.start + b.length]
-                    if self.dgc:  # momentum and weight decay already ran on the sender
-                        hp = dict(hp, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                                  nesterov=False)
-                        if not self.dgc_mask:  # ... and the lr: p -= mean(sent)
-                            hp.update(lr=1.0, lr_t=None)
-                        mom = None
+                    if self.dgc:  # momentum, weight decay (and unmasked: the lr) ran on the sender
+                        hp, mom = self._apply_hp(b.index), None
+                    else:
+                        hp, mom = opt.hparams(), opt.mom[b.start:b.start + b.length]
                     self.codec.decode_apply_sgd(b.index, recv, scale, self.flat.data_view(b),
                                                 mom, hp, opt.first,
                                                 shadow=self.flat.shadow_view(b),
-                                                key_state=self.key_state if adv else None,
+                                                key_state=self._advance_key(b.index),
                                                 rank=self.comm.rank)
                 else:
                     gv = self.flat.grad_view(b)

@@ -292,12 +292,11 @@ def test_bad_operands_rejected():
         C.sign_encode(ptrs, mask, 0, dp.chunks.data_ptr(), pay.data_ptr(), *enc,
                       dp.chunks.data_ptr(), lay.nbytes, 1, KEY)
     dec = (plan.num_chunks, lay.scales, lay.codes)
-    tail = (0.0, 0.0, 0.0, 0.0, 1.0, 0, 0, 0, stream, 0, 0, 0, 0)
     with pytest.raises(RuntimeError, match="missing table"):
-        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, 0, *dec, 0, 0, g.data_ptr(), 0, *tail,
-                            0, 0, 1, KEY)
+        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, 0, *dec,
+                            C.StepArgs(grad_out=g.data_ptr()), stream, 0, 0, 1, KEY)
     with pytest.raises(RuntimeError, match="misaligned"):
-        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, dp.chunks.data_ptr(), *dec, 0, 0,
-                            g.data_ptr() + 4, 0, *tail, 0, 0, 1, KEY)
+        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, dp.chunks.data_ptr(), *dec,
+                            C.StepArgs(grad_out=g.data_ptr() + 4), stream, 0, 0, 1, KEY)
     torch.cuda.synchronize()
     assert not pay.any() and not g.any()  # nothing ran
