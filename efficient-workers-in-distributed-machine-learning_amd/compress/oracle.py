@@ -1148,6 +1148,43 @@ def clip_grad_norm_(grads, max_norm: float):
     return norm, coef
 
 
+OUTER_KINDS = ("sgd", "nesterov")
+
+
+def outer_apply(anchor, data, momentum, delta, lr, mu, nesterov, shadow=None, stats=None):
+    """Local SGD's outer step on the flat fp32 views, in place (the CPU path and the definition of
+    ``ops/csrc/outer.hip``'s arithmetic; every product and sum rounded on its own)::
+
+        u      = u * mu + d
+        s      = d + u * mu        (nesterov)      |      s = u
+        anchor = anchor + lr * s
+        data   = anchor            (and the bf16 shadow, rounded to nearest even)
+
+    ``torch.optim.SGD(lr, momentum=mu, nesterov=...)`` on the pseudo-gradient ``-d`` with the
+    momentum buffer starting from the first gradient (= from zero, dampening 0): heavy ball is
+    SlowMo / BMUF, Nesterov with 0.7 / 0.9 DiLoCo.  With ``lr = 1, mu = 0`` and ``sgd`` it is
+    ``anchor + d`` bit for bit (``u * 0`` is +0, so a ``d`` of -0 enters as +0: that changes a bit
+    only where ``anchor`` itself is -0).
+
+    ``stats`` (fp32 ``[ceil(n / 8192), 2]``): per row of 8192 elements the sums of squares of
+    ``d`` and of the new ``u``, formed in fp64 here (the kernel's fp32 tree is within
+    ``ops.CLIP_SUM_CHAIN + 1`` roundings of it)."""
+    lr, mu = float(np.float32(lr)), float(np.float32(mu))
+    d = delta.to(torch.float32)
+    momentum.copy_(momentum * mu + d)
+    s = d + momentum * mu if nesterov else momentum
+    anchor.copy_(anchor + s * lr)
+    data.copy_(anchor)
+    if shadow is not None:
+        shadow.copy_(anchor)
+    if stats is not None:
+        rows = stats.shape[0]
+        pad = rows * CHUNK - d.numel()
+        for k, v in enumerate((d, momentum)):
+            sq = torch.nn.functional.pad(v.double(), (0, pad)).view(rows, CHUNK)
+            stats[:, k] = (sq * sq).sum(1).to(torch.float32)
+
+
 # ---------------------------------------------------------------------------------------------
 # PowerSGD (Vogels et al., NeurIPS 2019; torch's ``powerSGD_hook``): rank-r factors of the
 # error-compensated gradient matrices of one bucket (``plan.LowRankPlan``).  The CPU path and the

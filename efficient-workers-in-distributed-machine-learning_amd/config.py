@@ -85,6 +85,11 @@ class Config:
     sync_mode: str = "grad"  # grad: compressed gradient on sync steps | model: compressed delta
     sync_mode_default: bool = True  # --sync-mode not given (--method 6 then selects 'model')
     select_best: bool = False  # method 6: adopt the weights of the best-accuracy rank at sync
+    # local SGD in model mode: none | sgd (SlowMo / BMUF: heavy-ball momentum on the averaged
+    # delta) | nesterov (DiLoCo: 0.7 / 0.9).  anchor += outer_lr * step(momentum, delta)
+    outer_optimizer: str = "none"
+    outer_lr: Optional[float] = None  # None: 1.0; > 0
+    outer_momentum: Optional[float] = None  # None: 0.0; in [0, 1)
     # None (auto): on for the top-k codecs -- top-k at 1 % without error feedback trains 10-80x
     # slower than dense (profiles/validation/ef_stability_r03.md) -- and for the sign codec
     # (scaled sign is biased without its residual), off otherwise;
@@ -491,6 +496,35 @@ class Config:
         elif c.clip_scale_world:
             raise ValueError("--clip-scale-world divides the --clip-grad-norm threshold by "
                              "sqrt(N): it needs --clip-grad-norm")
+        if c.outer_optimizer not in ("none", "sgd", "nesterov"):
+            raise ValueError("--outer-optimizer must be none, sgd or nesterov")
+        if c.outer_optimizer != "none":
+            # SlowMo / BMUF (sgd) and DiLoCo (nesterov): the averaged model delta of a sync steps
+            # the common anchor as a pseudo-gradient (parallel/local_sgd.py, ops/csrc/outer.hip)
+            if c.outer_lr is None:
+                c.outer_lr = 1.0
+            if c.outer_momentum is None:
+                c.outer_momentum = 0.0
+            why = None
+            if c.sync_every <= 1:
+                why = ("steps on the model delta of H local steps: it needs --sync-every > 1")
+            elif c.sync_mode != "model":
+                why = ("steps on the averaged model delta: --sync-mode grad exchanges a gradient "
+                       "and re-broadcasts the replicas, there is no delta (it needs --sync-mode "
+                       "model)")
+            elif not (0.0 < float(c.outer_lr) < float("inf")):
+                why = f"needs --outer-lr > 0, not {c.outer_lr!r}"
+            elif not 0.0 <= float(c.outer_momentum) < 1.0:
+                why = f"needs --outer-momentum in [0, 1), not {c.outer_momentum!r}"
+            elif c.outer_optimizer == "nesterov" and float(c.outer_momentum) == 0.0:
+                why = ("looks ahead along its momentum: it needs --outer-momentum > 0 (torch's "
+                       "rule for nesterov)")
+            if why is not None:
+                raise ValueError(f"--outer-optimizer {c.outer_optimizer} " + why)
+        elif c.outer_lr is not None:
+            raise ValueError("--outer-lr belongs to --outer-optimizer sgd / nesterov")
+        elif c.outer_momentum is not None:
+            raise ValueError("--outer-momentum belongs to --outer-optimizer sgd / nesterov")
         if c.ef_mode == "ef21" and c.error_feedback and c.device != "cpu" and not c.no_cuda:
             import os
 
@@ -572,6 +606,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--sync-every", type=int, default=d.sync_every)
     a("--sync-mode", type=str, default=None, choices=["grad", "model"])
     a("--select-best", action="store_true", default=False)
+    a("--outer-optimizer", type=str, default=d.outer_optimizer,
+      choices=["none", "sgd", "nesterov"])
+    a("--outer-lr", type=float, default=None)
+    a("--outer-momentum", type=float, default=None)
     a("--error-feedback", dest="error_feedback", action="store_true", default=None)
     a("--no-error-feedback", dest="error_feedback", action="store_false")
     a("--ef-mode", type=str, default=d.ef_mode, choices=["dgc", "plain", "local", "ef21"])

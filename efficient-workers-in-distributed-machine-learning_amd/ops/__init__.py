@@ -935,6 +935,50 @@ def lion_flat(param, exp_avg, grad, lr, beta1, beta2, weight_decay=0.0, grad_sca
                 _stream(), _lrp(lr_tensor))
 
 
+OUTER_ROW = 8192  # elements per block of k_outer_apply, and per row of its outer_stats
+
+
+def outer_rows(n: int) -> int:
+    """Rows of ``outer_stats`` (fp32 ``[rows, 2]``) for a flat range of ``n`` elements."""
+    return (int(n) + OUTER_ROW - 1) // OUTER_ROW
+
+
+def outer_apply(anchor, data, momentum, delta, lr, mu, nesterov, shadow=None, stats=None):
+    """Local SGD's outer step over flat fp32 buffers in one launch (``csrc/outer.hip``; bitwise
+    ``compress/oracle.py outer_apply``): ``momentum = momentum * mu + delta``, ``anchor += lr *
+    (delta + momentum * mu if nesterov else momentum)``, ``data = anchor`` (and its bf16
+    ``shadow``).  Any ``numel`` (16-byte accesses, scalar tail).  ``stats`` (fp32 ``[outer_rows(n),
+    2]``): per row of 8192 elements the sums of squares of ``delta`` and of the new ``momentum``,
+    through ``k_clip_norm``'s tree (``CLIP_SUM_CHAIN``)."""
+    C = require()
+    _check(anchor, torch.float32, "anchor")
+    _check(data, torch.float32, "data")
+    _check(momentum, torch.float32, "momentum")
+    _check(delta, torch.float32, "delta")
+    n = anchor.numel()
+    if n < 1 or data.numel() != n or momentum.numel() != n or delta.numel() != n:
+        raise ValueError("flat buffers must have equal, non-zero numel")
+    if len({t.data_ptr() for t in (anchor, data, momentum, delta)}) != 4:
+        raise ValueError("anchor, data, momentum and delta must be four buffers")
+    if shadow is not None:
+        _check(shadow, torch.bfloat16, "shadow", align=8)
+        if shadow.numel() != n:
+            raise ValueError("shadow must match anchor")
+    rows = 0
+    if stats is not None:
+        _check(stats, torch.float32, "stats", align=4)
+        rows = outer_rows(n)
+        if stats.dim() != 2 or tuple(stats.shape) != (rows, 2):
+            raise ValueError(f"stats must be fp32 [{rows}, 2], one row per {OUTER_ROW} elements")
+    lr, mu = float(lr), float(mu)
+    if not (0.0 < lr < float("inf")):
+        raise ValueError("outer lr must be finite and > 0")
+    if not 0.0 <= mu < 1.0:
+        raise ValueError("outer momentum must be in [0, 1)")
+    C.outer_apply(_ptr(anchor), _ptr(data), _ptr(momentum), _ptr(delta), _ptr(shadow),
+                  _ptr(stats), n, rows, lr, mu, int(bool(nesterov)), _stream())
+
+
 def _check_vote_layout(dp, layout):
     if layout.kind != "vote":
         raise ValueError(f"vote codec given a {layout.kind!r} layout")

@@ -699,6 +699,26 @@ PYBIND11_MODULE(_C, m) {
           else throw std::runtime_error("ewdml clip: unknown op");
         });
 
+  m.def("outer_apply",
+        [](uintptr_t anchor, uintptr_t data, uintptr_t momentum, uintptr_t delta,
+           uintptr_t shadow, uintptr_t stats, long long n, long long stats_rows, float lr,
+           float mu, int nesterov, uintptr_t stream) {
+          OuterArgs a{};
+          a.anchor = anchor;
+          a.data = data;
+          a.momentum = momentum;
+          a.delta = delta;
+          a.shadow = shadow;
+          a.stats = stats;
+          a.stream = stream;
+          a.n = n;
+          a.stats_rows = stats_rows;
+          a.lr = lr;
+          a.mu = mu;
+          a.nesterov = nesterov;
+          ew_outer_apply(a);
+        });
+
   m.def("cast_scale", &ew_cast_scale);
 
   m.def("pack_grads",

@@ -366,6 +366,18 @@ struct ClipArgs {
 void ew_clip_norm(const ClipArgs& a);
 void ew_clip_scale(const ClipArgs& a);
 
+// Local SGD's outer optimizer over a flat range (outer.hip k_outer_apply): u = u * mu + delta;
+// s = nesterov ? delta + u * mu : u; anchor += lr * s; data = anchor (and its bf16 shadow).  n
+// need not be a multiple of 4 (scalar tail).  stats (nullable): fp32 [stats_rows, 2], one row per
+// 8192 elements = {sum of delta^2, sum of the new u^2}.
+struct OuterArgs {
+  uintptr_t anchor, data, momentum, delta, shadow, stats, stream;
+  long long n, stats_rows;
+  float lr, mu;
+  int nesterov;
+};
+void ew_outer_apply(const OuterArgs& a);
+
 size_t ew_topk_scratch_bytes(int num_tensors, int num_chunks, long long bucket_len,
                              long long total_cap);
 std::vector<int> ew_topk_stats(uintptr_t scratch, int num_tensors, int num_chunks);

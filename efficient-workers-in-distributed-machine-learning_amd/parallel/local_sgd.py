@@ -31,15 +31,18 @@ a gather into ``flat.grad`` per bucket for other optimizers -- never the per-par
 accumulate-adds of attached ``.grad`` views.  The model delta of a sync step is staged in
 ``flat.grad`` and the wrapped exchange encodes from there (``src_flat``).
 """
+import os
+
 import torch
 
 from .. import ops
+from ..compress import oracle
 from .engine import StepStats, sync_buffers
 
 
 class LocalSGDExchange:
     def __init__(self, inner, every: int, mode: str = "grad", select_best: bool = False,
-                 score_fn=None):
+                 score_fn=None, outer=None):
         if every < 1:
             raise ValueError("sync_every must be >= 1")
         self.inner, self.every, self.mode = inner, every, mode
@@ -47,6 +50,33 @@ class LocalSGDExchange:
         self.flat, self.comm, self.opt = inner.flat, inner.comm, inner.opt
         self.step_idx = 0
         self.anchor = self.flat.data.clone() if mode == "model" else None
+        # the outer optimizer (kind, lr, mu): the averaged delta steps the anchor as a
+        # pseudo-gradient.  Its momentum is shared state (zeros at the start, the same on every
+        # rank); both buffers live here, outside any graph pool
+        self.outer = None
+        self.outer_momentum = self.outer_stats = None
+        if outer is not None:
+            kind, lr, mu = outer
+            lr, mu = float(lr), float(mu)
+            if kind not in oracle.OUTER_KINDS:
+                raise ValueError(f"outer optimizer must be one of {oracle.OUTER_KINDS}, not "
+                                 f"{kind!r}")
+            if mode != "model":
+                raise ValueError("the outer optimizer steps on the model delta: it needs "
+                                 "mode='model'")
+            if not 0.0 < lr < float("inf"):
+                raise ValueError("outer lr must be finite and > 0")
+            if not 0.0 <= mu < 1.0:
+                raise ValueError("outer momentum must be in [0, 1)")
+            if kind == "nesterov" and mu == 0.0:
+                raise ValueError("nesterov needs an outer momentum > 0")
+            self.outer = (kind, lr, mu)
+            data = self.flat.data
+            self.outer_momentum = torch.zeros_like(data)
+            self.outer_stats = torch.zeros((ops.outer_rows(data.numel()), 2),
+                                           dtype=torch.float32, device=data.device)
+            # the torch oracle on the CPU, and on the device under EWDML_ORACLE=1
+            self._outer_hip = data.is_cuda and os.environ.get("EWDML_ORACLE") != "1"
         self.last = StepStats()
         self.best_rank_history = []
         self.best_t = None  # device index of the last sync's winner (model mode)
@@ -106,13 +136,42 @@ class LocalSGDExchange:
                     stats.wire_bytes_recv += (self.comm.world - 1) * buf
                 else:
                     self.inner.decode_average()
-                torch.add(self.anchor, self.flat.grad, out=self.flat.data)
-                self.anchor.copy_(self.flat.data)
-                self.flat.sync_shadow()
+                if self.outer is None:
+                    torch.add(self.anchor, self.flat.grad, out=self.flat.data)
+                    self.anchor.copy_(self.flat.data)
+                    self.flat.sync_shadow()
+                else:
+                    self._outer_step()
                 if self.clock is not None:
                     self.clock.mark("decode_update")
         self.last = stats
         self.step_idx += 1
+
+    def _outer_step(self):
+        """The sync step's tail with an outer optimizer: the decoded delta in ``flat.grad`` moves
+        the momentum, the anchor, the weights and their bf16 copy in one launch over the whole
+        flat buffer (``ops.outer_apply``; ``oracle.outer_apply`` on the CPU)."""
+        kind, lr, mu = self.outer
+        flat = self.flat
+        fn = ops.outer_apply if self._outer_hip else oracle.outer_apply
+        fn(self.anchor, flat.data, self.outer_momentum, flat.grad, lr, mu, kind == "nesterov",
+           shadow=flat.shadow, stats=self.outer_stats)
+
+    def _outer_norm(self, k: int):
+        if self.outer is None or self.step_idx < self.every:  # no sync yet
+            return None
+        return float(torch.sqrt(self.outer_stats[:, k].double().sum()))
+
+    @property
+    def outer_delta_norm(self):
+        """L2 norm of the last sync's averaged (or winning) delta; ``None`` before the first sync
+        or without an outer optimizer.  Read at log time: it synchronises."""
+        return self._outer_norm(0)
+
+    @property
+    def outer_momentum_norm(self):
+        """L2 norm of the outer momentum after the last sync (see :attr:`outer_delta_norm`)."""
+        return self._outer_norm(1)
 
     def local_step(self):
         """Optimizer step with this rank's own gradient."""

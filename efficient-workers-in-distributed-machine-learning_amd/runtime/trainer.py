@@ -306,8 +306,12 @@ class Trainer:
                                                                      not cfg.select_best)
                                              else "plain", clipper=self.clipper)
             if cfg.sync_every > 1 or cfg.select_best:
+                outer = None
+                if cfg.outer_optimizer != "none":  # SlowMo / BMUF / DiLoCo on the averaged delta
+                    outer = (cfg.outer_optimizer, cfg.outer_lr, cfg.outer_momentum)
                 self.exchange = LocalSGDExchange(self.exchange, cfg.sync_every, cfg.sync_mode,
-                                                 cfg.select_best, score_fn=self._holdout_score)
+                                                 cfg.select_best, score_fn=self._holdout_score,
+                                                 outer=outer)
 
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(cfg.amp)
         if self.amp_kept_fp32:
@@ -1070,6 +1074,8 @@ class Trainer:
                 extra[name] = allr
             if ex.anchor is not None:
                 extra["local_anchor"] = ex.anchor
+            if ex.outer_momentum is not None:  # shared like the anchor: one copy, rank 0's
+                extra["outer_momentum"] = ex.outer_momentum
             extra["local_syncs"] = inner.step_idx
         return extra
 
@@ -1135,6 +1141,16 @@ class Trainer:
             self.flat.sync_shadow()
             if ex.anchor is not None and ext.get("local_anchor") is not None:
                 ex.anchor.copy_(ext["local_anchor"].to(self.device))
+            if ex.outer_momentum is not None:
+                if ext.get("outer_momentum") is not None:
+                    ex.outer_momentum.copy_(ext["outer_momentum"].to(self.device))
+                else:
+                    ex.outer_momentum.zero_()
+                    if self.rank == 0:
+                        import warnings
+
+                        warnings.warn("resume: the checkpoint holds no outer_momentum, the outer "
+                                      "optimizer starts from zeros")
             if "local_syncs" in ext:
                 inner.step_idx = int(ext["local_syncs"])
         if hasattr(self.exchange, "step_idx"):
@@ -1216,6 +1232,12 @@ class Trainer:
                     clipped = self.clipper.last()
                     if clipped is not None:
                         rec["grad_norm"], rec["clip_coef"] = clipped
+                # outer optimizer: the last sync's delta and momentum norms (read only here)
+                if self.local_sgd and self.exchange.outer is not None:
+                    dn = self.exchange.outer_delta_norm
+                    if dn is not None:
+                        rec["outer_delta_norm"] = dn
+                        rec["outer_momentum_norm"] = self.exchange.outer_momentum_norm
                 rec["bytes_sent_total"] = acc["bytes_sent"]
                 rec["bytes_recv_total"] = acc["bytes_recv"]
                 rec["payload_bytes_total"] = acc["payload_bytes"]
