@@ -84,6 +84,27 @@ def _ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _args(cls, **fields):
+    """An argument struct of the extension (``csrc/ewdml_ops.h``, bound as a class in
+    ``csrc/bindings.cpp``) filled by field name: every field not named stays zero, and a name the
+    struct does not have raises ``AttributeError``."""
+    a = cls()
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
+def _tables(dp):
+    """The chunk and tensor tables of a bucket's ``DevicePlan``, as argument fields."""
+    return dict(chunks=_ptr(dp.chunks), num_chunks=dp.plan.num_chunks,
+                tensors=_ptr(dp.tensors), num_tensors=dp.plan.num_tensors)
+
+
+def _rows(recv, nranks, stride):
+    """The gathered payloads a receive side reads: ``nranks`` rows ``stride`` bytes apart."""
+    return dict(recv=_ptr(recv), nranks=nranks, stride=stride)
+
+
 def _check(t, dtype, name, align=16, dense=False):
     """``dense``: any non-overlapping dense layout is fine (the kernel reads the tensor in memory
     order, e.g. a channels_last conv-weight gradient matching its channels_last parameter)."""
@@ -240,10 +261,12 @@ def _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_deca
     if not apply and grad_out is None:
         raise ValueError("nothing to do: pass param/mom and/or grad_out")
     _check_shadow(dp, shadow)
-    return require().StepArgs(_ptr(param), _ptr(mom) if apply else 0, _ptr(grad_out),
-                              _ptr(shadow), lr, momentum, dampening, weight_decay, grad_scale,
-                              int(nesterov), int(first), int(apply), _keyp(key_state),
-                              key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, _lrp(lr_tensor))
+    return require().StepArgs(
+        param=_ptr(param), mom=_ptr(mom) if apply else 0, grad_out=_ptr(grad_out),
+        shadow=_ptr(shadow), lr=lr, momentum=momentum, dampening=dampening,
+        weight_decay=weight_decay, grad_scale=grad_scale, nesterov=int(nesterov),
+        first=int(first), apply=int(apply), key_state=_keyp(key_state),
+        key_seed=key_seed & 0xFFFFFFFF, key_rank=key_rank & 0xFFFFFFFF, lr_ptr=_lrp(lr_tensor))
 
 
 def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
@@ -288,15 +311,18 @@ def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, k
         if wd != 0.0:
             par = dgc["param"]
             _check_bucket(dp, par, "param")
-    C.topk_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(dp.tensors), _ptr(dp.scratch),
-                  _ptr(payload), layout.nbytes, dp.plan.num_tensors, dp.plan.num_chunks,
-                  layout.scales, layout.counts, layout.idx, layout.codes, vk,
-                  1 if norm == "l2" else 0, float(levels), float(1.0 / levels), key & 0xFFFFFFFF,
-                  dp.plan.bucket_offset & 0xFFFFFFFF, _keyp(key_tensor), _stream(), _ptr(vel),
-                  _ptr(par), mom, damp1, wd, nest, layout.bitmap, dmask, _lrp(lrt), dp.plan.length,
-                  _ptr(dp.cblocks), dp.plan.num_cblocks, int(_TOPK_PREDICT), int(_LB_FAULT[0]),
-                  int(max(dp.plan.ks)) if dp.plan.ks else 0, *_apply_args(dp, apply, norm),
-                  _stamps_ptr(dp, dgc))
+    C.topk_encode(_args(
+        C.TopkEncodeArgs, resid=_ptr(resid), scratch=_ptr(dp.scratch), payload=_ptr(payload),
+        payload_bytes=layout.nbytes, scales_off=layout.scales, counts_off=layout.counts,
+        idx_off=layout.idx, codes_off=layout.codes, bitmap_off=layout.bitmap, value_kind=vk,
+        norm_l2=1 if norm == "l2" else 0, levels=float(levels), inv_levels=float(1.0 / levels),
+        key=key & 0xFFFFFFFF, bucket_offset=dp.plan.bucket_offset & 0xFFFFFFFF,
+        key_ptr=_keyp(key_tensor), stream=_stream(), vel=_ptr(vel), param=_ptr(par),
+        dgc_momentum=mom, dgc_damp1=damp1, dgc_wd=wd, dgc_nesterov=nest, dgc_mask=dmask,
+        dgc_lr_ptr=_lrp(lrt), bucket_len=dp.plan.length, cblocks=_ptr(dp.cblocks),
+        num_cblocks=dp.plan.num_cblocks, predict=int(_TOPK_PREDICT), lb_fault=int(_LB_FAULT[0]),
+        max_k=int(max(dp.plan.ks)) if dp.plan.ks else 0, **_tables(dp),
+        **_apply_args(dp, apply, norm), dgc_stamps=_stamps_ptr(dp, dgc)), ptrs, mask)
 
 
 def _stamps_ptr(dp, dgc):
@@ -318,8 +344,9 @@ def topk_one_launch(dp) -> bool:
 
 
 def _apply_args(dp, apply, norm):
+    """The ``apply_*`` fields of a top-k encode (``apply`` None: off, none of them set)."""
     if apply is None:
-        return (0, 0, 0.0, 0, 1.0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0, 0)
+        return {}
     if not _TOPK_PREDICT or norm != "max":
         raise ValueError("the write-pass apply needs the predictive (max-norm) encode")
     param = apply["param"]
@@ -335,12 +362,17 @@ def _apply_args(dp, apply, norm):
             raise ValueError("the dense write-pass apply needs the momentum buffer and the "
                              "one-launch encode")
         _check_bucket(dp, mom, "mom")
-    return (_ptr(param), _ptr(apply.get("shadow")), float(apply["lr"]),
-            _lrp(apply.get("lr_tensor")), float(apply.get("grad_scale", 1.0)), _ptr(ks),
-            int(apply.get("key_seed", 0)) & 0xFFFFFFFF, int(apply.get("key_rank", 0)) & 0xFFFFFFFF,
-            int(dense), _ptr(mom), float(apply.get("momentum", 0.0)),
-            float(apply.get("dampening", 0.0)), float(apply.get("weight_decay", 0.0)),
-            int(bool(apply.get("nesterov", False))), int(bool(apply.get("first", False))))
+    return dict(
+        apply_param=_ptr(param), apply_shadow=_ptr(apply.get("shadow")),
+        apply_lr=float(apply["lr"]), apply_lr_ptr=_lrp(apply.get("lr_tensor")),
+        apply_scale=float(apply.get("grad_scale", 1.0)), apply_key_state=_ptr(ks),
+        apply_key_seed=int(apply.get("key_seed", 0)) & 0xFFFFFFFF,
+        apply_key_rank=int(apply.get("key_rank", 0)) & 0xFFFFFFFF, apply_mom_set=int(dense),
+        apply_mom=_ptr(mom), apply_momentum=float(apply.get("momentum", 0.0)),
+        apply_dampening=float(apply.get("dampening", 0.0)),
+        apply_wd=float(apply.get("weight_decay", 0.0)),
+        apply_nesterov=int(bool(apply.get("nesterov", False))),
+        apply_first=int(bool(apply.get("first", False))))
 
 
 def _lrp(lr_tensor):
@@ -361,9 +393,12 @@ def topk_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
     step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
                  grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
     vk = VK_F32 if layout.kind == "topk" else (VK_Q8 if layout.bits == 8 else VK_Q4)
-    C.topk_decode_apply(_ptr(recv), nranks, layout.nbytes, _ptr(dp.chunks), _ptr(dp.tensors),
-                        dp.plan.num_chunks, layout.scales, layout.counts, layout.idx,
-                        layout.codes, vk, float(1.0 / levels), step, _stream(), layout.bitmap)
+    C.topk_decode_apply(_args(
+        C.TopkDecodeArgs, **_rows(recv, nranks, layout.nbytes), chunks=_ptr(dp.chunks),
+        tensors=_ptr(dp.tensors), num_chunks=dp.plan.num_chunks, scales_off=layout.scales,
+        counts_off=layout.counts, idx_off=layout.idx, codes_off=layout.codes,
+        bitmap_off=layout.bitmap, value_kind=vk, inv_levels=float(1.0 / levels), step=step,
+        stream=_stream()))
 
 
 def qsgd_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
@@ -375,11 +410,13 @@ def qsgd_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, k
         _check_bucket(dp, resid, "resid")
     if not (1 <= levels <= (127 if layout.bits == 8 else 7)):
         raise ValueError(f"levels={levels} does not fit {layout.bits}-bit codes")
-    C.qsgd_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(dp.tensors), _ptr(dp.scratch),
-                  _ptr(payload), layout.nbytes, dp.plan.num_tensors, dp.plan.num_chunks,
-                  layout.scales, layout.codes, layout.bits, 1 if norm == "l2" else 0,
-                  float(levels), float(1.0 / levels), key & 0xFFFFFFFF,
-                  dp.plan.bucket_offset & 0xFFFFFFFF, _keyp(key_tensor), _stream())
+    C.qsgd_encode(_args(
+        C.QsgdEncodeArgs, resid=_ptr(resid), **_tables(dp), scratch=_ptr(dp.scratch),
+        payload=_ptr(payload), payload_bytes=layout.nbytes, scales_off=layout.scales,
+        codes_off=layout.codes, bits=layout.bits, norm_l2=1 if norm == "l2" else 0,
+        levels=float(levels), inv_levels=float(1.0 / levels), key=key & 0xFFFFFFFF,
+        bucket_offset=dp.plan.bucket_offset & 0xFFFFFFFF, key_ptr=_keyp(key_tensor),
+        stream=_stream()), ptrs, mask)
 
 
 def qsgd_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom=None,
@@ -391,9 +428,11 @@ def qsgd_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
     step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
                  grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor,
                  need_mom=True)  # k_qsgd_decode_apply reads the buffer whenever it applies
-    C.qsgd_decode_apply(_ptr(recv), nranks, layout.nbytes, _ptr(dp.chunks), _ptr(dp.tensors),
-                        dp.plan.num_chunks, layout.scales, layout.codes, layout.bits,
-                        float(1.0 / levels), step, _stream())
+    C.qsgd_decode_apply(_args(
+        C.QsgdDecodeArgs, **_rows(recv, nranks, layout.nbytes), chunks=_ptr(dp.chunks),
+        tensors=_ptr(dp.tensors), num_chunks=dp.plan.num_chunks, scales_off=layout.scales,
+        codes_off=layout.codes, bits=layout.bits, inv_levels=float(1.0 / levels), step=step,
+        stream=_stream()))
 
 
 class SignTables:
@@ -444,22 +483,25 @@ def _check_sign_layout(dp, layout):
 
 
 def _sign_payload(dp, payload, layout, slots):
-    """Checks of an encode's destination; returns (bytes, scales_off, bits_off, slots, slot_end)."""
+    """Checks of an encode's destination; returns the fields that address it and the bucket."""
     if slots is not None:  # the [N, P] row buffer: every chunk goes to its slot
         sp, end = _check_slots(dp, slots, payload, "payload")
-        return payload.numel(), 0, 0, sp, end
-    _check_sign_layout(dp, layout)
-    _encode_dst(payload, layout)
-    return layout.nbytes, layout.scales, layout.codes, 0, 0
+        dst = dict(payload_bytes=payload.numel(), slots=sp, slot_end=end)
+    else:
+        _check_sign_layout(dp, layout)
+        _encode_dst(payload, layout)
+        dst = dict(payload_bytes=layout.nbytes, scales_off=layout.scales, bits_off=layout.codes)
+    return dict(dst, payload=_ptr(payload), chunks=_ptr(dp.chunks),
+                num_chunks=dp.plan.num_chunks, num_tensors=dp.plan.num_tensors)
 
 
 def _rot(rot_key, slots):
-    """(rotate, rot_key) of the sign wrappers: ``rot_key`` None is the unrotated codec."""
+    """The rotate / rot_key fields of the sign wrappers: ``rot_key`` None is the unrotated codec."""
     if rot_key is None:
-        return 0, 0
+        return {}
     if slots is not None:
         raise ValueError("the rotated sign codec has no slot-addressed (two-stage) form")
-    return 1, int(rot_key) & 0xFFFFFFFF
+    return dict(rotate=1, rot_key=int(rot_key) & 0xFFFFFFFF)
 
 
 def sign_encode(dp, grad, payload, layout, resid=None, slots=None, rot_key=None):
@@ -470,14 +512,13 @@ def sign_encode(dp, grad, payload, layout, resid=None, slots=None, rot_key=None)
     buffer and every chunk is written to its slot (``layout`` unused; pads are not written).
     ``rot_key`` (``oracle.hsign_rot_key``): the Hadamard-rotated form, ``k_hsign_encode``."""
     C = require()
-    rotate, rot_key = _rot(rot_key, slots)
+    rot = _rot(rot_key, slots)
     ptrs, mask = grad_pointers(dp, grad)
-    nbytes, so, bo, sp, end = _sign_payload(dp, payload, layout, slots)
+    dst = _sign_payload(dp, payload, layout, slots)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
-    C.sign_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), nbytes,
-                  dp.plan.num_tensors, dp.plan.num_chunks, so, bo, _stream(), sp, end,
-                  rotate, rot_key)
+    C.sign_encode(_args(C.SignEncodeArgs, resid=_ptr(resid), stream=_stream(), **dst, **rot),
+                  ptrs, mask)
 
 
 def sign_reduce_encode(dp, recv, layout, inv_n, sresid, out):
@@ -500,19 +541,23 @@ def sign_reduce_encode(dp, recv, layout, inv_n, sresid, out):
     if sresid is None:
         raise ValueError("the owner step needs the server residual")
     _check_bucket(dp, sresid, "sresid")
-    C.sign_reduce_encode(_ptr(recv), recv.shape[0], recv.shape[1], _ptr(dp.chunks),
-                         dp.plan.num_chunks, layout.scales, layout.codes, float(inv_n),
-                         _ptr(sresid), _ptr(out), out.numel(), _stream())
+    C.sign_reduce_encode(_args(
+        C.SignReduceArgs, **_rows(recv, recv.shape[0], recv.shape[1]), chunks=_ptr(dp.chunks),
+        num_chunks=dp.plan.num_chunks, scales_off=layout.scales, bits_off=layout.codes,
+        inv_n=float(inv_n), sresid=_ptr(sresid), out=_ptr(out), out_bytes=out.numel(),
+        stream=_stream()))
 
 
 def _sign_recv(dp, recv, layout, slots):
-    """Checks of a decode's source; returns (nranks, stride, scales_off, bits_off, slots,
-    slot_end)."""
+    """Checks of a decode's source; returns the fields that address it and the chunk table."""
     if slots is not None:  # the gathered [N, P] row buffer, read as one slot-addressed payload
         sp, end = _check_slots(dp, slots, recv, "recv")
-        return 1, recv.numel(), 0, 0, sp, end
-    _check_sign_layout(dp, layout)
-    return _recv_rows(recv, layout), layout.nbytes, layout.scales, layout.codes, 0, 0
+        src = dict(_rows(recv, 1, recv.numel()), slots=sp, slot_end=end)
+    else:
+        _check_sign_layout(dp, layout)
+        src = dict(_rows(recv, _recv_rows(recv, layout), layout.nbytes),
+                   scales_off=layout.scales, bits_off=layout.codes)
+    return dict(src, chunks=_ptr(dp.chunks), num_chunks=dp.plan.num_chunks)
 
 
 def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
@@ -526,12 +571,11 @@ def sign_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=
     form, ``k_hsign_decode_apply`` (the summed rows go through one inverse transform; bitwise
     ``oracle.decode_sum(..., rot_key=rot_key)``)."""
     C = require()
-    rotate, rot_key = _rot(rot_key, slots)
-    nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
+    rot = _rot(rot_key, slots)
+    src = _sign_recv(dp, recv, layout, slots)
     step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
                  grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
-    C.sign_decode_apply(_ptr(recv), nranks, stride, _ptr(dp.chunks), dp.plan.num_chunks, so, bo,
-                        step, _stream(), sp, end, rotate, rot_key)
+    C.sign_decode_apply(_args(C.SignDecodeArgs, step=step, stream=_stream(), **src, **rot))
 
 
 def _check_mx_layout(dp, layout):
@@ -559,9 +603,11 @@ def mx_encode(dp, grad, payload, layout, resid=None, soft=False):
     _encode_dst(payload, layout)
     if resid is not None:
         _check_bucket(dp, resid, "resid")
-    C.mx_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), layout.nbytes,
-                dp.plan.length, dp.plan.num_tensors, dp.plan.num_chunks, layout.scales,
-                layout.codes, layout.bits, int(bool(soft)), _stream())
+    C.mx_encode(_args(
+        C.MxEncodeArgs, resid=_ptr(resid), chunks=_ptr(dp.chunks), payload=_ptr(payload),
+        payload_bytes=layout.nbytes, length=dp.plan.length, num_tensors=dp.plan.num_tensors,
+        num_chunks=dp.plan.num_chunks, scales_off=layout.scales, codes_off=layout.codes,
+        bits=layout.bits, soft=int(bool(soft)), stream=_stream()), ptrs, mask)
 
 
 def mx_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
@@ -576,9 +622,11 @@ def mx_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.
     nranks = _recv_rows(recv, layout)
     step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
                  grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
-    C.mx_decode_apply(_ptr(recv), nranks, layout.nbytes, dp.plan.length, _ptr(dp.chunks),
-                      dp.plan.num_chunks, layout.scales, layout.codes, layout.bits,
-                      int(bool(soft)), step, _stream())
+    C.mx_decode_apply(_args(
+        C.MxDecodeArgs, **_rows(recv, nranks, layout.nbytes), length=dp.plan.length,
+        chunks=_ptr(dp.chunks), num_chunks=dp.plan.num_chunks, scales_off=layout.scales,
+        codes_off=layout.codes, bits=layout.bits, soft=int(bool(soft)), step=step,
+        stream=_stream()))
 
 
 def _check_tern_layout(dp, layout):
@@ -610,11 +658,12 @@ def tern_encode(dp: DevicePlan, grad, payload, layout, clip: float, key: int, re
         _check_bucket(dp, resid, "resid")
     if not float(clip) >= 0.0:
         raise ValueError("tern clip must be >= 0")
-    C.tern_encode(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(dp.tensors), _ptr(dp.scratch),
-                  _ptr(payload), layout.nbytes, dp.plan.total_codes, dp.plan.num_tensors,
-                  dp.plan.num_chunks, layout.scales, layout.codes, float(clip),
-                  key & 0xFFFFFFFF, dp.plan.bucket_offset & 0xFFFFFFFF, _keyp(key_tensor),
-                  _stream())
+    C.tern_encode(_args(
+        C.TernEncodeArgs, resid=_ptr(resid), **_tables(dp), scratch=_ptr(dp.scratch),
+        payload=_ptr(payload), payload_bytes=layout.nbytes, total_codes=dp.plan.total_codes,
+        scales_off=layout.scales, codes_off=layout.codes, clip=float(clip),
+        key=key & 0xFFFFFFFF, bucket_offset=dp.plan.bucket_offset & 0xFFFFFFFF,
+        key_ptr=_keyp(key_tensor), stream=_stream()), ptrs, mask)
 
 
 def tern_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
@@ -629,9 +678,10 @@ def tern_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_o
     nranks = _recv_rows(recv, layout)
     step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
                  grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
-    C.tern_decode_apply(_ptr(recv), nranks, layout.nbytes, dp.plan.total_codes, _ptr(dp.chunks),
-                        _ptr(dp.tensors), dp.plan.num_tensors, dp.plan.num_chunks, layout.scales,
-                        layout.codes, step, _stream())
+    C.tern_decode_apply(_args(
+        C.TernDecodeArgs, **_rows(recv, nranks, layout.nbytes), **_tables(dp),
+        total_codes=dp.plan.total_codes, scales_off=layout.scales, codes_off=layout.codes,
+        step=step, stream=_stream()))
 
 
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
@@ -642,7 +692,7 @@ def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
     ``slots``: as in :func:`sign_encode`."""
     C = require()
     ptrs, mask = grad_pointers(dp, grad)
-    nbytes, so, bo, sp, end = _sign_payload(dp, payload, layout, slots)
+    dst = _sign_payload(dp, payload, layout, slots)
     if resid is None or exp_avg is None:
         raise ValueError("the momentum encode needs the residual and exp_avg")
     _check_bucket(dp, resid, "resid")
@@ -653,10 +703,9 @@ def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
         _check_bucket(dp, param, "param")
     else:
         param = None
-    C.sign_encode_momentum(ptrs, mask, _ptr(resid), _ptr(dp.chunks), _ptr(payload), nbytes,
-                           dp.plan.num_tensors, dp.plan.num_chunks, so, bo,
-                           _ptr(exp_avg), _ptr(param), float(beta1), float(weight_decay),
-                           _stream(), sp, end)
+    C.sign_encode(_args(
+        C.SignEncodeArgs, resid=_ptr(resid), mom_exp_avg=_ptr(exp_avg), mom_param=_ptr(param),
+        mom_beta1=float(beta1), mom_wd=float(weight_decay), stream=_stream(), **dst), ptrs, mask)
 
 
 def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_step,
@@ -668,7 +717,7 @@ def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_s
     step + 1 and derives ``lr_step = lr * sqrt(1 - beta2^freeze_step) / (1 - beta1^t)`` on the
     device (``lr_step`` is then ignored).  ``slots``: as in :func:`sign_decode_apply`."""
     C = require()
-    nranks, stride, so, bo, sp, end = _sign_recv(dp, recv, layout, slots)
+    src = _sign_recv(dp, recv, layout, slots)
     for t, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         if t is None:
             raise ValueError(f"the 1-bit Adam step needs {nm}")
@@ -678,12 +727,13 @@ def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_s
     if step is not None:
         _check(step, torch.int32, "step", align=4)
     _check_shadow(dp, shadow)
-    C.sign_decode_onebit(_ptr(recv), nranks, stride, _ptr(dp.chunks),
-                         dp.plan.num_chunks, so, bo, _ptr(param),
-                         _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(shadow), float(lr_step),
-                         float(inv_n), float(eps), float(beta1), float(beta2), int(freeze_step),
-                         _ptr(step), float(lr), _lrp(lr_tensor), _stream(), _keyp(key_state),
-                         key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF, sp, end)
+    C.sign_decode_onebit(_args(
+        C.SignOnebitArgs, **src, param=_ptr(param), exp_avg=_ptr(exp_avg),
+        exp_avg_sq=_ptr(exp_avg_sq), shadow=_ptr(shadow), lr_step=float(lr_step),
+        inv_n=float(inv_n), eps=float(eps), beta1=float(beta1), beta2=float(beta2),
+        freeze_step=int(freeze_step), step=_ptr(step), lr=float(lr), lr_ptr=_lrp(lr_tensor),
+        stream=_stream(), key_state=_keyp(key_state), key_seed=key_seed & 0xFFFFFFFF,
+        key_rank=key_rank & 0xFFFFFFFF))
 
 
 class OnebitLambTables:
@@ -725,7 +775,7 @@ def onebit_lamb_step(lt: OnebitLambTables, recv, layout, param, exp_avg, exp_avg
     tensor, optional): the kernels read ``t = step + 1`` and derive ``bc1`` on the device."""
     C = require()
     dp = lt.dp
-    nranks, stride, so, bo, _, _ = _sign_recv(dp, recv, layout, None)
+    src = _sign_recv(dp, recv, layout, None)
     for x, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"),
                   (exp_avg_sq_fresh, "exp_avg_sq_fresh")):
         if x is None:
@@ -737,17 +787,21 @@ def onebit_lamb_step(lt: OnebitLambTables, recv, layout, param, exp_avg, exp_avg
         _check(step, torch.int32, "step", align=4)
     _check_shadow(dp, shadow)
     b1, b2 = betas
-    args = (_ptr(recv), nranks, stride, _ptr(dp.chunks), dp.plan.num_chunks, _ptr(dp.tensors),
-            dp.plan.num_tensors, so, bo, _ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq),
-            _ptr(exp_avg_sq_fresh), _ptr(shadow), _ptr(lt.adapt), _ptr(lt.partials),
-            _ptr(lt.r_frozen), _ptr(lt.last_factor), lt.last_factor.stride(0), _ptr(lt.ratio), float(lr), float(inv_n),
-            float(b1), float(b2), float(eps), float(weight_decay),
-            float(1.0 - b1 ** t if bc1 is None else bc1), 1.0 - b2 ** int(freeze_step),
-            float(factor_min), float(factor_max), float(factor_threshold), int(t),
-            int(freeze_step), _ptr(step), _lrp(lr_tensor), _stream(), _keyp(key_state),
-            key_seed & 0xFFFFFFFF, key_rank & 0xFFFFFFFF)
-    C.onebit_lamb(0, *args)
-    C.onebit_lamb(1, *args)
+    args = _args(
+        C.SignLambArgs, **src, tensors=_ptr(dp.tensors), num_tensors=dp.plan.num_tensors,
+        param=_ptr(param), exp_avg=_ptr(exp_avg), exp_avg_sq=_ptr(exp_avg_sq),
+        exp_avg_sq_fresh=_ptr(exp_avg_sq_fresh), shadow=_ptr(shadow), adapt=_ptr(lt.adapt),
+        partials=_ptr(lt.partials), r_frozen=_ptr(lt.r_frozen),
+        last_factor=_ptr(lt.last_factor), lf_stride=lt.last_factor.stride(0),
+        ratio=_ptr(lt.ratio), lr=float(lr), inv_n=float(inv_n), beta1=float(b1), beta2=float(b2),
+        eps=float(eps), weight_decay=float(weight_decay),
+        bc1=float(1.0 - b1 ** t if bc1 is None else bc1), bc2w=1.0 - b2 ** int(freeze_step),
+        factor_min=float(factor_min), factor_max=float(factor_max),
+        factor_threshold=float(factor_threshold), t=int(t), freeze_step=int(freeze_step),
+        step=_ptr(step), lr_ptr=_lrp(lr_tensor), stream=_stream(), key_state=_keyp(key_state),
+        key_seed=key_seed & 0xFFFFFFFF, key_rank=key_rank & 0xFFFFFFFF)
+    C.sign_decode_lamb_stage(args)
+    C.lamb_onebit_apply(args)
 
 
 class LowRankTables:
@@ -802,8 +856,9 @@ def _psgd_buf(t, n, name):
         raise ValueError(f"{name} has {t.numel()} floats, the plan needs {n}")
 
 
-def _psgd(op, lt, items, num_items, grad=None, resid=None, p=None, q=None, inv_n=1.0, q_out=None,
-          step=None):
+def _psgd(launch, lt, items, num_items, grad=None, resid=None, p=None, q=None, inv_n=1.0,
+          q_out=None, step=None):
+    """Launch ``psgd_<launch>`` of the extension."""
     C = require()
     lrp = lt.lrp
     _psgd_buf(p, lrp.p_floats, "p")
@@ -813,11 +868,14 @@ def _psgd(op, lt, items, num_items, grad=None, resid=None, p=None, q=None, inv_n
     for t, nm in ((q, "q"), (q_out, "q_out")):
         if t is not None:
             _psgd_buf(t, lrp.q_floats, nm)
-    C.psgd(op, lrp.rank, _ptr(lt.mats), len(lrp.mats), _ptr(lt.dense), len(lrp.dense),
-           _ptr(items), num_items, lrp.plan.length, lrp.p_floats, lrp.q_floats, _ptr(grad),
-           _ptr(resid), _ptr(p), _ptr(q), _ptr(lt.slabs), lrp.slab_floats, _ptr(lt.tickets),
-           lrp.num_tickets, float(inv_n), _ptr(q_out), C.StepArgs() if step is None else step,
-           _stream())
+    getattr(C, "psgd_" + launch)(_args(
+        C.PsgdArgs, rank=lrp.rank, mats=_ptr(lt.mats), num_mats=len(lrp.mats),
+        dense=_ptr(lt.dense), num_dense=len(lrp.dense), items=_ptr(items), num_items=num_items,
+        bucket_len=lrp.plan.length, p_floats=lrp.p_floats, q_floats=lrp.q_floats,
+        grad=_ptr(grad), resid=_ptr(resid), p=_ptr(p), q=_ptr(q), slabs=_ptr(lt.slabs),
+        slab_floats=lrp.slab_floats, tickets=_ptr(lt.tickets), num_tickets=lrp.num_tickets,
+        inv_n=float(inv_n), q_out=_ptr(q_out), step=C.StepArgs() if step is None else step,
+        stream=_stream()))
 
 
 def psgd_project(lt: LowRankTables, grad, resid, q, p):
@@ -826,19 +884,19 @@ def psgd_project(lt: LowRankTables, grad, resid, q, p):
     ``resid`` are the bucket's flat views."""
     if grad is None or resid is None or q is None:
         raise ValueError("the project launch needs grad, resid and q")
-    _psgd(0, lt, lt.rows, len(lt.lrp.row_items), grad=grad, resid=resid, p=p, q=q)
+    _psgd("project", lt, lt.rows, len(lt.lrp.row_items), grad=grad, resid=resid, p=p, q=q)
 
 
 def psgd_orth(lt: LowRankTables, p, inv_n: float):
     """PowerSGD launch 2: every P block times ``inv_n``, then modified Gram-Schmidt."""
-    _psgd(1, lt, None, 0, p=p, inv_n=inv_n)
+    _psgd("orth", lt, None, 0, p=p, inv_n=inv_n)
 
 
 def psgd_backproject(lt: LowRankTables, resid, p, q):
     """PowerSGD launch 3: ``q`` = the ``M^T P`` factors (``resid`` holds M)."""
     if resid is None or q is None:
         raise ValueError("the back-project launch needs resid and q")
-    _psgd(2, lt, lt.tiles, lt.lrp.num_mat_tiles, resid=resid, p=p, q=q)
+    _psgd("backproject", lt, lt.tiles, lt.lrp.num_mat_tiles, resid=resid, p=p, q=q)
 
 
 def psgd_decode_apply(lt: LowRankTables, resid, p, q, q_out, inv_n, param=None, mom=None,
@@ -854,8 +912,8 @@ def psgd_decode_apply(lt: LowRankTables, resid, p, q, q_out, inv_n, param=None, 
         raise ValueError("q_out must not be q: other blocks still read q")
     step = _step(lt, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay, 1.0,
                  nesterov, first, None, 0, 0, lr_tensor)
-    _psgd(3, lt, lt.tiles, len(lt.lrp.tile_items), resid=resid, p=p, q=q, inv_n=inv_n,
-          q_out=q_out, step=step)
+    _psgd("decode_apply", lt, lt.tiles, len(lt.lrp.tile_items), resid=resid, p=p, q=q,
+          inv_n=inv_n, q_out=q_out, step=step)
 
 
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -876,9 +934,17 @@ def sgd_flat(param, mom, grad, lr, momentum=0.0, dampening=0.0, weight_decay=0.0
         _check(shadow, torch.bfloat16, "shadow", align=8)
         if shadow.numel() != n:
             raise ValueError("shadow must match param")
-    C.sgd_flat(_ptr(param), _ptr(mom), _ptr(grad), _ptr(shadow), n, _GDT[grad.dtype], lr,
-               momentum, dampening, weight_decay, grad_scale, int(nesterov), int(first),
-               _stream(), _lrp(lr_tensor))
+    C.sgd_flat(_args(
+        C.SgdFlatArgs, param=_ptr(param), mom=_ptr(mom), grad=_ptr(grad), shadow=_ptr(shadow),
+        n=n, grad_dtype=_GDT[grad.dtype], lr=lr, momentum=momentum, dampening=dampening,
+        weight_decay=weight_decay, grad_scale=grad_scale, nesterov=int(nesterov),
+        first=int(first), stream=_stream(), lr_ptr=_lrp(lr_tensor)))
+
+
+def _adam_args(C, **fields):
+    """``AdamFlatArgs`` of :func:`adam_flat`: ``lr_step`` carries both bias corrections, so
+    ``bc2_sqrt`` is always 1."""
+    return _args(C.AdamFlatArgs, bc2_sqrt=1.0, **fields)
 
 
 def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, beta2, eps,
@@ -908,9 +974,12 @@ def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, 
         _check(shadow, torch.bfloat16, "shadow", align=8)
         if shadow.numel() != n:
             raise ValueError("shadow must match param")
-    C.adam_flat(_ptr(param), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(max_exp_avg_sq), _ptr(grad),
-                _ptr(shadow), n, _GDT[grad.dtype], lr_step, beta1, beta2, eps, weight_decay,
-                grad_scale, int(amsgrad), _stream(), _ptr(step), float(lr), _lrp(lr_tensor))
+    C.adam_flat(_adam_args(
+        C, param=_ptr(param), exp_avg=_ptr(exp_avg), exp_avg_sq=_ptr(exp_avg_sq),
+        max_exp_avg_sq=_ptr(max_exp_avg_sq), grad=_ptr(grad), shadow=_ptr(shadow), n=n,
+        grad_dtype=_GDT[grad.dtype], lr_step=lr_step, beta1=beta1, beta2=beta2, eps=eps,
+        weight_decay=weight_decay, grad_scale=grad_scale, amsgrad=int(amsgrad),
+        stream=_stream(), step=_ptr(step), lr=float(lr), lr_ptr=_lrp(lr_tensor)))
 
 
 def lion_flat(param, exp_avg, grad, lr, beta1, beta2, weight_decay=0.0, grad_scale=1.0,
@@ -930,9 +999,11 @@ def lion_flat(param, exp_avg, grad, lr, beta1, beta2, weight_decay=0.0, grad_sca
         _check(shadow, torch.bfloat16, "shadow", align=8)
         if shadow.numel() != n:
             raise ValueError("shadow must match param")
-    C.lion_flat(_ptr(param), _ptr(exp_avg), _ptr(grad), _ptr(shadow), n, _GDT[grad.dtype],
-                float(lr), float(beta1), float(beta2), float(weight_decay), float(grad_scale),
-                _stream(), _lrp(lr_tensor))
+    C.lion_flat(_args(
+        C.LionFlatArgs, param=_ptr(param), exp_avg=_ptr(exp_avg), grad=_ptr(grad),
+        shadow=_ptr(shadow), n=n, grad_dtype=_GDT[grad.dtype], lr=float(lr), beta1=float(beta1),
+        beta2=float(beta2), weight_decay=float(weight_decay), grad_scale=float(grad_scale),
+        stream=_stream(), lr_ptr=_lrp(lr_tensor)))
 
 
 OUTER_ROW = 8192  # elements per block of k_outer_apply, and per row of its outer_stats
@@ -975,8 +1046,10 @@ def outer_apply(anchor, data, momentum, delta, lr, mu, nesterov, shadow=None, st
         raise ValueError("outer lr must be finite and > 0")
     if not 0.0 <= mu < 1.0:
         raise ValueError("outer momentum must be in [0, 1)")
-    C.outer_apply(_ptr(anchor), _ptr(data), _ptr(momentum), _ptr(delta), _ptr(shadow),
-                  _ptr(stats), n, rows, lr, mu, int(bool(nesterov)), _stream())
+    C.outer_apply(_args(
+        C.OuterArgs, anchor=_ptr(anchor), data=_ptr(data), momentum=_ptr(momentum),
+        delta=_ptr(delta), shadow=_ptr(shadow), stats=_ptr(stats), n=n, stats_rows=rows, lr=lr,
+        mu=mu, nesterov=int(bool(nesterov)), stream=_stream()))
 
 
 def _check_vote_layout(dp, layout):
@@ -1014,9 +1087,12 @@ def lion_encode(dp, grad, payload, layout, exp_avg, beta1, beta2, step, rank, st
     _check_bucket(dp, exp_avg, "exp_avg")
     if step_tensor is not None:
         _check(step_tensor, torch.int32, "step", align=4)
-    C.lion_encode(ptrs, mask, _ptr(exp_avg), _ptr(dp.chunks), _ptr(payload), nbytes,
-                  dp.plan.num_tensors, dp.plan.num_chunks, codes, float(beta1),
-                  float(beta2), int(step), _ptr(step_tensor), int(rank), _stream(), sp, end)
+    C.lion_encode(_args(
+        C.LionEncodeArgs, exp_avg=_ptr(exp_avg), chunks=_ptr(dp.chunks), payload=_ptr(payload),
+        payload_bytes=nbytes, num_tensors=dp.plan.num_tensors, num_chunks=dp.plan.num_chunks,
+        bits_off=codes, beta1=float(beta1), beta2=float(beta2), step=int(step),
+        step_ptr=_ptr(step_tensor), rank=int(rank), stream=_stream(), slots=sp, slot_end=end),
+        ptrs, mask)
 
 
 def vote_reduce(dp, recv, layout, owner_row, out):
@@ -1038,8 +1114,10 @@ def vote_reduce(dp, recv, layout, owner_row, out):
     _check(out, torch.uint8, "out")
     if out.numel() < layout.nbytes:
         raise ValueError("out too small")
-    C.vote_reduce(_ptr(recv), recv.shape[0], recv.shape[1], int(owner_row), dp.plan.num_chunks,
-                  layout.codes, _ptr(out), out.numel(), _stream())
+    C.vote_reduce(_args(
+        C.VoteReduceArgs, **_rows(recv, recv.shape[0], recv.shape[1]), owner=int(owner_row),
+        num_chunks=dp.plan.num_chunks, bits_off=layout.codes, out=_ptr(out),
+        out_bytes=out.numel(), stream=_stream()))
 
 
 def lion_vote_apply(dp, recv, layout, param, lr, weight_decay=0.0, aggregate="majority",
@@ -1067,11 +1145,13 @@ def lion_vote_apply(dp, recv, layout, param, lr, weight_decay=0.0, aggregate="ma
         n, stride, codes, sp, end = recv.shape[0], layout.nbytes, layout.codes, 0, 0
     _check_bucket(dp, param, "param")
     _check_shadow(dp, shadow)
-    C.lion_vote_apply(_ptr(recv), n, stride, _ptr(dp.chunks), dp.plan.num_chunks,
-                      codes, _ptr(param), _ptr(shadow), float(lr), float(weight_decay),
-                      float(1.0 / n if inv_n is None else inv_n), int(aggregate == "average"),
-                      _lrp(lr_tensor), _stream(), _keyp(key_state), key_seed & 0xFFFFFFFF,
-                      key_rank & 0xFFFFFFFF, sp, end)
+    C.lion_vote_apply(_args(
+        C.LionVoteArgs, **_rows(recv, n, stride), chunks=_ptr(dp.chunks),
+        num_chunks=dp.plan.num_chunks, bits_off=codes, param=_ptr(param), shadow=_ptr(shadow),
+        lr=float(lr), weight_decay=float(weight_decay),
+        inv_n=float(1.0 / n if inv_n is None else inv_n), average=int(aggregate == "average"),
+        lr_ptr=_lrp(lr_tensor), stream=_stream(), key_state=_keyp(key_state),
+        key_seed=key_seed & 0xFFFFFFFF, key_rank=key_rank & 0xFFFFFFFF, slots=sp, slot_end=end))
 
 
 # Longest chain of fp32 additions behind one chunk's sum of squares in k_lw_stage
@@ -1106,6 +1186,15 @@ class LayerwisePlan:
         self.chunks = plan.chunk_table(adapt.device)
 
 
+def _layerwise_args(C, betas, t, **fields):
+    """``LayerwiseArgs`` with the betas of step ``t`` (1-based): in double (``beta1d`` /
+    ``beta2d``), rounded to fp32 as C's ``(float)`` does (``beta1`` / ``beta2``: the float field
+    takes the same double), and LAMB's bias corrections ``bc1`` / ``bc2``."""
+    b1, b2 = betas
+    return _args(C.LayerwiseArgs, beta1=float(b1), beta2=float(b2), beta1d=float(b1),
+                 beta2d=float(b2), bc1=1.0 - b1 ** t, bc2=1.0 - b2 ** t, **fields)
+
+
 def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=None, *, lr,
                    weight_decay=0.0, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, eta=0.001,
                    momentum=0.0, dampening=0.0, nesterov=False, first=False, t=1, step=None,
@@ -1135,16 +1224,18 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
     _check_shadow(lw, shadow)
     if step is not None:
         _check(step, torch.int32, "step", align=4)
-    b1, b2 = betas
-    args = (LAYERWISE_KINDS[kind], _ptr(param), _ptr(grad), _GDT[grad.dtype], _ptr(state1),
-            _ptr(state2) if kind == "lamb" else 0, _ptr(shadow), _ptr(lw.chunks),
-            lw.plan.num_chunks, _ptr(lw.tensors), _ptr(lw.adapt), _ptr(lw.partials),
-            _ptr(lw.ratio), float(lr), float(b1), float(b2), float(eps), float(weight_decay),
-            float(grad_scale), float(eta), float(momentum), float(dampening),
-            int(bool(nesterov)), int(bool(first)), 1.0 - b1 ** t, 1.0 - b2 ** t, _ptr(step),
-            _lrp(lr_tensor), _stream())
-    C.layerwise(0, *args)
-    C.layerwise(1, *args)
+    args = _layerwise_args(
+        C, betas, t, kind=LAYERWISE_KINDS[kind], param=_ptr(param), grad=_ptr(grad),
+        grad_dtype=_GDT[grad.dtype], state1=_ptr(state1),
+        state2=_ptr(state2) if kind == "lamb" else 0, shadow=_ptr(shadow),
+        chunks=_ptr(lw.chunks), num_chunks=lw.plan.num_chunks, tensors=_ptr(lw.tensors),
+        adapt=_ptr(lw.adapt), partials=_ptr(lw.partials), ratio=_ptr(lw.ratio), lr=float(lr),
+        eps=float(eps), weight_decay=float(weight_decay), grad_scale=float(grad_scale),
+        eta=float(eta), momentum=float(momentum), dampening=float(dampening),
+        nesterov=int(bool(nesterov)), first=int(bool(first)), step=_ptr(step),
+        lr_ptr=_lrp(lr_tensor), stream=_stream())
+    C.layerwise_stage(args)
+    C.layerwise_apply(args)
 
 
 # Longest chain of fp32 additions behind one chunk's sum of squares in k_clip_norm
@@ -1203,8 +1294,11 @@ def _clip_args(cp, bi, grads, max_norm):
     for t in ([grads] if torch.is_tensor(grads) else grads):
         if t.device != dev:
             raise ValueError("gradients and clip plan live on different devices")
-    return (ptrs, mask, b.plan.num_tensors, _ptr(b.chunks), b.plan.num_chunks, _ptr(cp.partials),
-            b.chunk0, cp.total_chunks, _ptr(cp.state), float(max_norm), _stream())
+    return _args(
+        require().ClipArgs, num_tensors=b.plan.num_tensors, chunks=_ptr(b.chunks),
+        num_chunks=b.plan.num_chunks, partials=_ptr(cp.partials), chunk0=b.chunk0,
+        total_chunks=cp.total_chunks, state=_ptr(cp.state), max_norm=float(max_norm),
+        stream=_stream()), ptrs, mask
 
 
 def clip_norm(cp: ClipPlan, bi: int, grads):
@@ -1212,7 +1306,7 @@ def clip_norm(cp: ClipPlan, bi: int, grads):
     (``grads`` as for :func:`pack_grads`: the bucket's flat fp32 view, or one fp32 / bf16 tensor per
     plan tensor) into ``cp.partials``.  Every bucket's norm launch precedes any
     :func:`clip_scale`."""
-    require().clip(0, *_clip_args(cp, bi, grads, 1.0))
+    require().clip_norm(*_clip_args(cp, bi, grads, 1.0))
 
 
 def clip_scale(cp: ClipPlan, bi: int, grads, max_norm: float):
@@ -1222,7 +1316,7 @@ def clip_scale(cp: ClipPlan, bi: int, grads, max_norm: float):
     max_norm = float(max_norm)
     if not max_norm > 0.0 or max_norm != max_norm:
         raise ValueError("max_norm must be > 0")
-    require().clip(1, *_clip_args(cp, bi, grads, max_norm))
+    require().clip_scale(*_clip_args(cp, bi, grads, max_norm))
 
 
 _DDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -1252,9 +1346,11 @@ def sgd_ptrs(dp, grads, param, mom, lr, momentum=0.0, dampening=0.0, weight_deca
         if t.numel() < dp.plan.length:
             raise ValueError(f"{nm} too small for the bucket")
     _check_shadow(dp, shadow)
-    C.sgd_ptrs(ptrs, mask, dp.plan.num_tensors, _ptr(dp.chunks), dp.plan.num_chunks, _ptr(param),
-               _ptr(mom), _ptr(shadow), lr, momentum, dampening, weight_decay, grad_scale,
-               int(nesterov), int(first), _stream(), _lrp(lr_tensor))
+    C.sgd_ptrs(ptrs, mask, dp.plan.num_tensors, _ptr(dp.chunks), dp.plan.num_chunks, _args(
+        C.SgdFlatArgs, param=_ptr(param), mom=_ptr(mom), shadow=_ptr(shadow), lr=lr,
+        momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+        grad_scale=grad_scale, nesterov=int(nesterov), first=int(first), stream=_stream(),
+        lr_ptr=_lrp(lr_tensor)))
 
 
 def cast_scale(src, dst, scale=1.0):

@@ -3,6 +3,9 @@
 // The Python wrappers in ops/__init__.py validate tensors and pass raw device pointers and the
 // current hipStream_t of torch (so every launch is ordered on, and graph-capturable from, the
 // caller's stream).
+//
+// The codec and optimizer launchers take the argument structs of ewdml_ops.h, bound here as
+// classes: Python fills them by field name (ops._args) and each field is named once, below.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -19,26 +22,161 @@ static GradSrc grad_src(const Ptrs& grads, const Mask& mask) {
   return GradSrc{grads.data(), (int)grads.size(), mask.data(), (int)mask.size()};
 }
 
+// f(args, grads, mask) of the entry points that read gradients through the pointer table: `src`
+// points into host arrays that must outlive the call, so it is set here and never bound
+template <class A, void (*fn)(const A&)>
+static void with_grads(A a, const Ptrs& grads, const Mask& mask) {
+  a.src = grad_src(grads, mask);
+  fn(a);
+}
+
+// StepArgs() of Python, and the `step` member of a new decode's arguments: a gradient scale of 1
+static StepArgs default_step() {
+  StepArgs s{};
+  s.grad_scale = 1.0f;
+  return s;
+}
+template <class A>
+static A zero_with_step() {
+  A a{};
+  a.step = default_step();
+  return a;
+}
+
+// EW_ARGS(T, F(field) ...): class T with T() = T{} (every field zero) and its read/write fields;
+// EW_ARGS_STEP: the same for a struct that embeds the receive-side step as `step`
+#define F(f) .def_readwrite(#f, &A::f)
+#define EW_ARGS(T, ...)                                                 \
+  {                                                                     \
+    using A = T;                                                        \
+    py::class_<A>(m, #T).def(py::init([] { return A{}; })) __VA_ARGS__; \
+  }
+#define EW_ARGS_STEP(T, ...)                                                   \
+  {                                                                            \
+    using A = T;                                                               \
+    py::class_<A>(m, #T).def(py::init(&zero_with_step<A>)) F(step) __VA_ARGS__; \
+  }
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "ewdml CDNA4 (gfx950) kernels";
   m.attr("arch") = "gfx950";
 
-  // the receive-side step of every *_decode_apply and of psgd (ops._step builds it)
-  py::class_<StepArgs>(m, "StepArgs")
-      .def(py::init([](uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
-                       float lr, float momentum, float dampening, float weight_decay,
-                       float grad_scale, int nesterov, int first, int apply, uintptr_t key_state,
-                       uint32_t key_seed, uint32_t key_rank, uintptr_t lr_ptr) {
-             return StepArgs{param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
-                             grad_scale, nesterov, first, apply, key_state, key_seed, key_rank,
-                             lr_ptr};
-           }),
-           py::arg("param") = 0, py::arg("mom") = 0, py::arg("grad_out") = 0,
-           py::arg("shadow") = 0, py::arg("lr") = 0.0f, py::arg("momentum") = 0.0f,
-           py::arg("dampening") = 0.0f, py::arg("weight_decay") = 0.0f,
-           py::arg("grad_scale") = 1.0f, py::arg("nesterov") = 0, py::arg("first") = 0,
-           py::arg("apply") = 0, py::arg("key_state") = 0, py::arg("key_seed") = 0,
-           py::arg("key_rank") = 0, py::arg("lr_ptr") = 0);
+  {  // the receive-side step of every *_decode_apply and of psgd (ops._step builds it)
+    using A = StepArgs;
+    const StepArgs d = default_step();
+    py::class_<A>(m, "StepArgs")
+        .def(py::init([](uintptr_t param, uintptr_t mom, uintptr_t grad_out, uintptr_t shadow,
+                         float lr, float momentum, float dampening, float weight_decay,
+                         float grad_scale, int nesterov, int first, int apply,
+                         uintptr_t key_state, uint32_t key_seed, uint32_t key_rank,
+                         uintptr_t lr_ptr) {
+               return StepArgs{param, mom, grad_out, shadow, lr, momentum, dampening,
+                               weight_decay, grad_scale, nesterov, first, apply, key_state,
+                               key_seed, key_rank, lr_ptr};
+             }),
+             py::arg("param") = 0, py::arg("mom") = 0, py::arg("grad_out") = 0,
+             py::arg("shadow") = 0, py::arg("lr") = 0.0f, py::arg("momentum") = 0.0f,
+             py::arg("dampening") = 0.0f, py::arg("weight_decay") = 0.0f,
+             py::arg("grad_scale") = d.grad_scale, py::arg("nesterov") = 0, py::arg("first") = 0,
+             py::arg("apply") = 0, py::arg("key_state") = 0, py::arg("key_seed") = 0,
+             py::arg("key_rank") = 0, py::arg("lr_ptr") = 0)
+        F(param) F(mom) F(grad_out) F(shadow) F(lr) F(momentum) F(dampening) F(weight_decay)
+        F(grad_scale) F(nesterov) F(first) F(apply) F(key_state) F(key_seed) F(key_rank)
+        F(lr_ptr);
+  }
+
+  EW_ARGS(TopkEncodeArgs,
+          F(resid) F(chunks) F(tensors) F(scratch) F(payload) F(stream) F(payload_bytes)
+          F(num_tensors) F(num_chunks) F(scales_off) F(counts_off) F(idx_off) F(codes_off)
+          F(bitmap_off) F(value_kind) F(norm_l2) F(levels) F(inv_levels) F(key) F(bucket_offset)
+          F(key_ptr) F(vel) F(param) F(dgc_momentum) F(dgc_damp1) F(dgc_wd) F(dgc_nesterov)
+          F(dgc_mask) F(dgc_lr_ptr) F(bucket_len) F(cblocks) F(num_cblocks) F(predict)
+          F(lb_fault) F(max_k) F(apply_param) F(apply_shadow) F(apply_lr_ptr)
+          F(apply_key_state) F(apply_lr) F(apply_scale) F(apply_key_seed) F(apply_key_rank)
+          F(dgc_stamps) F(apply_mom_set) F(apply_mom) F(apply_momentum) F(apply_dampening)
+          F(apply_wd) F(apply_nesterov) F(apply_first))
+  EW_ARGS_STEP(TopkDecodeArgs,
+               F(recv) F(chunks) F(tensors) F(stream) F(stride) F(nranks) F(num_chunks)
+               F(scales_off) F(counts_off) F(idx_off) F(codes_off) F(bitmap_off) F(value_kind)
+               F(inv_levels))
+  EW_ARGS(QsgdEncodeArgs,
+          F(resid) F(chunks) F(tensors) F(scratch) F(payload) F(stream) F(payload_bytes)
+          F(num_tensors) F(num_chunks) F(scales_off) F(codes_off) F(bits) F(norm_l2) F(levels)
+          F(inv_levels) F(key) F(bucket_offset) F(key_ptr))
+  EW_ARGS_STEP(QsgdDecodeArgs,
+               F(recv) F(chunks) F(tensors) F(stream) F(stride) F(nranks) F(num_chunks)
+               F(scales_off) F(codes_off) F(bits) F(inv_levels))
+  EW_ARGS(SignEncodeArgs,
+          F(resid) F(chunks) F(payload) F(stream) F(payload_bytes) F(num_tensors) F(num_chunks)
+          F(scales_off) F(bits_off) F(mom_exp_avg) F(mom_param) F(mom_beta1) F(mom_wd) F(slots)
+          F(slot_end) F(rotate) F(rot_key))
+  EW_ARGS(SignReduceArgs,
+          F(recv) F(chunks) F(sresid) F(out) F(stream) F(stride) F(out_bytes) F(nranks)
+          F(num_chunks) F(scales_off) F(bits_off) F(inv_n))
+  EW_ARGS(SignOnebitArgs,
+          F(recv) F(chunks) F(param) F(exp_avg) F(exp_avg_sq) F(shadow) F(stream) F(stride)
+          F(nranks) F(num_chunks) F(scales_off) F(bits_off) F(lr_step) F(inv_n) F(eps) F(beta1)
+          F(beta2) F(freeze_step) F(step) F(lr) F(lr_ptr) F(key_state) F(key_seed) F(key_rank)
+          F(slots) F(slot_end))
+  EW_ARGS(SignLambArgs,
+          F(recv) F(chunks) F(tensors) F(stream) F(param) F(exp_avg) F(exp_avg_sq)
+          F(exp_avg_sq_fresh) F(shadow) F(adapt) F(partials) F(r_frozen) F(last_factor) F(ratio)
+          F(stride) F(nranks) F(num_chunks) F(num_tensors) F(lf_stride) F(scales_off)
+          F(bits_off) F(beta1) F(beta2) F(lr) F(inv_n) F(eps) F(weight_decay) F(bc1) F(bc2w)
+          F(factor_min) F(factor_max) F(factor_threshold) F(t) F(freeze_step) F(step) F(lr_ptr)
+          F(key_state) F(key_seed) F(key_rank))
+  EW_ARGS_STEP(SignDecodeArgs,
+               F(recv) F(chunks) F(stream) F(stride) F(nranks) F(num_chunks) F(scales_off)
+               F(bits_off) F(slots) F(slot_end) F(rotate) F(rot_key))
+  EW_ARGS(MxEncodeArgs,
+          F(resid) F(chunks) F(payload) F(stream) F(payload_bytes) F(length) F(num_tensors)
+          F(num_chunks) F(scales_off) F(codes_off) F(bits) F(soft))
+  EW_ARGS_STEP(MxDecodeArgs,
+               F(recv) F(chunks) F(stream) F(stride) F(length) F(nranks) F(num_chunks)
+               F(scales_off) F(codes_off) F(bits) F(soft))
+  EW_ARGS(TernEncodeArgs,
+          F(resid) F(chunks) F(tensors) F(scratch) F(payload) F(stream) F(payload_bytes)
+          F(total_codes) F(num_tensors) F(num_chunks) F(scales_off) F(codes_off) F(clip) F(key)
+          F(bucket_offset) F(key_ptr))
+  EW_ARGS_STEP(TernDecodeArgs,
+               F(recv) F(chunks) F(tensors) F(stream) F(stride) F(total_codes) F(nranks)
+               F(num_tensors) F(num_chunks) F(scales_off) F(codes_off))
+  EW_ARGS_STEP(PsgdArgs,
+               F(mats) F(dense) F(items) F(stream) F(rank) F(num_mats) F(num_dense) F(num_items)
+               F(bucket_len) F(p_floats) F(q_floats) F(grad) F(resid) F(p) F(q) F(slabs)
+               F(tickets) F(slab_floats) F(num_tickets) F(inv_n) F(q_out))
+  EW_ARGS(SgdFlatArgs,
+          F(param) F(mom) F(grad) F(shadow) F(stream) F(n) F(grad_dtype) F(lr) F(momentum)
+          F(dampening) F(weight_decay) F(grad_scale) F(nesterov) F(first) F(lr_ptr))
+  EW_ARGS(AdamFlatArgs,
+          F(param) F(exp_avg) F(exp_avg_sq) F(max_exp_avg_sq) F(grad) F(shadow) F(stream) F(n)
+          F(grad_dtype) F(lr_step) F(beta1) F(beta2) F(eps) F(weight_decay) F(grad_scale)
+          F(bc2_sqrt) F(amsgrad) F(step) F(lr) F(lr_ptr))
+  EW_ARGS(LionFlatArgs,
+          F(param) F(exp_avg) F(grad) F(shadow) F(stream) F(n) F(grad_dtype) F(lr) F(beta1)
+          F(beta2) F(weight_decay) F(grad_scale) F(lr_ptr))
+  EW_ARGS(LionEncodeArgs,
+          F(exp_avg) F(chunks) F(payload) F(stream) F(payload_bytes) F(num_tensors)
+          F(num_chunks) F(bits_off) F(beta1) F(beta2) F(step) F(rank) F(step_ptr) F(slots)
+          F(slot_end))
+  EW_ARGS(LionVoteArgs,
+          F(recv) F(chunks) F(param) F(shadow) F(stream) F(stride) F(nranks) F(num_chunks)
+          F(bits_off) F(lr) F(weight_decay) F(inv_n) F(average) F(lr_ptr) F(key_state)
+          F(key_seed) F(key_rank) F(slots) F(slot_end))
+  EW_ARGS(VoteReduceArgs,
+          F(recv) F(out) F(stream) F(stride) F(out_bytes) F(nranks) F(owner) F(num_chunks)
+          F(bits_off))
+  EW_ARGS(LayerwiseArgs,
+          F(param) F(grad) F(state1) F(state2) F(shadow) F(chunks) F(tensors) F(adapt)
+          F(partials) F(ratio) F(stream) F(num_chunks) F(kind) F(grad_dtype) F(lr) F(beta1)
+          F(beta2) F(eps) F(weight_decay) F(grad_scale) F(eta) F(momentum) F(dampening) F(bc1)
+          F(bc2) F(beta1d) F(beta2d) F(nesterov) F(first) F(step) F(lr_ptr))
+  EW_ARGS(ClipArgs,
+          F(num_tensors) F(num_chunks) F(chunk0) F(total_chunks) F(chunks) F(partials) F(state)
+          F(stream) F(max_norm))
+  EW_ARGS(OuterArgs,
+          F(anchor) F(data) F(momentum) F(delta) F(shadow) F(stats) F(stream) F(n) F(stats_rows)
+          F(lr) F(mu) F(nesterov))
 
   m.def("topk_scratch_bytes", &ew_topk_scratch_bytes);
   m.def("topk_lookback_errors", &ew_topk_lookback_errors);
@@ -46,681 +184,40 @@ PYBIND11_MODULE(_C, m) {
   m.def("graph_info", &ew_graph_info);
   m.def("qsgd_scratch_bytes", &ew_qsgd_scratch_bytes);
 
-  m.def("topk_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t tensors, uintptr_t scratch, uintptr_t payload, long long payload_bytes,
-           int T, int C, int scales_off, int counts_off, int idx_off, int codes_off,
-           int value_kind, int norm_l2, float levels, float inv_levels, uint32_t key,
-           uint32_t bucket_offset, uintptr_t key_ptr, uintptr_t stream, uintptr_t vel,
-           uintptr_t param, float dgc_momentum, float dgc_damp1, float dgc_wd,
-           int dgc_nesterov, int bitmap_off, int dgc_mask, uintptr_t dgc_lr_ptr,
-           long long bucket_len, uintptr_t cblocks, int num_cblocks, int predict,
-           int lb_fault, int max_k, uintptr_t apply_param, uintptr_t apply_shadow,
-           float apply_lr, uintptr_t apply_lr_ptr, float apply_scale,
-           uintptr_t apply_key_state, uint32_t apply_key_seed, uint32_t apply_key_rank,
-           int apply_mom_set, uintptr_t apply_mom, float apply_momentum, float apply_dampening,
-           float apply_wd, int apply_nesterov, int apply_first, uintptr_t dgc_stamps) {
-          TopkEncodeArgs a{};
-          a.dgc_stamps = dgc_stamps;
-          a.apply_mom_set = apply_mom_set;
-          a.apply_mom = apply_mom;
-          a.apply_momentum = apply_momentum;
-          a.apply_dampening = apply_dampening;
-          a.apply_wd = apply_wd;
-          a.apply_nesterov = apply_nesterov;
-          a.apply_first = apply_first;
-          a.apply_param = apply_param;
-          a.apply_shadow = apply_shadow;
-          a.apply_lr = apply_lr;
-          a.apply_lr_ptr = apply_lr_ptr;
-          a.apply_scale = apply_scale;
-          a.apply_key_state = apply_key_state;
-          a.apply_key_seed = apply_key_seed;
-          a.apply_key_rank = apply_key_rank;
-          a.lb_fault = lb_fault;
-          a.max_k = max_k;
-          a.bucket_len = bucket_len;
-          a.cblocks = cblocks;
-          a.num_cblocks = num_cblocks;
-          a.predict = predict;
-          a.dgc_mask = dgc_mask;
-          a.dgc_lr_ptr = dgc_lr_ptr;
-          a.bitmap_off = bitmap_off;
-          a.vel = vel;
-          a.param = param;
-          a.dgc_momentum = dgc_momentum;
-          a.dgc_damp1 = dgc_damp1;
-          a.dgc_wd = dgc_wd;
-          a.dgc_nesterov = dgc_nesterov;
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.scratch = scratch;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.counts_off = counts_off;
-          a.idx_off = idx_off;
-          a.codes_off = codes_off;
-          a.value_kind = value_kind;
-          a.norm_l2 = norm_l2;
-          a.levels = levels;
-          a.inv_levels = inv_levels;
-          a.key = key;
-          a.bucket_offset = bucket_offset;
-          a.key_ptr = key_ptr;
-          ew_topk_encode(a);
-        });
+  m.def("topk_encode", &with_grads<TopkEncodeArgs, ew_topk_encode>);
+  m.def("qsgd_encode", &with_grads<QsgdEncodeArgs, ew_qsgd_encode>);
+  m.def("sign_encode", &with_grads<SignEncodeArgs, ew_sign_encode>);
+  m.def("mx_encode", &with_grads<MxEncodeArgs, ew_mx_encode>);
+  m.def("tern_encode", &with_grads<TernEncodeArgs, ew_tern_encode>);
+  m.def("lion_encode", &with_grads<LionEncodeArgs, ew_lion_encode>);
+  m.def("clip_norm", &with_grads<ClipArgs, ew_clip_norm>);
+  m.def("clip_scale", &with_grads<ClipArgs, ew_clip_scale>);
 
-  m.def("topk_decode_apply",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, uintptr_t tensors,
-           int C, int scales_off, int counts_off, int idx_off, int codes_off, int value_kind,
-           float inv_levels, const StepArgs& step, uintptr_t stream, int bitmap_off) {
-          TopkDecodeArgs a{};
-          a.step = step;
-          a.bitmap_off = bitmap_off;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.stream = stream;
-          a.stride = stride;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.counts_off = counts_off;
-          a.idx_off = idx_off;
-          a.codes_off = codes_off;
-          a.value_kind = value_kind;
-          a.inv_levels = inv_levels;
-          ew_topk_decode_apply(a);
-        });
-
-  m.def("qsgd_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t tensors, uintptr_t scratch, uintptr_t payload, long long payload_bytes,
-           int T, int C, int scales_off, int codes_off, int bits, int norm_l2, float levels,
-           float inv_levels, uint32_t key, uint32_t bucket_offset, uintptr_t key_ptr,
-           uintptr_t stream) {
-          QsgdEncodeArgs a{};
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.scratch = scratch;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          a.bits = bits;
-          a.norm_l2 = norm_l2;
-          a.levels = levels;
-          a.inv_levels = inv_levels;
-          a.key = key;
-          a.bucket_offset = bucket_offset;
-          a.key_ptr = key_ptr;
-          ew_qsgd_encode(a);
-        });
-
-  m.def("qsgd_decode_apply",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, uintptr_t tensors,
-           int C, int scales_off, int codes_off, int bits, float inv_levels,
-           const StepArgs& step, uintptr_t stream) {
-          QsgdDecodeArgs a{};
-          a.step = step;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.stream = stream;
-          a.stride = stride;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          a.bits = bits;
-          a.inv_levels = inv_levels;
-          ew_qsgd_decode_apply(a);
-        });
-
-  m.def("sign_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
-           int bits_off, uintptr_t stream, uintptr_t slots, long long slot_end, int rotate,
-           uint32_t rot_key) {
-          SignEncodeArgs a{};
-          a.rotate = rotate;
-          a.rot_key = rot_key;
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          ew_sign_encode(a);
-        });
-
-  m.def("sign_encode_momentum",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t payload, long long payload_bytes, int T, int C, int scales_off,
-           int bits_off, uintptr_t exp_avg, uintptr_t param, float beta1, float weight_decay,
-           uintptr_t stream, uintptr_t slots, long long slot_end) {
-          SignEncodeArgs a{};
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          if (!exp_avg) throw std::runtime_error("ewdml sign: the momentum encode needs exp_avg");
-          a.mom_exp_avg = exp_avg;
-          a.mom_param = param;
-          a.mom_beta1 = beta1;
-          a.mom_wd = weight_decay;
-          ew_sign_encode(a);
-        });
-
-  m.def("sign_reduce_encode",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
-           int bits_off, float inv_n, uintptr_t sresid, uintptr_t out, long long out_bytes,
-           uintptr_t stream) {
-          SignReduceArgs a{};
-          a.recv = recv;
-          a.chunks = chunks;
-          a.sresid = sresid;
-          a.out = out;
-          a.stream = stream;
-          a.stride = stride;
-          a.out_bytes = out_bytes;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          a.inv_n = inv_n;
-          ew_sign_reduce_encode(a);
-        });
-
-  m.def("sign_decode_onebit",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
-           int bits_off, uintptr_t param, uintptr_t exp_avg, uintptr_t exp_avg_sq,
-           uintptr_t shadow, float lr_step, float inv_n, float eps, float beta1, float beta2,
-           int freeze_step, uintptr_t step, double lr, uintptr_t lr_ptr, uintptr_t stream,
-           uintptr_t key_state, uint32_t key_seed, uint32_t key_rank, uintptr_t slots,
-           long long slot_end) {
-          SignOnebitArgs a{};
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.param = param;
-          a.exp_avg = exp_avg;
-          a.exp_avg_sq = exp_avg_sq;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.stride = stride;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          a.lr_step = lr_step;
-          a.inv_n = inv_n;
-          a.eps = eps;
-          a.beta1 = beta1;
-          a.beta2 = beta2;
-          a.freeze_step = freeze_step;
-          a.step = step;
-          a.lr = lr;
-          a.lr_ptr = lr_ptr;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
-          ew_sign_decode_onebit(a);
-        });
-
-  m.def("onebit_lamb",
-        [](int op, uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C,
-           uintptr_t tensors, int T, int scales_off, int bits_off, uintptr_t param,
-           uintptr_t exp_avg, uintptr_t exp_avg_sq, uintptr_t exp_avg_sq_fresh, uintptr_t shadow,
-           uintptr_t adapt, uintptr_t partials, uintptr_t r_frozen, uintptr_t last_factor,
-           int lf_stride, uintptr_t ratio, float lr, float inv_n, double beta1, double beta2, float eps,
-           float weight_decay, float bc1, float bc2w, float factor_min, float factor_max,
-           float factor_threshold, int t, int freeze_step, uintptr_t step, uintptr_t lr_ptr,
-           uintptr_t stream, uintptr_t key_state, uint32_t key_seed, uint32_t key_rank) {
-          SignLambArgs a{};
-          a.recv = recv;
-          a.nranks = nranks;
-          a.stride = stride;
-          a.chunks = chunks;
-          a.num_chunks = C;
-          a.tensors = tensors;
-          a.num_tensors = T;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          a.param = param;
-          a.exp_avg = exp_avg;
-          a.exp_avg_sq = exp_avg_sq;
-          a.exp_avg_sq_fresh = exp_avg_sq_fresh;
-          a.shadow = shadow;
-          a.adapt = adapt;
-          a.partials = partials;
-          a.r_frozen = r_frozen;
-          a.last_factor = last_factor;
-          a.lf_stride = lf_stride;
-          a.ratio = ratio;
-          a.lr = lr;
-          a.inv_n = inv_n;
-          a.beta1 = beta1;
-          a.beta2 = beta2;
-          a.eps = eps;
-          a.weight_decay = weight_decay;
-          a.bc1 = bc1;
-          a.bc2w = bc2w;
-          a.factor_min = factor_min;
-          a.factor_max = factor_max;
-          a.factor_threshold = factor_threshold;
-          a.t = t;
-          a.freeze_step = freeze_step;
-          a.step = step;
-          a.lr_ptr = lr_ptr;
-          a.stream = stream;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
-          if (op == 0) ew_sign_decode_lamb_stage(a);
-          else if (op == 1) ew_lamb_onebit_apply(a);
-          else throw std::runtime_error("ewdml 1-bit LAMB: unknown op");
-        });
-
-  m.def("sign_decode_apply",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int scales_off,
-           int bits_off, const StepArgs& step, uintptr_t stream, uintptr_t slots,
-           long long slot_end, int rotate, uint32_t rot_key) {
-          SignDecodeArgs a{};
-          a.step = step;
-          a.rotate = rotate;
-          a.rot_key = rot_key;
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.stream = stream;
-          a.stride = stride;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.bits_off = bits_off;
-          ew_sign_decode_apply(a);
-        });
-
-  m.def("mx_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t payload, long long payload_bytes, long long length, int T, int C,
-           int scales_off, int codes_off, int bits, int soft, uintptr_t stream) {
-          MxEncodeArgs a{};
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.length = length;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          a.bits = bits;
-          a.soft = soft;
-          ew_mx_encode(a);
-        });
-
-  m.def("mx_decode_apply",
-        [](uintptr_t recv, int nranks, long long stride, long long length, uintptr_t chunks, int C,
-           int scales_off, int codes_off, int bits, int soft, const StepArgs& step,
-           uintptr_t stream) {
-          MxDecodeArgs a{};
-          a.step = step;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.stream = stream;
-          a.stride = stride;
-          a.length = length;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          a.bits = bits;
-          a.soft = soft;
-          ew_mx_decode_apply(a);
-        });
-
-  m.def("tern_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t resid, uintptr_t chunks,
-           uintptr_t tensors, uintptr_t scratch, uintptr_t payload, long long payload_bytes,
-           long long total_codes, int T, int C, int scales_off, int codes_off, float clip,
-           uint32_t key, uint32_t bucket_offset, uintptr_t key_ptr, uintptr_t stream) {
-          TernEncodeArgs a{};
-          a.src = grad_src(grads, mask);
-          a.resid = resid;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.scratch = scratch;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.total_codes = total_codes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          a.clip = clip;
-          a.key = key;
-          a.bucket_offset = bucket_offset;
-          a.key_ptr = key_ptr;
-          ew_tern_encode(a);
-        });
-
-  m.def("tern_decode_apply",
-        [](uintptr_t recv, int nranks, long long stride, long long total_codes, uintptr_t chunks,
-           uintptr_t tensors, int T, int C, int scales_off, int codes_off, const StepArgs& step,
-           uintptr_t stream) {
-          TernDecodeArgs a{};
-          a.step = step;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.tensors = tensors;
-          a.stream = stream;
-          a.stride = stride;
-          a.total_codes = total_codes;
-          a.nranks = nranks;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.scales_off = scales_off;
-          a.codes_off = codes_off;
-          ew_tern_decode_apply(a);
-        });
-
-  // PowerSGD (powersgd.hip): op 0 = project, 1 = orth, 2 = backproject, 3 = decode_apply
-  m.def("psgd",
-        [](int op, int rank, uintptr_t mats, int num_mats, uintptr_t dense, int num_dense,
-           uintptr_t items, int num_items, long long bucket_len, long long p_floats,
-           long long q_floats, uintptr_t grad, uintptr_t resid, uintptr_t p, uintptr_t q,
-           uintptr_t slabs, long long slab_floats, uintptr_t tickets, int num_tickets,
-           float inv_n, uintptr_t q_out, const StepArgs& step, uintptr_t stream) {
-          PsgdArgs a{};
-          a.mats = mats;
-          a.dense = dense;
-          a.items = items;
-          a.stream = stream;
-          a.rank = rank;
-          a.num_mats = num_mats;
-          a.num_dense = num_dense;
-          a.num_items = num_items;
-          a.bucket_len = bucket_len;
-          a.p_floats = p_floats;
-          a.q_floats = q_floats;
-          a.grad = grad;
-          a.resid = resid;
-          a.p = p;
-          a.q = q;
-          a.slabs = slabs;
-          a.tickets = tickets;
-          a.slab_floats = slab_floats;
-          a.num_tickets = num_tickets;
-          a.inv_n = inv_n;
-          a.q_out = q_out;
-          a.step = step;
-          if (op == 0) ew_psgd_project(a);
-          else if (op == 1) ew_psgd_orth(a);
-          else if (op == 2) ew_psgd_backproject(a);
-          else if (op == 3) ew_psgd_decode_apply(a);
-          else throw std::runtime_error("ewdml powersgd: unknown op");
-        });
-
-  m.def("sgd_flat",
-        [](uintptr_t param, uintptr_t mom, uintptr_t grad, uintptr_t shadow, long long n,
-           int grad_dtype, float lr, float momentum, float dampening, float weight_decay,
-           float grad_scale, int nesterov, int first, uintptr_t stream, uintptr_t lr_ptr) {
-          SgdFlatArgs a{};
-          a.lr_ptr = lr_ptr;
-          a.param = param;
-          a.mom = mom;
-          a.grad = grad;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.n = n;
-          a.grad_dtype = grad_dtype;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          ew_sgd_flat(a);
-        });
-
-  m.def("adam_flat",
-        [](uintptr_t param, uintptr_t m1, uintptr_t m2, uintptr_t vmax, uintptr_t grad,
-           uintptr_t shadow, long long n, int grad_dtype, float lr_step, float beta1, float beta2,
-           float eps, float weight_decay, float grad_scale, int amsgrad, uintptr_t stream,
-           uintptr_t step, double lr, uintptr_t lr_ptr) {
-          AdamFlatArgs a{};
-          a.lr_ptr = lr_ptr;
-          a.step = step;
-          a.lr = lr;
-          a.param = param;
-          a.exp_avg = m1;
-          a.exp_avg_sq = m2;
-          a.max_exp_avg_sq = vmax;
-          a.grad = grad;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.n = n;
-          a.grad_dtype = grad_dtype;
-          a.lr_step = lr_step;
-          a.beta1 = beta1;
-          a.beta2 = beta2;
-          a.eps = eps;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.bc2_sqrt = 1.0f;
-          a.amsgrad = amsgrad;
-          ew_adam_flat(a);
-        });
-
-  m.def("lion_flat",
-        [](uintptr_t param, uintptr_t exp_avg, uintptr_t grad, uintptr_t shadow, long long n,
-           int grad_dtype, float lr, float beta1, float beta2, float weight_decay,
-           float grad_scale, uintptr_t stream, uintptr_t lr_ptr) {
-          LionFlatArgs a{};
-          a.param = param;
-          a.exp_avg = exp_avg;
-          a.grad = grad;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.n = n;
-          a.grad_dtype = grad_dtype;
-          a.lr = lr;
-          a.beta1 = beta1;
-          a.beta2 = beta2;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.lr_ptr = lr_ptr;
-          ew_lion_flat(a);
-        });
-
-  m.def("lion_encode",
-        [](const Ptrs& grads, const Mask& mask, uintptr_t exp_avg, uintptr_t chunks,
-           uintptr_t payload, long long payload_bytes, int T, int C, int bits_off, float beta1,
-           float beta2, int step, uintptr_t step_ptr, int rank, uintptr_t stream,
-           uintptr_t slots, long long slot_end) {
-          LionEncodeArgs a{};
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.src = grad_src(grads, mask);
-          a.exp_avg = exp_avg;
-          a.chunks = chunks;
-          a.payload = payload;
-          a.stream = stream;
-          a.payload_bytes = payload_bytes;
-          a.num_tensors = T;
-          a.num_chunks = C;
-          a.bits_off = bits_off;
-          a.beta1 = beta1;
-          a.beta2 = beta2;
-          a.step = step;
-          a.step_ptr = step_ptr;
-          a.rank = rank;
-          ew_lion_encode(a);
-        });
-
-  m.def("lion_vote_apply",
-        [](uintptr_t recv, int nranks, long long stride, uintptr_t chunks, int C, int bits_off,
-           uintptr_t param, uintptr_t shadow, float lr, float weight_decay, float inv_n,
-           int average, uintptr_t lr_ptr, uintptr_t stream, uintptr_t key_state,
-           uint32_t key_seed, uint32_t key_rank, uintptr_t slots, long long slot_end) {
-          LionVoteArgs a{};
-          a.slots = slots;
-          a.slot_end = slot_end;
-          a.recv = recv;
-          a.chunks = chunks;
-          a.param = param;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.stride = stride;
-          a.nranks = nranks;
-          a.num_chunks = C;
-          a.bits_off = bits_off;
-          a.lr = lr;
-          a.weight_decay = weight_decay;
-          a.inv_n = inv_n;
-          a.average = average;
-          a.lr_ptr = lr_ptr;
-          a.key_state = key_state;
-          a.key_seed = key_seed;
-          a.key_rank = key_rank;
-          ew_lion_vote_apply(a);
-        });
-
-  m.def("vote_reduce",
-        [](uintptr_t recv, int nranks, long long stride, int owner, int C, int bits_off,
-           uintptr_t out, long long out_bytes, uintptr_t stream) {
-          VoteReduceArgs a{};
-          a.recv = recv;
-          a.out = out;
-          a.stream = stream;
-          a.stride = stride;
-          a.out_bytes = out_bytes;
-          a.nranks = nranks;
-          a.owner = owner;
-          a.num_chunks = C;
-          a.bits_off = bits_off;
-          ew_vote_reduce(a);
-        });
-
-  m.def("layerwise",
-        [](int op, int kind, uintptr_t param, uintptr_t grad, int grad_dtype, uintptr_t state1,
-           uintptr_t state2, uintptr_t shadow, uintptr_t chunks, int num_chunks,
-           uintptr_t tensors, uintptr_t adapt, uintptr_t partials, uintptr_t ratio, float lr,
-           double beta1, double beta2, float eps, float weight_decay, float grad_scale, float eta,
-           float momentum, float dampening, int nesterov, int first, float bc1, float bc2,
-           uintptr_t step, uintptr_t lr_ptr, uintptr_t stream) {
-          LayerwiseArgs a{};
-          a.kind = kind;
-          a.param = param;
-          a.grad = grad;
-          a.grad_dtype = grad_dtype;
-          a.state1 = state1;
-          a.state2 = state2;
-          a.shadow = shadow;
-          a.chunks = chunks;
-          a.num_chunks = num_chunks;
-          a.tensors = tensors;
-          a.adapt = adapt;
-          a.partials = partials;
-          a.ratio = ratio;
-          a.lr = lr;
-          a.beta1 = (float)beta1;
-          a.beta2 = (float)beta2;
-          a.beta1d = beta1;
-          a.beta2d = beta2;
-          a.eps = eps;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.eta = eta;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.bc1 = bc1;
-          a.bc2 = bc2;
-          a.step = step;
-          a.lr_ptr = lr_ptr;
-          a.stream = stream;
-          if (op == 0) ew_layerwise_stage(a);
-          else if (op == 1) ew_layerwise_apply(a);
-          else throw std::runtime_error("ewdml layerwise: unknown op");
-        });
-
-  m.def("clip",
-        [](int op, const Ptrs& grads, const Mask& mask, int T, uintptr_t chunks, int C,
-           uintptr_t partials, int chunk0, int total_chunks, uintptr_t state, float max_norm,
-           uintptr_t stream) {
-          ClipArgs a{};
-          a.src = grad_src(grads, mask);
-          a.num_tensors = T;
-          a.chunks = chunks;
-          a.num_chunks = C;
-          a.partials = partials;
-          a.chunk0 = chunk0;
-          a.total_chunks = total_chunks;
-          a.state = state;
-          a.max_norm = max_norm;
-          a.stream = stream;
-          if (op == 0) ew_clip_norm(a);
-          else if (op == 1) ew_clip_scale(a);
-          else throw std::runtime_error("ewdml clip: unknown op");
-        });
-
-  m.def("outer_apply",
-        [](uintptr_t anchor, uintptr_t data, uintptr_t momentum, uintptr_t delta,
-           uintptr_t shadow, uintptr_t stats, long long n, long long stats_rows, float lr,
-           float mu, int nesterov, uintptr_t stream) {
-          OuterArgs a{};
-          a.anchor = anchor;
-          a.data = data;
-          a.momentum = momentum;
-          a.delta = delta;
-          a.shadow = shadow;
-          a.stats = stats;
-          a.stream = stream;
-          a.n = n;
-          a.stats_rows = stats_rows;
-          a.lr = lr;
-          a.mu = mu;
-          a.nesterov = nesterov;
-          ew_outer_apply(a);
-        });
+  m.def("topk_decode_apply", &ew_topk_decode_apply);
+  m.def("qsgd_decode_apply", &ew_qsgd_decode_apply);
+  m.def("sign_reduce_encode", &ew_sign_reduce_encode);
+  m.def("sign_decode_onebit", &ew_sign_decode_onebit);
+  m.def("sign_decode_lamb_stage", &ew_sign_decode_lamb_stage);
+  m.def("lamb_onebit_apply", &ew_lamb_onebit_apply);
+  m.def("sign_decode_apply", &ew_sign_decode_apply);
+  m.def("mx_decode_apply", &ew_mx_decode_apply);
+  m.def("tern_decode_apply", &ew_tern_decode_apply);
+  m.def("psgd_project", &ew_psgd_project);
+  m.def("psgd_orth", &ew_psgd_orth);
+  m.def("psgd_backproject", &ew_psgd_backproject);
+  m.def("psgd_decode_apply", &ew_psgd_decode_apply);
+  m.def("sgd_flat", &ew_sgd_flat);
+  m.def("adam_flat", &ew_adam_flat);
+  m.def("lion_flat", &ew_lion_flat);
+  m.def("lion_vote_apply", &ew_lion_vote_apply);
+  m.def("vote_reduce", &ew_vote_reduce);
+  m.def("layerwise_stage", &ew_layerwise_stage);
+  m.def("layerwise_apply", &ew_layerwise_apply);
+  m.def("outer_apply", &ew_outer_apply);
 
   m.def("cast_scale", &ew_cast_scale);
 
+  // these two launchers take the pointer table as raw arrays, not as a GradSrc
   m.def("pack_grads",
         [](const Ptrs& grads, const Mask& mask, int T, uintptr_t chunks, int C, uintptr_t dst,
            int dst_dtype, float scale, uintptr_t stream) {
@@ -729,23 +226,8 @@ PYBIND11_MODULE(_C, m) {
         });
 
   m.def("sgd_ptrs",
-        [](const Ptrs& grads, const Mask& mask, int T, uintptr_t chunks, int C, uintptr_t param,
-           uintptr_t mom, uintptr_t shadow, float lr, float momentum, float dampening,
-           float weight_decay, float grad_scale, int nesterov, int first, uintptr_t stream,
-           uintptr_t lr_ptr) {
-          SgdFlatArgs a{};
-          a.param = param;
-          a.mom = mom;
-          a.shadow = shadow;
-          a.stream = stream;
-          a.lr = lr;
-          a.momentum = momentum;
-          a.dampening = dampening;
-          a.weight_decay = weight_decay;
-          a.grad_scale = grad_scale;
-          a.nesterov = nesterov;
-          a.first = first;
-          a.lr_ptr = lr_ptr;
+        [](const Ptrs& grads, const Mask& mask, int T, uintptr_t chunks, int C,
+           const SgdFlatArgs& a) {
           ew_sgd_ptrs(grads.data(), (int)grads.size(), mask.data(), (int)mask.size(), T, chunks,
                       C, a);
         });

@@ -1,5 +1,10 @@
 // Host-side entry points of the ewdml HIP kernels (C++ only, no HIP types), bound to Python in
 // bindings.cpp.  Pointers are device addresses passed as integers; `stream` is a hipStream_t.
+//
+// The *Args structs of the codecs and optimizers are the Python interface: bindings.cpp binds each
+// as a class whose fields ops/__init__.py sets by name, so a new field needs one F(field) there
+// (and nothing else).  T() in Python is T{}: every field zero, but for an embedded StepArgs, which
+// starts as Python's StepArgs() does: all zero with grad_scale 1.  GradSrc members are not bound.
 #pragma once
 #include <stdexcept>
 #include <string>

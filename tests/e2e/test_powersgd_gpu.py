@@ -58,8 +58,10 @@ def test_four_launches_and_two_collectives_per_bucket_and_step(monkeypatch):
     tr = _trainer(SYN + ["--hip-graph", "off"], 3)
     tr.train_step()
     launches, colls = [], []
-    real = C.psgd
-    monkeypatch.setattr(ops._C, "psgd", lambda op, *a: (launches.append(op), real(op, *a))[1])
+    for op, name in enumerate(("project", "orth", "backproject", "decode_apply")):
+        real = getattr(C, "psgd_" + name)
+        monkeypatch.setattr(ops._C, "psgd_" + name,
+                            lambda a, op=op, real=real: (launches.append(op), real(a))[1])
     ar = tr.comm.all_reduce
     monkeypatch.setattr(tr.comm, "all_reduce", lambda t, *a, **k: (colls.append(t.numel()),
                                                                    ar(t, *a, **k))[1])

@@ -173,8 +173,11 @@ def test_two_launches_per_step_range(kind, monkeypatch):
     flat = make_flat(SHAPES6, device=DEV, bucket_bytes=BUCKET_BYTES)
     opt = _opt(kind, flat)
     g = make_grad(flat, 0)
-    calls, real = [], C.layerwise
-    monkeypatch.setattr(ops._C, "layerwise", lambda op, *a: (calls.append(op), real(op, *a))[1])
+    calls = []
+    for op, name in enumerate(("layerwise_stage", "layerwise_apply")):
+        real = getattr(C, name)
+        monkeypatch.setattr(ops._C, name,
+                            lambda a, op=op, real=real: (calls.append(op), real(a))[1])
     opt.step(grad=g)  # the whole model: builds its plan
     assert calls == [0, 1]
     for b in flat.buckets:

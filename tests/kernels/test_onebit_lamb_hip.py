@@ -261,8 +261,11 @@ def test_two_launches_per_bucket(monkeypatch):
     c = Case([8192 + 9, 300], seed=1)
     d = c.device()
     recv = _payloads(c.plan, c.lay, 2, seed=3).to(DEV)
-    calls, real = [], C.onebit_lamb
-    monkeypatch.setattr(ops._C, "onebit_lamb", lambda op, *a: (calls.append(op), real(op, *a))[1])
+    calls = []
+    for op, name in enumerate(("sign_decode_lamb_stage", "lamb_onebit_apply")):
+        real = getattr(C, name)
+        monkeypatch.setattr(ops._C, name,
+                            lambda a, op=op, real=real: (calls.append(op), real(a))[1])
     c.dev_step(d, recv, TW + 1, 1e-3, 0.0, 0.5)
     assert calls == [0, 1]
     monkeypatch.undo()

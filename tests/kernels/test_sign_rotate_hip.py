@@ -279,24 +279,33 @@ def test_bad_operands_rejected():
     C = ops.require()
     ptrs, mask = ops.grad_pointers(dp, g)
     stream = torch.cuda.current_stream().cuda_stream
-    enc = (lay.nbytes, plan.num_tensors, plan.num_chunks, lay.scales, lay.codes, stream)
+    def encode(**fields):
+        a = dict(resid=0, chunks=dp.chunks.data_ptr(), payload=pay.data_ptr(),
+                 payload_bytes=lay.nbytes, num_tensors=plan.num_tensors,
+                 num_chunks=plan.num_chunks, scales_off=lay.scales, bits_off=lay.codes,
+                 stream=stream, slots=0, slot_end=0, rotate=1, rot_key=KEY)
+        a.update(fields)
+        C.sign_encode(ops._args(C.SignEncodeArgs, **a), ptrs, mask)
+
     with pytest.raises(RuntimeError, match="missing table"):
-        C.sign_encode(ptrs, mask, 0, 0, pay.data_ptr(), *enc, 0, 0, 1, KEY)
+        encode(chunks=0)
     with pytest.raises(RuntimeError, match="misaligned"):
-        C.sign_encode(ptrs, mask, g.data_ptr() + 4, dp.chunks.data_ptr(), pay.data_ptr(), *enc,
-                      0, 0, 1, KEY)
+        encode(resid=g.data_ptr() + 4)
     with pytest.raises(RuntimeError, match="do not fit"):
-        C.sign_encode(ptrs, mask, 0, dp.chunks.data_ptr(), pay.data_ptr(), lay.nbytes - 16,
-                      *enc[1:], 0, 0, 1, KEY)
+        encode(payload_bytes=lay.nbytes - 16)
     with pytest.raises(RuntimeError, match="slot-addressed"):
-        C.sign_encode(ptrs, mask, 0, dp.chunks.data_ptr(), pay.data_ptr(), *enc,
-                      dp.chunks.data_ptr(), lay.nbytes, 1, KEY)
-    dec = (plan.num_chunks, lay.scales, lay.codes)
+        encode(slots=dp.chunks.data_ptr(), slot_end=lay.nbytes)
+
+    def decode(chunks, grad_out):
+        C.sign_decode_apply(ops._args(
+            C.SignDecodeArgs, recv=pay.data_ptr(), nranks=1, stride=lay.nbytes, chunks=chunks,
+            num_chunks=plan.num_chunks, scales_off=lay.scales, bits_off=lay.codes,
+            step=C.StepArgs(grad_out=grad_out), stream=stream, slots=0, slot_end=0, rotate=1,
+            rot_key=KEY))
+
     with pytest.raises(RuntimeError, match="missing table"):
-        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, 0, *dec,
-                            C.StepArgs(grad_out=g.data_ptr()), stream, 0, 0, 1, KEY)
+        decode(0, g.data_ptr())
     with pytest.raises(RuntimeError, match="misaligned"):
-        C.sign_decode_apply(pay.data_ptr(), 1, lay.nbytes, dp.chunks.data_ptr(), *dec,
-                            C.StepArgs(grad_out=g.data_ptr() + 4), stream, 0, 0, 1, KEY)
+        decode(dp.chunks.data_ptr(), g.data_ptr() + 4)
     torch.cuda.synchronize()
     assert not pay.any() and not g.any()  # nothing ran
