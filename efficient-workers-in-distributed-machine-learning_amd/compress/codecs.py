@@ -26,6 +26,10 @@
   * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
     al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
     methods below)
+  * ``sketch`` -- a count sketch of the error-compensated gradient (SketchedSGD, Ivkin et al.
+    2019): ``rows`` x W fp32 table summed by one all-reduce, the heavy coordinates of the *sum*
+    recovered from it and their exact values summed by a second one (``parallel/sketch.py``; the
+    ``sk_*`` methods below); ``ratio`` / ``dense_below`` give k per tensor as for ``topk``
 
 Device tensors go through the HIP kernels (``ops``); CPU tensors through the torch oracle.  On a
 GPU box a missing extension raises instead of silently falling back.
@@ -40,11 +44,11 @@ from .. import ops
 # variants before they have kernels; needs flat gradient views, EWDML_GRAD_VIEWS=1)
 _FORCE_ORACLE = os.environ.get("EWDML_ORACLE") == "1"
 from . import oracle
-from .plan import POWERSGD_RANKS, BucketPlan, Layout
+from .plan import POWERSGD_RANKS, SKETCH_ROWS, BucketPlan, Layout, SketchPlan
 from .rng import stream_key
 
 KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx",
-         "tern")
+         "tern", "sketch")
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
 MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
@@ -54,7 +58,7 @@ class Codec:
     def __init__(self, kind: str = "topk_qsgd", ratio: float = 0.01, levels: int = 127,
                  bits: int = 8, norm: str = "max", seed: int = 0, dense_below: int = 0,
                  rank: int = 4, aggregate: str = "majority", rotate: str = "none",
-                 fmt: str = None, clip: float = 2.5):
+                 fmt: str = None, clip: float = 2.5, rows: int = None, width: float = None):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
@@ -84,8 +88,18 @@ class Codec:
         if not clip >= 0.0:
             raise ValueError("tern clip must be >= 0 (0: no clipping)")
         self.clip = clip
+        if (rows is not None or width is not None) and kind != "sketch":
+            raise ValueError("rows and width belong to the sketch codec")
+        if kind == "sketch":
+            rows = 3 if rows is None else rows
+            width = 2.0 if width is None else float(width)
+            if rows not in SKETCH_ROWS:
+                raise ValueError(f"sketch rows must be one of {SKETCH_ROWS}, not {rows!r}")
+            if not width > 0.0:
+                raise ValueError(f"sketch width must be > 0, not {width!r}")
+        self.rows, self.width = rows, width
         # the sign, vote and low-rank codecs have neither bits nor levels; tern's are fixed
-        if kind not in ("sign", "powersgd", "vote", "tern") and bits not in (4, 8):
+        if kind not in ("sign", "powersgd", "vote", "tern", "sketch") and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -128,6 +142,8 @@ class Codec:
             return "mx" + self.fmt
         if self.kind == "tern":
             return f"tern2b(c={self.clip:g})" if self.clip > 0 else "tern2b"
+        if self.kind == "sketch":
+            return f"sketch-r{self.rows}"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -138,6 +154,9 @@ class Codec:
         if self.kind == "powersgd":
             raise ValueError("the PowerSGD codec is bound by its own exchange (bind_powersgd; "
                              "--compress powersgd on the trainer)")
+        if self.kind == "sketch":
+            raise ValueError("the sketch codec is bound by its own exchange (bind_sketch; "
+                             "--compress sketch on the trainer)")
         if self.allreduce:
             self.layouts = [None] * len(self.plans)
             return self
@@ -158,12 +177,15 @@ class Codec:
     def set_ratio(self, ratio: float):
         """Switch a bound top-k codec to another density (top-k warm-up): the per-tensor k, the
         payload layouts and the device tables change; bindings are cached per ratio."""
-        if self.kind not in ("topk", "topk_qsgd"):
+        if self.kind not in ("topk", "topk_qsgd", "sketch"):
             raise ValueError("only top-k codecs have a density")
         if not 0.0 < ratio <= 1.0:
             raise ValueError("top-k ratio must be in (0, 1]")
         if ratio == self.ratio:
             return self
+        if self.kind == "sketch":  # k per tensor, and with it the table width, change
+            self.ratio = ratio
+            return self.bind_sketch(self.plans, self.device)
         hit = self._bound.get(ratio)
         if hit is None:
             plans = [BucketPlan(p.numels, p.offsets, ratio, p.bucket_offset, p.length,
@@ -554,6 +576,79 @@ class Codec:
         qa = oracle.powersgd_reconstruct_apply(resid, p, q, lrp, inv_n, param, mom, hp, first,
                                                grad_out)
         q_out[:lrp.q_floats].copy_(qa)
+
+    # -- count sketch (parallel/sketch.py): stage + table, estimate + select + gather, apply -------
+    def bind_sketch(self, plans, device):
+        """Bind the buckets' top-k plans at this codec's density: per bucket the ``topk`` payload
+        layout (its index sections carry the selection, its values the second all-reduce) and
+        the :class:`SketchPlan`; on the GPU their device tables.  Called again by ``set_ratio``
+        (density warm-up: k, W and the layouts change); bindings are cached per ratio."""
+        if self.kind != "sketch":
+            raise ValueError("the sketch exchange needs the sketch codec")
+        self.device = torch.device(device)
+        if not hasattr(self, "_bound"):
+            self._bound = {}
+        hit = self._bound.get(self.ratio)
+        if hit is None:
+            bplans = [BucketPlan(p.numels, p.offsets, self.ratio, p.bucket_offset, p.length,
+                                 self.dense_below) for p in plans]
+            layouts = [Layout.build("topk", p) for p in bplans]
+            sk = [SketchPlan(p, self.rows, self.width, *oracle.sketch_keys(self.seed, b))
+                  for b, p in enumerate(bplans)]
+            dplans, sk_dev = [], None
+            if self.device.type == "cuda" and not _FORCE_ORACLE:
+                if ops.hip_required():
+                    ops.require()
+                dplans = [ops.DevicePlan(p, self.device) for p in bplans]
+                sk_dev = [ops.SketchTables(t, self.device) for t in sk]
+            hit = self._bound[self.ratio] = (bplans, layouts, dplans, sk, sk_dev)
+        self.plans, self.layouts, self.dplans, self.sk, self.sk_dev = hit
+        return self
+
+    def sk_sketch(self, b: int, grad: torch.Tensor, resid: torch.Tensor, table: torch.Tensor):
+        """``resid <- acc = grad + resid`` on the sketched tensors of bucket ``b`` and ``table`` =
+        the count sketch of ``acc``.  Two launches on the GPU."""
+        if self._ts_kernel(grad):
+            ops.sketch_stage(self.sk_dev[b], grad, resid)
+            ops.sketch_accum(self.sk_dev[b], resid, table)
+            return
+        sp = self.sk[b]
+        oracle.sketch_stage(grad, resid, sp)
+        table[:sp.table_floats].copy_(oracle.sketch_accumulate(resid, sp))
+
+    def sk_select_gather(self, b: int, table: torch.Tensor, est: torch.Tensor,
+                         grad: torch.Tensor, resid: torch.Tensor, payload: torch.Tensor):
+        """From the summed ``table`` of bucket ``b``: the estimate (``est``, a bucket-length
+        scratch whose dense tensors and pads stay 0), the top-k selection of the estimate into
+        ``payload`` and this rank's own values at the selected coordinates in its values section,
+        cleared from ``resid``.  The estimate, the exact top-k passes and the gather on the GPU."""
+        sp, lay = self.sk[b], self.layouts[b]
+        if self._ts_kernel(table):
+            st, dp = self.sk_dev[b], self.dplans[b]
+            ops.sketch_estimate(st, table, est)
+            ops.topk_encode(dp, est, payload, lay, self.levels, "max", 0, predict=False)
+            ops.sketch_gather(st, dp, payload, lay, grad, resid)
+            return
+        est[:sp.plan.length].copy_(oracle.sketch_estimate(table, sp))
+        payload[:lay.nbytes].copy_(oracle.sketch_select(est[:sp.plan.length], sp, lay))
+        oracle.sketch_gather(payload, grad, resid, sp, lay)
+
+    def sk_values(self, b: int, payload: torch.Tensor) -> torch.Tensor:
+        """The fp32 values section of bucket ``b``'s payload: what the second all-reduce sums."""
+        lay = self.layouts[b]
+        return payload[lay.codes:lay.codes + 4 * self.plans[b].total_k].view(torch.float32)
+
+    def sk_decode_apply_sgd(self, b: int, payload: torch.Tensor, inv_n: float, param, mom, hp,
+                            first: bool, grad_out=None, shadow=None):
+        """``g^ = vals * inv_n`` at the selected coordinates of bucket ``b`` and 0 elsewhere, and
+        the fused SGD step (``param`` None: ``g^`` to ``grad_out`` only): the plain top-k decode
+        of the one summed payload."""
+        recv = payload[:self.layouts[b].nbytes].unsqueeze(0)
+        if param is None:
+            self.decode(b, recv, grad_out, inv_n)
+            return
+        self.decode_apply_sgd(b, recv, inv_n, param, mom, hp, first, grad_out=grad_out,
+                              shadow=shadow)
 
     def decode_apply_onebit(self, b: int, recv: torch.Tensor, inv_n: float, param: torch.Tensor,
                             exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,

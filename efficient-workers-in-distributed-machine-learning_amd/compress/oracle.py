@@ -35,6 +35,10 @@ Reference semantics being reproduced:
     element, one fp32 scaler per tensor clipped at ``clip`` times the tensor's root mean square
     (about zero, not about the mean); the sum of squares runs in the kernel's order
     (``_tern_sumsq``), so scalers, codes and residuals are bitwise the kernels'.
+  * Count sketch (no reference counterpart; SketchedSGD, Ivkin et al., NeurIPS 2019): ``sketch_*``
+    -- the table of the error-compensated gradient under a per-chunk rotation hash, summed in the
+    kernel's one order, the median estimate and the gather of the selected coordinates; bitwise
+    the kernels'.
 """
 import numpy as np
 import torch
@@ -1287,3 +1291,132 @@ def powersgd_init_q(lrp, seed: int, bucket: int, dtype=torch.float32):
                 rest = Q[:, c + 1:]
                 rest.sub_((col * rest).sum(dim=0, keepdim=True) * col)
     return q
+
+
+# ---------------------------------------------------------------------------------------------
+# Count sketch (SketchedSGD, Ivkin et al., NeurIPS 2019; no reference counterpart): the table of
+# the error-compensated gradient of one bucket (``plan.SketchPlan``), the per-coordinate estimate
+# from the summed table, and the gather of the selected coordinates' own values.  The CPU path
+# and the definition of every bit of ``ops/csrc/sketch_codec.hip``.  The selection between the
+# estimate and the gather is the project's top-k (``encode_topk`` of the estimate in the ``topk``
+# layout: its count / index / bitmap sections are the selection) and the apply is ``decode_sum``
+# of the one summed payload.
+# ---------------------------------------------------------------------------------------------
+SKETCH_SHIFT_TAG = 0x534B5348  # "SKSH": the rank slot of stream_key, as ROT_TAG
+SKETCH_SIGN_TAG = 0x534B5347  # "SKSG"
+
+
+def sketch_keys(seed: int, bucket: int):
+    """(sk_key, sg_key) of a bucket: the keys of the column shifts and of the signs, the same on
+    every rank and every step."""
+    return (rng.stream_key(seed, bucket, SKETCH_SHIFT_TAG),
+            rng.stream_key(seed, bucket, SKETCH_SIGN_TAG))
+
+
+def _sketch_hash(sp, start: int, ln: int, device) -> torch.Tensor:
+    """``mix32(gidx ^ sg_key)`` of ``ln`` consecutive elements from bucket offset ``start``; bit
+    j is their sign in row j."""
+    gidx = sp.plan.bucket_offset + start + torch.arange(ln, dtype=torch.int64, device=device)
+    return rng.mix32((gidx & rng.M32) ^ sp.sg_key)
+
+
+def _sketch_signed(x: torch.Tensor, h: torch.Tensor, j: int) -> torch.Tensor:
+    return torch.where(((h >> j) & 1).bool(), -x, x)
+
+
+def sketch_stage(grad: torch.Tensor, resid: torch.Tensor, sp) -> None:
+    """``resid <- acc = grad + resid`` on the sketched tensors (in place; a dense tensor keeps no
+    residual)."""
+    for t in sp.sketched:
+        off, n = sp.plan.offsets[t], sp.plan.numels[t]
+        resid[off:off + n] = grad[off:off + n] + resid[off:off + n]
+
+
+def sketch_accumulate(resid: torch.Tensor, sp) -> torch.Tensor:
+    """The table ``T[R][W]`` (flat, row-major) of the staged ``resid``.  Per row: the chunks in
+    groups of ``SKETCH_SUM_GROUP`` consecutive chunk indices; within a group sequential fp32 adds
+    in ascending chunk order from +0.0, then the group partials in ascending group order from
+    +0.0.  (A chunk adds nothing to the columns outside its image, which is bitwise adding +0.0:
+    no sum here is ever -0.0.)"""
+    from .plan import SKETCH_SUM_GROUP
+
+    W = sp.W
+    table = torch.zeros(sp.rows * W, dtype=torch.float32, device=resid.device)
+    C = sp.plan.num_chunks
+    for j in range(sp.rows):
+        total = table[j * W:(j + 1) * W]
+        for g0 in range(0, C, SKETCH_SUM_GROUP):
+            part = torch.zeros(W, dtype=torch.float32, device=resid.device)
+            for c in range(g0, min(g0 + SKETCH_SUM_GROUP, C)):
+                start, ln = sp.chunk_rows[c]
+                if ln == 0:
+                    continue
+                o = sp.shifts[j][c]
+                v = _sketch_signed(resid[start:start + ln],
+                                   _sketch_hash(sp, start, ln, resid.device), j)
+                head = min(ln, W - o)
+                part[o:o + head] += v[:head]
+                if head < ln:  # the image wraps
+                    part[:ln - head] += v[head:]
+            total += part
+    return table
+
+
+def _cx(a, b):
+    s = b < a
+    return torch.where(s, b, a), torch.where(s, a, b)
+
+
+def sketch_median(v):
+    """The median of 1, 3 or 5 tensors by a compare-exchange network (a select on ``b < a``: no
+    arithmetic; equal values and NaNs stay in place), as the kernel's ``sk_median``."""
+    v = list(v)
+    if len(v) == 3:
+        order = ((0, 1), (1, 2), (0, 1))
+    elif len(v) == 5:
+        order = ((0, 1), (3, 4), (2, 4), (2, 3), (1, 4), (0, 3), (0, 2), (1, 3), (1, 2))
+    elif len(v) == 1:
+        order = ()
+    else:
+        raise ValueError("the median network takes 1, 3 or 5 values")
+    for a, b in order:
+        v[a], v[b] = _cx(v[a], v[b])
+    return v[len(v) // 2]
+
+
+def sketch_estimate(table: torch.Tensor, sp) -> torch.Tensor:
+    """fp32 [plan.length]: ``est[i]`` = the median over the rows of ``sign_j(i) * T[j][(p +
+    o[j][c]) mod W]``; 0 on dense tensors and pads."""
+    W = sp.W
+    est = torch.zeros(sp.plan.length, dtype=torch.float32, device=table.device)
+    for c, (start, ln) in enumerate(sp.chunk_rows):
+        if ln == 0:
+            continue
+        h = _sketch_hash(sp, start, ln, table.device)
+        p = torch.arange(ln, dtype=torch.int64, device=table.device)
+        est[start:start + ln] = sketch_median(
+            [_sketch_signed(table[j * W + (p + sp.shifts[j][c]) % W], h, j)
+             for j in range(sp.rows)])
+    return est
+
+
+def sketch_select(est: torch.Tensor, sp, layout: Layout) -> torch.Tensor:
+    """The ``topk`` payload of the estimate: per tensor ``topk_indices(est, k)`` in its count /
+    index / bitmap sections (the values section holds the estimates until the gather)."""
+    if layout.kind != "topk":
+        raise ValueError("the sketch selects through the plain top-k layout")
+    return encode_topk(est, sp.plan, layout, 0, "max", 0)
+
+
+def sketch_gather(payload: torch.Tensor, grad: torch.Tensor, resid: torch.Tensor, sp,
+                  layout: Layout) -> None:
+    """The payload's values section <- this rank's ``acc`` at the selected coordinates in payload
+    order (``grad`` itself on dense tensors), and ``resid[selected] = 0`` (in place)."""
+    pos, _ = _decoded_entries(payload, sp.plan, layout, 0)
+    src = resid.clone()
+    for t, d in enumerate(sp.dense):
+        if d:
+            off, n = sp.plan.offsets[t], sp.plan.numels[t]
+            src[off:off + n] = grad[off:off + n]
+    _section(payload, layout.codes, sp.plan.total_k, torch.float32).copy_(src[pos])
+    resid[pos] = 0.0  # dense tensors' residual is 0 already

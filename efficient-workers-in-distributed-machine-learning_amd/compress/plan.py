@@ -36,9 +36,12 @@ exchange is a fixed-size all-gather with no size handshake):
 from dataclasses import dataclass, field
 from typing import List
 
+import math
 import os
 
 import torch
+
+from .rng import mix32_int
 
 CHUNK = 8192
 BM_WORDS = CHUNK // 32  # bitmap words per chunk
@@ -422,3 +425,69 @@ class LowRankPlan:
     def tile_table(self, device) -> torch.Tensor:
         """int32 [W, 4]: the back-project (first ``num_mat_tiles``) and reconstruct items."""
         return torch.tensor(self.tile_items, dtype=torch.int32, device=device)
+
+
+SKETCH_ROWS = (1, 3, 5)  # odd: the median of a coordinate's row values is one of them
+# summation order of a count-sketch table entry (ops/csrc/sketch_codec.hip k_sketch_accum and
+# compress/oracle.py sketch_accumulate): chunks in groups of this many consecutive chunk indices
+SKETCH_SUM_GROUP = 64
+
+
+class SketchPlan:
+    """One bucket of the count-sketch exchange (``parallel/sketch.py``; SketchedSGD, Ivkin et al.,
+    NeurIPS 2019) over the bucket's top-k ``BucketPlan``.
+
+    A tensor with ``k == numel`` is *dense*: it is not sketched, always selected whole and keeps
+    no residual.  ``K`` = the sum of ``k`` over the sketched tensors and the table has ``rows``
+    rows of ``W = CHUNK * max(1, ceil(width * K / CHUNK))`` fp32 columns (``W >= CHUNK``: two
+    elements of one chunk never share a column).
+
+    The hash is a per-chunk rotation.  In row ``j`` chunk ``c`` (its index in the bucket) is
+    shifted by ``shifts[j][c] = (mix32((c * 8 + j) ^ sk_key) * W) >> 32`` and its element at
+    chunk-local position ``p`` lands in column ``(p + shifts[j][c]) mod W`` with the sign bit
+    ``j`` of ``mix32(gidx ^ sg_key)``, ``gidx = bucket_offset + offset`` (the QSGD streams'
+    index).  ``set_shift`` overrides one shift (the tests' wrap and no-wrap edges).
+
+    ``chunk_rows[c] = (start, len)`` with ``len = 0`` for the chunks of dense tensors."""
+
+    def __init__(self, bucket_plan: BucketPlan, rows: int, width: float, sk_key: int,
+                 sg_key: int):
+        if rows not in SKETCH_ROWS:
+            raise ValueError(f"sketch rows must be one of {SKETCH_ROWS}, not {rows!r}")
+        if not float(width) > 0.0:
+            raise ValueError(f"sketch width must be > 0, not {width!r}")
+        if bucket_plan.num_tensors > MAX_SEGMENTS:
+            raise ValueError(f"bucket has {bucket_plan.num_tensors} tensors (max {MAX_SEGMENTS})")
+        self.plan, self.rows, self.width = bucket_plan, int(rows), float(width)
+        self.sk_key, self.sg_key = sk_key & 0xFFFFFFFF, sg_key & 0xFFFFFFFF
+        p = bucket_plan
+        self.dense = [k == n for k, n in zip(p.ks, p.numels)]
+        self.sketched = [t for t, d in enumerate(self.dense) if not d]
+        self.K = sum(p.ks[t] for t in self.sketched)
+        self.dense_elems = sum(n for n, d in zip(p.numels, self.dense) if d)
+        self.W = CHUNK * max(1, math.ceil(self.width * self.K / CHUNK))
+        if self.rows * self.W >= 1 << 31:
+            raise ValueError("sketch table of 2^31 floats or more: use smaller buckets")
+        self.table_floats = self.rows * self.W
+        self.chunk_rows = [(s, 0 if self.dense[t] else ln) for t, s, ln in
+                           zip(p.chunk_tensor, p.chunk_start, p.chunk_len)]
+        self.shifts = [[(mix32_int((c * 8 + j) ^ self.sk_key) * self.W) >> 32
+                        for c in range(p.num_chunks)] for j in range(self.rows)]
+
+    def set_shift(self, row: int, chunk: int, shift: int):
+        if not 0 <= shift < self.W:
+            raise ValueError("a shift is a column of the table")
+        self.shifts[row][chunk] = int(shift)
+
+    @property
+    def payload_floats(self) -> int:
+        """fp32 values the two all-reduces move: the table and one value per selected element."""
+        return self.table_floats + self.K + self.dense_elems
+
+    def row_table(self, device) -> torch.Tensor:
+        """int32 [C, 2]: start (rel. bucket), sketched length (0: a dense tensor's chunk)."""
+        return torch.tensor(self.chunk_rows, dtype=torch.int32, device=device)
+
+    def shift_table(self, device) -> torch.Tensor:
+        """int32 [R, C]: the column shift of every chunk in every row."""
+        return torch.tensor(self.shifts, dtype=torch.int32, device=device)

@@ -58,9 +58,14 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern
+    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern | sketch
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
+    # --compress sketch (count sketch, parallel/sketch.py): rows of the table, 1, 3 or 5 (None: 3;
+    # odd, so the median is one of the row values) and table columns per selected element, > 0
+    # (None: 2.0); k per tensor is --topk-ratio / --topk-dense-below's
+    sketch_rows: Optional[int] = None
+    sketch_width: Optional[float] = None
     # --compress sign: none | hadamard (the signs of a randomised Hadamard rotation of every chunk,
     # DRIVE / EDEN; the same payload, one inverse transform on the receiver)
     sign_rotate: str = "none"
@@ -360,7 +365,7 @@ class Config:
             c.error_feedback = ((c.compress in ("topk", "topk_qsgd", "sign")
                                  and c.topology == "allgather")
                                 or (c.compress == "sign" and c.topology == "twostage")
-                                or c.compress == "powersgd")
+                                or c.compress in ("powersgd", "sketch"))
         if c.optimizer == "onebit_lamb":
             # 1-bit LAMB's compressed stage is the sign codec's all-gather with its residual, as
             # 1-bit Adam's; refused ahead of the exchanges' own checks so the reason names it
@@ -448,6 +453,57 @@ class Config:
                 raise ValueError("--compress powersgd " + why)
         elif c.powersgd_rank != Config.powersgd_rank:
             raise ValueError("--powersgd-rank belongs to --compress powersgd")
+        if c.compress == "sketch":
+            # the count sketch (parallel/sketch.py): two dependent all-reduces per bucket (the
+            # table, then the selected coordinates' values), always with its plain residual,
+            # averaged with 1/N in its decode
+            if c.sketch_rows is None:
+                c.sketch_rows = 3
+            if c.sketch_width is None:
+                c.sketch_width = 2.0
+            why = None
+            if c.sketch_rows not in (1, 3, 5):
+                why = (f"takes the median of an odd number of rows: --sketch-rows must be 1, 3 or "
+                       f"5, not {c.sketch_rows}")
+            elif not float(c.sketch_width) > 0.0:
+                why = (f"sizes its table in columns per selected element: --sketch-width must be "
+                       f"> 0, not {c.sketch_width!r}")
+            elif c.topology != "allgather":
+                why = (f"sums its tables by all-reduce on every rank: it does not run with "
+                       f"--topology {c.topology}")
+            elif c.sync_every > 1:
+                why = "exchanges every step: it does not run with --sync-every > 1"
+            elif c.select_best:
+                why = "sums all workers' sketches: it does not run with --select-best"
+            elif not c.error_feedback:
+                why = ("sends only the heavy coordinates and relies on its residual for the rest: "
+                       "it does not run with --no-error-feedback")
+            elif c.ef_mode != Config.ef_mode:
+                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
+                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
+            elif c.predivide != 1.0:
+                why = ("averages the summed values with 1/N in its decode: it does not run with "
+                       "--predivide other than 1")
+            elif c.pull_compress is not None:
+                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
+            elif c.hip_graph in ("full", "segmented"):
+                why = (f"issues its two all-reduces, the estimate, the selection and the gather "
+                       f"between two graphs: --hip-graph {c.hip_graph} is not supported (auto "
+                       f"resolves to split)")
+            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
+                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
+                       f"sign-compressed momentum (--compress sign)")
+            if why is not None:
+                raise ValueError("--compress sketch " + why)
+            if c.hip_graph == "auto":  # graph A -> eager all-reduces, select, gather -> graph B
+                c.hip_graph = "split"
+        elif c.sketch_rows is not None:
+            raise ValueError("--sketch-rows belongs to --compress sketch")
+        elif c.sketch_width is not None:
+            raise ValueError("--sketch-width belongs to --compress sketch")
+        if c.pull_compress == "sketch":
+            raise ValueError("--pull-compress sketch: the sketch codec has no parameter-server "
+                             "form")
         if c.optimizer == "onebit_adam":
             # the compressed stage is the sign codec's all-gather with its residual; every option
             # that changes what is exchanged, or that scales it, breaks the momentum's linearity
@@ -587,7 +643,9 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote",
-               "mx", "tern"])
+               "mx", "tern", "sketch"])
+    a("--sketch-rows", type=int, default=None)
+    a("--sketch-width", type=float, default=None)
     a("--mx-format", type=str, default=None, choices=["fp8", "fp4"])
     a("--tern-clip", type=float, default=None)
     a("--vote-aggregate", type=str, default=None, choices=["majority", "average"])

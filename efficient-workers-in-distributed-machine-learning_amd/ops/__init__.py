@@ -270,8 +270,11 @@ def _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_deca
 
 
 def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
-                resid=None, key_tensor=None, dgc=None, apply=None):
-    """``dgc``: momentum-corrected error feedback, ``{velocity, momentum, dampening, nesterov,
+                resid=None, key_tensor=None, dgc=None, apply=None, predict=None):
+    """``predict`` False: this encode takes the exact full passes whatever EWDML_TOPK_PREDICT
+    says (the count sketch's selection, whose input is not a gradient that drifts slowly).
+
+    ``dgc``: momentum-corrected error feedback, ``{velocity, momentum, dampening, nesterov,
     weight_decay, param}`` (bucket views; compress/oracle.py dgc_accumulate).
 
     ``apply`` (a world of one, where the all-gathered payload is this rank's own): the write pass
@@ -320,7 +323,9 @@ def topk_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, k
         key_ptr=_keyp(key_tensor), stream=_stream(), vel=_ptr(vel), param=_ptr(par),
         dgc_momentum=mom, dgc_damp1=damp1, dgc_wd=wd, dgc_nesterov=nest, dgc_mask=dmask,
         dgc_lr_ptr=_lrp(lrt), bucket_len=dp.plan.length, cblocks=_ptr(dp.cblocks),
-        num_cblocks=dp.plan.num_cblocks, predict=int(_TOPK_PREDICT), lb_fault=int(_LB_FAULT[0]),
+        num_cblocks=dp.plan.num_cblocks,
+        predict=int(_TOPK_PREDICT if predict is None else bool(predict)),
+        lb_fault=int(_LB_FAULT[0]),
         max_k=int(max(dp.plan.ks)) if dp.plan.ks else 0, **_tables(dp),
         **_apply_args(dp, apply, norm), dgc_stamps=_stamps_ptr(dp, dgc)), ptrs, mask)
 
@@ -914,6 +919,91 @@ def psgd_decode_apply(lt: LowRankTables, resid, p, q, q_out, inv_n, param=None, 
                  nesterov, first, None, 0, 0, lr_tensor)
     _psgd("decode_apply", lt, lt.tiles, len(lt.lrp.tile_items), resid=resid, p=p, q=q,
           inv_n=inv_n, q_out=q_out, step=step)
+
+
+# Count sketch (csrc/sketch_codec.hip): a table entry sums its chunks in groups of this many
+# consecutive chunk indices, sequentially within a group and then over the groups (SK_GROUP;
+# compress/plan.py SKETCH_SUM_GROUP and compress/oracle.py sketch_accumulate mirror it)
+SKETCH_SUM_GROUP = 64
+
+
+class SketchTables:
+    """Device tables of one bucket of the count-sketch exchange (``compress/plan.py
+    SketchPlan``), checked once against the buffers the kernels index with them."""
+
+    def __init__(self, sp, device):
+        from ..compress.plan import SKETCH_SUM_GROUP as plan_group
+
+        if not (require().sketch_sum_group() == SKETCH_SUM_GROUP == plan_group):
+            raise RuntimeError("the sketch summation group of the kernel, ops and the plan differ")
+        self.sp, self.plan = sp, sp.plan
+        L, C = sp.plan.length, sp.plan.num_chunks
+        if len(sp.chunk_rows) != C or len(sp.shifts) != sp.rows:
+            raise ValueError("sketch tables do not fit their plan")
+        for start, ln in sp.chunk_rows:
+            if not (0 <= ln <= 8192 and 0 <= start and start + ln <= L and start % 4 == 0):
+                raise ValueError("sketch chunk row outside the bucket, or not at a multiple of 4 "
+                                 "elements")
+        for row in sp.shifts:
+            if len(row) != C or not all(0 <= o < sp.W for o in row):
+                raise ValueError("sketch shift outside the table")
+        self.rows = sp.row_table(device)
+        self.shifts = sp.shift_table(device)
+
+    def args(self, **fields):
+        sp = self.sp
+        return _args(require().SketchArgs, rows=_ptr(self.rows), shifts=_ptr(self.shifts),
+                     stream=_stream(), num_chunks=sp.plan.num_chunks, sketch_rows=sp.rows,
+                     width=sp.W, bucket_len=sp.plan.length, sg_key=sp.sg_key,
+                     bucket_offset=sp.plan.bucket_offset & 0xFFFFFFFF, **fields)
+
+
+def _sketch_table(st: SketchTables, table):
+    _check(table, torch.float32, "table")
+    if table.numel() < st.sp.table_floats:
+        raise ValueError(f"table has {table.numel()} floats, the sketch needs "
+                         f"{st.sp.table_floats}")
+
+
+def sketch_stage(st: SketchTables, grad, resid):
+    """Sketch launch 1: ``resid <- grad + resid`` on the sketched tensors of the bucket."""
+    _check_bucket(st, grad)
+    _check_bucket(st, resid, "resid")
+    require().sketch_stage(st.args(grad=_ptr(grad), resid=_ptr(resid)))
+
+
+def sketch_accum(st: SketchTables, resid, table):
+    """Sketch launch 2: ``table`` = the ``[R, W]`` count sketch of the staged ``resid``, bitwise
+    ``compress/oracle.py sketch_accumulate`` and the same from run to run."""
+    _check_bucket(st, resid, "resid")
+    _sketch_table(st, table)
+    require().sketch_accum(st.args(resid=_ptr(resid), table=_ptr(table)))
+
+
+def sketch_estimate(st: SketchTables, table, est):
+    """Sketch launch 3: ``est`` = per element the median of its rows' signed table entries
+    (dense tensors and pads are not written: they keep the buffer's zeros)."""
+    _sketch_table(st, table)
+    _check_bucket(st, est, "est")
+    require().sketch_estimate(st.args(table=_ptr(table), est=_ptr(est)))
+
+
+def sketch_gather(st: SketchTables, dp: DevicePlan, payload, layout, grad, resid):
+    """Sketch launch 4 (after ``topk_encode`` of the estimate into ``payload``): the payload's
+    values <- ``resid`` at the selected coordinates (``grad`` on dense tensors), ``resid`` cleared
+    there."""
+    if layout.kind != "topk" or dp.plan is not st.plan:
+        raise ValueError("the sketch gathers through its own plan's plain top-k payload")
+    _encode_dst(payload, layout)
+    _check_bucket(st, grad)
+    _check_bucket(st, resid, "resid")
+    p = st.plan
+    require().sketch_gather(st.args(
+        grad=_ptr(grad), resid=_ptr(resid), payload=_ptr(payload), payload_bytes=layout.nbytes,
+        total_k=p.total_k, total_idx=p.total_idx, total_bm_words=p.total_bm_words,
+        counts_off=layout.counts, idx_off=layout.idx, codes_off=layout.codes,
+        bitmap_off=layout.bitmap, chunks=_ptr(dp.chunks), tensors=_ptr(dp.tensors),
+        num_tensors=p.num_tensors))
 
 
 _GDT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}

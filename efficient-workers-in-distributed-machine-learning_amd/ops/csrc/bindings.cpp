@@ -145,6 +145,11 @@ PYBIND11_MODULE(_C, m) {
                F(mats) F(dense) F(items) F(stream) F(rank) F(num_mats) F(num_dense) F(num_items)
                F(bucket_len) F(p_floats) F(q_floats) F(grad) F(resid) F(p) F(q) F(slabs)
                F(tickets) F(slab_floats) F(num_tickets) F(inv_n) F(q_out))
+  EW_ARGS(SketchArgs,
+          F(rows) F(shifts) F(stream) F(num_chunks) F(sketch_rows) F(width) F(bucket_len)
+          F(sg_key) F(bucket_offset) F(grad) F(resid) F(table) F(est) F(chunks) F(tensors)
+          F(payload) F(payload_bytes) F(total_k) F(total_idx) F(total_bm_words) F(num_tensors)
+          F(counts_off) F(idx_off) F(codes_off) F(bitmap_off))
   EW_ARGS(SgdFlatArgs,
           F(param) F(mom) F(grad) F(shadow) F(stream) F(n) F(grad_dtype) F(lr) F(momentum)
           F(dampening) F(weight_decay) F(grad_scale) F(nesterov) F(first) F(lr_ptr))
@@ -206,6 +211,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("psgd_orth", &ew_psgd_orth);
   m.def("psgd_backproject", &ew_psgd_backproject);
   m.def("psgd_decode_apply", &ew_psgd_decode_apply);
+  m.def("sketch_stage", &ew_sketch_stage);
+  m.def("sketch_accum", &ew_sketch_accum);
+  m.def("sketch_estimate", &ew_sketch_estimate);
+  m.def("sketch_gather", &ew_sketch_gather);
+  m.def("sketch_sum_group", &ew_sketch_sum_group);
   m.def("sgd_flat", &ew_sgd_flat);
   m.def("adam_flat", &ew_adam_flat);
   m.def("lion_flat", &ew_lion_flat);

@@ -258,6 +258,23 @@ struct PsgdArgs {
   StepArgs step;  // reconstruct only: grad_scale 1, no key advance
 };
 
+// Count sketch of one bucket (sketch_codec.hip; compress/plan.py SketchPlan).  rows: int2 [C]
+// {start, sketched length (0: a dense tensor's chunk)}; shifts: int32 [R][C] column shifts;
+// table: fp32 [R][width].  The bucket views (grad, resid, est) hold bucket_len elements.  The
+// gather walks the index sections of a `topk` payload (chunks / tensors: the bucket's DevicePlan
+// tables) and overwrites its fp32 values section.
+struct SketchArgs {
+  uintptr_t rows, shifts, stream;
+  int num_chunks, sketch_rows;
+  long long width, bucket_len;
+  uint32_t sg_key, bucket_offset;
+  uintptr_t grad, resid, table, est;
+  // gather only
+  uintptr_t chunks, tensors, payload;
+  long long payload_bytes, total_k, total_idx, total_bm_words;
+  int num_tensors, counts_off, idx_off, codes_off, bitmap_off;
+};
+
 struct SgdFlatArgs {
   uintptr_t param, mom, grad, shadow, stream;
   long long n;
@@ -416,6 +433,11 @@ void ew_psgd_project(const PsgdArgs& a);
 void ew_psgd_orth(const PsgdArgs& a);
 void ew_psgd_backproject(const PsgdArgs& a);
 void ew_psgd_decode_apply(const PsgdArgs& a);
+void ew_sketch_stage(const SketchArgs& a);
+void ew_sketch_accum(const SketchArgs& a);
+void ew_sketch_estimate(const SketchArgs& a);
+void ew_sketch_gather(const SketchArgs& a);
+int ew_sketch_sum_group();
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

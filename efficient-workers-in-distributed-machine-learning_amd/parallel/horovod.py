@@ -174,6 +174,13 @@ class Compression:
         trainer)."""
         return Codec("powersgd", rank=rank)
 
+    @staticmethod
+    def sketch(rows: int = 3, width: float = 2.0):
+        """Count sketch (SketchedSGD): an ``rows`` x W fp32 table, ``width`` columns per selected
+        element.  Its two dependent all-reduces do not fit this wrapper's exchange:
+        ``DistributedOptimizer`` refuses it (use ``--compress sketch`` on the trainer)."""
+        return Codec("sketch", rows=rows, width=width)
+
 
 def _as_codec(compression) -> Codec:
     if isinstance(compression, Codec):
@@ -276,6 +283,10 @@ class _DistributedOptimizer:
             raise ValueError("Compression.powersgd is not supported by DistributedOptimizer: "
                              "PowerSGD exchanges two dependent all-reduces per bucket; train "
                              "with --compress powersgd on the trainer (distributed_nn.py)")
+        if codec.kind == "sketch":
+            raise ValueError("Compression.sketch is not supported by DistributedOptimizer: the "
+                             "count sketch exchanges two dependent all-reduces per bucket; train "
+                             "with --compress sketch on the trainer (distributed_nn.py)")
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
                                          # scaled sign and round-to-nearest block floating

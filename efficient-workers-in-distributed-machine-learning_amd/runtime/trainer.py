@@ -32,6 +32,7 @@ from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
 from ..parallel.sharded import ShardedPSExchange
 from ..parallel.powersgd import PowerSGDExchange
+from ..parallel.sketch import SketchExchange
 from ..parallel.twostage import TwoStageSignExchange, TwoStageVoteExchange
 from ..utils import checkpoint as ckpt
 from ..utils.metrics import MetricsLogger, accuracy, byte_summary
@@ -175,7 +176,8 @@ class Trainer:
         # (and PowerSGD, whose project launch reads the flat gradient buffer, and the two-stage
         # vote, whose push encode does)
         vote_ts = cfg.compress == "vote" and cfg.vote_exchange == "twostage"
-        ptr_grads = (self.cuda and cfg.topology == "allgather" and cfg.compress != "powersgd"
+        ptr_grads = (self.cuda and cfg.topology == "allgather"
+                     and cfg.compress not in ("powersgd", "sketch")  # the sketch's stage too
                      and not vote_ts
                      and os.environ.get("EWDML_GRAD_VIEWS") != "1")
         bf16_params = (ptr_grads and cfg.amp == "bf16" and cfg.param_dtype == "auto"
@@ -192,7 +194,7 @@ class Trainer:
         # here because the segmented step wants smaller buckets
         self.graph_plan = None
         if (cfg.hip_graph == "auto" and self.cuda and not cfg.sync_debug
-                and cfg.compress != "powersgd"  # always split graphs (below)
+                and cfg.compress not in ("powersgd", "sketch")  # always split graphs (below)
                 and cfg.topology == "allgather" and cfg.sync_every == 1 and not cfg.select_best):
             # EWDML_PLAN_AS_WORLD (test hook): plan as if the job had that many ranks, so the
             # N > 1 decision runs end to end on a one-GPU box (world of one, real communicator)
@@ -259,6 +261,14 @@ class Trainer:
                                              make_codec("powersgd", seed=cfg.seed,
                                                         rank=cfg.powersgd_rank), self.opt,
                                              clipper=self.clipper)
+        elif cfg.compress == "sketch":
+            self.exchange = SketchExchange(self.flat, self.comm,
+                                           make_codec("sketch", seed=cfg.seed,
+                                                      ratio=cfg.topk_ratio,
+                                                      dense_below=cfg.topk_dense_below,
+                                                      rows=cfg.sketch_rows,
+                                                      width=cfg.sketch_width), self.opt,
+                                           clipper=self.clipper)
         elif vote_ts:
             self.exchange = TwoStageVoteExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt,
@@ -334,7 +344,10 @@ class Trainer:
                     or isinstance(self.exchange, TwoStageVoteExchange)
                     # PowerSGD: graph A = ..., project -> eager all-reduces, orthogonalise and
                     # back-project -> graph B = reconstruct + step
-                    or isinstance(self.exchange, PowerSGDExchange))
+                    or isinstance(self.exchange, PowerSGDExchange)
+                    # the count sketch: graph A = ..., stage, table -> eager all-reduces,
+                    # estimate, select and gather -> graph B = decode + step
+                    or isinstance(self.exchange, SketchExchange))
         self.ps_graph = ps_split
         if self.graph_mode == "auto":
             # graphs wherever the step can be captured: the all-to-all exchange, local SGD's
@@ -344,7 +357,7 @@ class Trainer:
             # update); the k-of-n arrival polling stays eager
             if self.graph_plan is not None:
                 self.graph_mode = self.graph_plan["mode"]
-            elif cfg.topology == "twostage" or cfg.compress == "powersgd":
+            elif cfg.topology == "twostage" or cfg.compress in ("powersgd", "sketch"):
                 self.graph_mode = "split"
             elif isinstance(self.exchange, GradientExchange) or self.local_sgd:
                 self.graph_mode = "full"
