@@ -23,6 +23,12 @@
     rank's codes are decoded with that rank's own scaler (no scaler sharing).  Runs on the
     all-gather exchange, error feedback optional (off by default); three encode launches and one
     fused decode launch per bucket
+  * ``thresh`` -- threshold-search sparsification (RedSync, Fang et al. 2019; MSTopK, Shi et al.
+    2021; hard-threshold sparsification, Sahu et al. 2021): per 8192-element chunk everything at
+    or above a canonical bf16-level threshold chosen so that at most the chunk's share of the
+    tensor's top-k quota is sent, with the exact fp32 values; no exact selection.  Runs on the
+    all-gather exchange with plain error feedback, one encode and one fused decode launch per
+    bucket
   * ``powersgd`` -- rank-r factors of the error-compensated gradient matrices (PowerSGD, Vogels et
     al. 2019), averaged by two small fp32 all-reduces (``parallel/powersgd.py``; the ``ps_*``
     methods below)
@@ -48,7 +54,7 @@ from .plan import POWERSGD_RANKS, SKETCH_ROWS, BucketPlan, Layout, SketchPlan
 from .rng import stream_key
 
 KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx",
-         "tern", "sketch")
+         "tern", "sketch", "thresh")
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
 MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
@@ -99,7 +105,8 @@ class Codec:
                 raise ValueError(f"sketch width must be > 0, not {width!r}")
         self.rows, self.width = rows, width
         # the sign, vote and low-rank codecs have neither bits nor levels; tern's are fixed
-        if kind not in ("sign", "powersgd", "vote", "tern", "sketch") and bits not in (4, 8):
+        if kind not in ("sign", "powersgd", "vote", "tern", "sketch", "thresh") \
+                and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
             lim = 127 if bits == 8 else 7
@@ -144,6 +151,8 @@ class Codec:
             return f"tern2b(c={self.clip:g})" if self.clip > 0 else "tern2b"
         if self.kind == "sketch":
             return f"sketch-r{self.rows}"
+        if self.kind == "thresh":
+            return f"thresh-k{self.ratio:g}"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -161,7 +170,7 @@ class Codec:
             self.layouts = [None] * len(self.plans)
             return self
         lk = "qsgd" if self.kind == "qsgd" else self.kind
-        if self.kind in ("topk", "topk_qsgd"):
+        if self.kind in ("topk", "topk_qsgd", "thresh"):
             # the plans carry k; rebuild with this codec's ratio if needed
             self.plans = [p if (p.ratio == self.ratio and p.dense_below == self.dense_below)
                           else BucketPlan(p.numels, p.offsets, self.ratio, p.bucket_offset,
@@ -171,13 +180,19 @@ class Codec:
             if ops.hip_required():
                 ops.require()
             self.dplans = [ops.DevicePlan(p, self.device) for p in self.plans]
+            if self.kind == "thresh":
+                # last step's threshold of every chunk row: where the next search starts.  Chunk
+                # rows do not depend on the ratio, so it outlives set_ratio; the payload never
+                # depends on it, so it is no part of a checkpoint
+                self.thr_state = [torch.zeros(p.num_chunks, dtype=torch.int32,
+                                              device=self.device) for p in self.plans]
         self._bound[self.ratio] = (self.plans, self.layouts, self.dplans)
         return self
 
     def set_ratio(self, ratio: float):
         """Switch a bound top-k codec to another density (top-k warm-up): the per-tensor k, the
         payload layouts and the device tables change; bindings are cached per ratio."""
-        if self.kind not in ("topk", "topk_qsgd", "sketch"):
+        if self.kind not in ("topk", "topk_qsgd", "sketch", "thresh"):
             raise ValueError("only top-k codecs have a density")
         if not 0.0 < ratio <= 1.0:
             raise ValueError("top-k ratio must be in (0, 1]")
@@ -230,7 +245,7 @@ class Codec:
         (``ops.topk_encode``), so no decode launch follows."""
         if dgc is not None and (resid is None or self.kind not in ("topk", "topk_qsgd")):
             raise ValueError("momentum correction needs a top-k codec and a residual")
-        if self.kind in ("sign", "mx", "tern") and apply is not None:
+        if self.kind in ("sign", "mx", "tern", "thresh") and apply is not None:
             raise ValueError(f"the {self.kind} codec has no encode-side apply")
         if self.kind == "vote":
             raise ValueError("the vote codec sends the sign of Lion's update direction: "
@@ -251,6 +266,8 @@ class Codec:
             elif self.kind == "tern":
                 ops.tern_encode(self.dplans[b], grad, payload, lay, self.clip, key, resid,
                                 key_tensor)
+            elif self.kind == "thresh":
+                ops.thresh_encode(self.dplans[b], grad, payload, lay, resid, self.thr_state[b])
             elif self.kind == "qsgd":
                 ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
                                 resid, key_tensor)
@@ -268,6 +285,8 @@ class Codec:
             out = oracle.encode_mx(grad, plan, lay, resid)
         elif self.kind == "tern":
             out = oracle.encode_tern(grad, plan, lay, self.clip, key, resid)
+        elif self.kind == "thresh":
+            out = oracle.encode_thresh(grad, plan, lay, resid)
         elif self.kind == "qsgd":
             out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
         else:
@@ -713,6 +732,8 @@ class Codec:
             ops.mx_decode_apply(dp, recv, lay, **kw)
         elif self.kind == "tern":
             ops.tern_decode_apply(dp, recv, lay, **kw)
+        elif self.kind == "thresh":
+            ops.thresh_decode_apply(dp, recv, lay, **kw)
         else:
             fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
             fn(dp, recv, lay, self.levels, **kw)

@@ -39,6 +39,11 @@ Reference semantics being reproduced:
     -- the table of the error-compensated gradient under a per-chunk rotation hash, summed in the
     kernel's one order, the median estimate and the gather of the selected coordinates; bitwise
     the kernels'.
+  * Threshold-search sparsification (no reference counterpart; RedSync, Fang et al. 2019; MSTopK,
+    Shi et al. 2021; hard-threshold sparsification, Sahu et al. 2021): ``encode_thresh`` -- per
+    8192-element chunk everything at or above a canonical bf16-level threshold, with plain error
+    feedback; the threshold does not depend on how it is searched, so payloads and residuals are
+    bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -819,6 +824,86 @@ def _tern_decoded(pay: torch.Tensor, plan: BucketPlan, layout: Layout) -> torch.
 
 
 # ---------------------------------------------------------------------------------------------
+# Threshold-search sparsifier (RedSync, Fang et al. 2019; MSTopK, Shi et al. 2021; hard-threshold
+# sparsification, Sahu et al. 2021): per chunk, everything above a bf16-level threshold
+# ---------------------------------------------------------------------------------------------
+THRESH_LEVELS = 32768  # levels 0 .. 32767; the threshold J lies in [0, THRESH_LEVELS]
+
+
+def thresh_level(x: torch.Tensor) -> torch.Tensor:
+    """int32 level of every fp32 element: the bf16 truncation of ``|x|``, ``(bits & 0x7fffffff)
+    >> 16``, 15 bits and monotone in ``|x|`` (an inf is 0x7f80, a NaN lies above it)."""
+    return (x.contiguous().view(torch.int32) & 0x7FFFFFFF) >> 16
+
+
+def thresh_threshold(lev: torch.Tensor, cap: int) -> int:
+    """The smallest J in [0, 32768] with ``#{lev >= J} <= cap``: 0 when everything fits, else one
+    above the (cap + 1)-th largest level (all ties at that level are left out)."""
+    n = lev.numel()
+    if n <= cap:
+        return 0
+    return int(torch.sort(lev, descending=True).values[cap]) + 1
+
+
+def encode_thresh(g: torch.Tensor, plan: BucketPlan, layout: Layout,
+                  residual: torch.Tensor = None) -> torch.Tensor:
+    """Threshold sparsification of one bucket -> uint8 payload (``counts u16[C] | idx u16[S] |
+    values f32[S]``, ``plan.thresh_slots``).
+
+    ``acc = g`` (``g + residual`` under error feedback).  Per chunk row c with capacity ``cap_c``:
+    ``J_c`` = :func:`thresh_threshold` of the chunk's :func:`thresh_level`; the elements with ``lev
+    >= J_c`` are sent in increasing chunk-local index with their exact fp32 ``acc``, at most
+    ``cap_c`` of them by the choice of ``J_c`` (ties at the boundary level are all left out, so an
+    all-equal chunk longer than its capacity sends nothing); unused slots hold index 0 and +0.0.
+    ``residual`` = 0 where sent, ``acc`` elsewhere.  Nothing is special-cased: a NaN or an inf has
+    a high level and is sent."""
+    if layout.kind != "thresh":
+        raise ValueError(f"encode_thresh given a {layout.kind!r} layout")
+    acc = g.to(torch.float32)
+    if residual is not None:
+        acc = acc + residual
+    cap, slot0, S = plan.thresh_slots()
+    C = plan.num_chunks
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=acc.device)
+    counts = _section(out, layout.counts, C, torch.int16)
+    idx = _section(out, layout.idx, S, torch.int16)
+    vals = _section(out, layout.codes, S, torch.float32)
+    for c in range(C):
+        s0, n = plan.chunk_start[c], plan.chunk_len[c]
+        x = acc[s0:s0 + n]
+        lev = thresh_level(x)
+        sel = (lev >= thresh_threshold(lev, cap[c])).nonzero().flatten()
+        m = sel.numel()
+        counts[c] = m if m < 32768 else m - 65536
+        idx[slot0[c]:slot0[c] + m] = sel.to(torch.int16)
+        vals[slot0[c]:slot0[c] + m] = x[sel]
+        if residual is not None:  # the chunk's own positions only, as the kernel writes them
+            left = x.clone()
+            left[sel] = 0.0
+            residual[s0:s0 + n] = left
+    return out
+
+
+def _thresh_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout):
+    """(bucket positions, values) of one ``thresh`` payload.  A count is clamped to the chunk's
+    capacity and an index at or past the chunk's length is ignored, as the decode kernel does: a
+    corrupt row never reaches outside its chunk."""
+    cap, slot0, S = plan.thresh_slots()
+    C = plan.num_chunks
+    counts = _section(pay, layout.counts, C, torch.int16).to(torch.int64) & 0xFFFF
+    idx = _section(pay, layout.idx, S, torch.int16).to(torch.int64) & 0xFFFF
+    vals = _section(pay, layout.codes, S, torch.float32)
+    pos, out = [], []
+    for c in range(C):
+        m = min(int(counts[c]), cap[c])
+        i = idx[slot0[c]:slot0[c] + m]
+        ok = i < plan.chunk_len[c]
+        pos.append(plan.chunk_start[c] + i[ok])
+        out.append(vals[slot0[c]:slot0[c] + m][ok])
+    return torch.cat(pos), torch.cat(out)
+
+
+# ---------------------------------------------------------------------------------------------
 # decode: sum over ranks (in rank order) of the dequantised payloads, times ``scale``
 # ---------------------------------------------------------------------------------------------
 def _decoded_entries(pay: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int):
@@ -877,6 +962,9 @@ def decode_sum(recv: torch.Tensor, plan: BucketPlan, layout: Layout, levels: int
             acc += _mx_decoded(recv[r], plan, layout)
         elif layout.kind == "tern":
             acc += _tern_decoded(recv[r], plan, layout)
+        elif layout.kind == "thresh":  # an index appears once per row: the order is the ranks'
+            pos, vals = _thresh_entries(recv[r], plan, layout)
+            acc.index_add_(0, pos, vals)
         else:
             acc += _dense_decoded(recv[r], plan, layout, levels)
     return acc * torch.tensor(scale, dtype=torch.float32)

@@ -32,6 +32,10 @@ exchange is a fixed-size all-gather with no size handshake):
 ``tern``     : scales f32[T] | codes u32[D' / 16]  (TernGrad; D' as for ``qsgd``, so every tensor
                starts on a word; element i of a tensor is bits 2 (i & 15) .. 2 (i & 15) + 1 of word
                code0 / 16 + (i >> 4); 0 = 0, 1 = +1, 3 = -1, 2 is never written, pad codes are 0)
+``thresh``   : counts u16[C] | idx u16[S] | values f32[S]  (threshold-search sparsifier; chunk c owns
+               the slots [slot0_c, slot0_c + cap_c) of both sections, S = the sum of cap_c
+               (``thresh_slots``); its first counts[c] slots hold the sent entries in increasing
+               chunk-local index with their exact fp32 values, the rest index 0 and value +0.0)
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -173,6 +177,26 @@ class BucketPlan:
         rows = [[t, j] for t, nb in enumerate(self.tensor_cblocks) for j in range(nb)]
         return torch.tensor(rows, dtype=torch.int32, device=device)
 
+    def thresh_slots(self):
+        """Per chunk row of the ``thresh`` codec: (cap, slot0, S).  ``cap[c]`` entries at most are
+        sent from chunk c -- the whole chunk where its tensor goes whole (``k == numel``), else
+        the chunk's share of the tensor's k, ``max(1, ceil(k * len / numel))`` -- into the slots
+        ``[slot0[c], slot0[c] + cap[c])``; ``S`` is their sum."""
+        cap = []
+        for t, ln in zip(self.chunk_tensor, self.chunk_len):
+            k, n = self.ks[t], self.numels[t]
+            cap.append(ln if k == n else max(1, (k * ln + n - 1) // n))
+        slot0, s = [], 0
+        for c in cap:
+            slot0.append(s)
+            s += c
+        return cap, slot0, s
+
+    def thresh_table(self, device) -> torch.Tensor:
+        """int32 [C, 2]: cap, slot0 of every chunk row (csrc/thresh_codec.hip int2 slots)."""
+        cap, slot0, _ = self.thresh_slots()
+        return torch.tensor(list(zip(cap, slot0)), dtype=torch.int32, device=device)
+
     def chunk_table(self, device) -> torch.Tensor:
         """int32 [C, 4]: tensor, start (rel. bucket), len, local chunk index."""
         rows = []
@@ -248,6 +272,15 @@ class Layout:
             bits = 2
             counts = idx = codes = off
             off += plan.total_codes // 4
+        elif kind == "thresh":
+            # no scales: one count per chunk row, then the chunks' slots -- a u16 chunk-local index
+            # and an fp32 value each (`codes` is the values' byte offset)
+            bits = 32
+            S = plan.thresh_slots()[2]
+            counts = 0
+            idx = _align(2 * C)
+            codes = _align(idx + 2 * S)
+            off = codes + 4 * S
         else:
             raise ValueError(kind)
         return Layout(kind, bits, scales, counts, idx, codes, _align(off), bitmap)

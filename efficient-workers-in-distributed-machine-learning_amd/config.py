@@ -58,7 +58,8 @@ class Config:
     local_rank: Optional[int] = None
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
-    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern | sketch
+    # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern | sketch |
+    # thresh
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     # --compress sketch (count sketch, parallel/sketch.py): rows of the table, 1, 3 or 5 (None: 3;
@@ -297,6 +298,36 @@ class Config:
             raise ValueError("--tern-clip belongs to --compress tern")
         if c.pull_compress == "tern":
             raise ValueError("--pull-compress tern: the tern codec has no parameter-server form")
+        if c.compress == "thresh":
+            # the threshold-search sparsifier (compress/oracle.py encode_thresh): the all-gather
+            # exchange's encode and fused decode with that exchange's plain residual; k per tensor
+            # is --topk-ratio / --topk-dense-below's.  --qsgd-bits / --qsgd-levels and --ef-warmup
+            # none are accepted and unused (the values travel as fp32; there is no warm-up)
+            why = None
+            if c.topology != "allgather":
+                why = (f"runs the all-gather exchange, which keeps its residual: it does not run "
+                       f"with --topology {c.topology} (no ps, sharded or two-stage form is built)")
+            elif c.sync_every > 1:
+                why = ("keeps its residual in the all-gather exchange's every-step path: it does "
+                       "not run with --sync-every > 1")
+            elif c.select_best:
+                why = ("keeps its residual in the all-gather exchange's every-step path: it does "
+                       "not run with --select-best")
+            elif c.pull_compress is not None:
+                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
+            elif c.ef_mode != Config.ef_mode:
+                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
+                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
+            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
+                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
+                       f"sign-compressed momentum (--compress sign)")
+            if why is not None:
+                raise ValueError("--compress thresh " + why)
+            if c.error_feedback is None:  # what lies below the threshold is never sent without it
+                c.error_feedback = True
+        if c.pull_compress == "thresh":
+            raise ValueError("--pull-compress thresh: the thresh codec has no parameter-server "
+                             "form")
         if c.compress == "vote":
             # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
             # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
@@ -643,7 +674,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote",
-               "mx", "tern", "sketch"])
+               "mx", "tern", "sketch", "thresh"])
     a("--sketch-rows", type=int, default=None)
     a("--sketch-width", type=float, default=None)
     a("--mx-format", type=str, default=None, choices=["fp8", "fp4"])

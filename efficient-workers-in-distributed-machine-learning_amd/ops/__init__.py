@@ -689,6 +689,83 @@ def tern_decode_apply(dp: DevicePlan, recv, layout, param=None, mom=None, grad_o
         step=step, stream=_stream()))
 
 
+def _thresh_tables(dp, layout):
+    """The fields that address a ``thresh`` payload of ``dp``'s bucket.  The layout must be the
+    one the plan gives (the kernels take every slot from the plan's table); layout and device
+    table are built once per plan."""
+    if layout.kind != "thresh":
+        raise ValueError(f"thresh codec given a {layout.kind!r} layout")
+    known = dp.__dict__.get("_thresh")
+    if known is None:
+        from ..compress.plan import Layout
+        known = dp.__dict__["_thresh"] = (Layout.build("thresh", dp.plan),
+                                          dp.plan.thresh_table(dp.chunks.device),
+                                          dp.plan.thresh_slots()[2])
+    if layout != known[0]:
+        raise ValueError("thresh layout does not match the bucket plan")
+    return dict(chunks=_ptr(dp.chunks), num_chunks=dp.plan.num_chunks, slots=_ptr(known[1]),
+                total_slots=known[2], counts_off=layout.counts, idx_off=layout.idx,
+                codes_off=layout.codes)
+
+
+def _thresh_ints(t, dp, name):
+    """A per-chunk int32 device vector of the thresh encode (None: not passed)."""
+    if t is None:
+        return 0
+    _check(t, torch.int32, name, align=4)
+    if t.numel() < dp.plan.num_chunks:
+        raise ValueError(f"{name} needs one int32 per chunk row ({dp.plan.num_chunks})")
+    return t.data_ptr()
+
+
+def thresh_encode(dp, grad, payload, layout, resid=None, state=None, passes=None):
+    """Threshold sparsification of one bucket (``csrc/thresh_codec.hip``): per chunk row the
+    entries of ``acc = grad + resid`` at or above the chunk's canonical bf16-level threshold, in
+    index order with their fp32 values, and ``resid`` (error feedback) overwritten with 0 where
+    sent and ``acc`` elsewhere.  One launch, no scratch; every byte of the payload is written;
+    bitwise ``compress/oracle.py encode_thresh``.  ``state`` (int32 per chunk row): last encode's
+    thresholds, where the search starts, rewritten -- a warm start only, the payload does not
+    depend on it (None: a cold start).  ``passes`` (int32 per chunk row, probes): receives the
+    counting passes every chunk took."""
+    C = require()
+    tab = _thresh_tables(dp, layout)
+    ptrs, mask = grad_pointers(dp, grad)
+    _encode_dst(payload, layout)
+    if resid is not None:
+        _check_bucket(dp, resid, "resid")
+    C.thresh_encode(_args(
+        C.ThreshEncodeArgs, resid=_ptr(resid), payload=_ptr(payload), payload_bytes=layout.nbytes,
+        num_tensors=dp.plan.num_tensors, state=_thresh_ints(state, dp, "state"),
+        dbg_passes=_thresh_ints(passes, dp, "passes"), stream=_stream(), **tab), ptrs, mask)
+
+
+def thresh_decode_apply(dp, recv, layout, param=None, mom=None, grad_out=None, lr=0.0,
+                        momentum=0.0, dampening=0.0, weight_decay=0.0, grad_scale=1.0,
+                        nesterov=False, first=False, shadow=None, key_state=None, key_seed=0,
+                        key_rank=0, lr_tensor=None):
+    """``grad_out = grad_scale * sum over the rows of recv (rank order) of the scattered entries``
+    and / or the fused SGD step on ``param`` (``mom`` None: a step without momentum); a count
+    above the chunk's capacity is cut to it and an index past the chunk's length is dropped;
+    bitwise ``oracle.decode_sum``."""
+    C = require()
+    tab = _thresh_tables(dp, layout)
+    nranks = _recv_rows(recv, layout)
+    step = _step(dp, param, mom, grad_out, shadow, lr, momentum, dampening, weight_decay,
+                 grad_scale, nesterov, first, key_state, key_seed, key_rank, lr_tensor)
+    C.thresh_decode_apply(_args(
+        C.ThreshDecodeArgs, **_rows(recv, nranks, layout.nbytes), step=step, stream=_stream(),
+        **tab))
+
+
+def thresh_kernel_info() -> dict:
+    """Registers, scratch bytes per thread and static LDS bytes of the loaded thresh kernels (the
+    runtime's view of the compiler's resource report)."""
+    v = require().thresh_kernel_info()
+    names = ("k_thr_encode<EF>", "k_thr_encode", "k_thr_decode_apply")
+    return {n: {"vgprs": v[3 * i], "scratch_bytes": v[3 * i + 1], "lds_bytes": v[3 * i + 2]}
+            for i, n in enumerate(names)}
+
+
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
                          weight_decay=0.0, param=None, slots=None):
     """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad

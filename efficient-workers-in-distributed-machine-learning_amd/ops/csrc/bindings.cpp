@@ -141,6 +141,13 @@ PYBIND11_MODULE(_C, m) {
   EW_ARGS_STEP(TernDecodeArgs,
                F(recv) F(chunks) F(tensors) F(stream) F(stride) F(total_codes) F(nranks)
                F(num_tensors) F(num_chunks) F(scales_off) F(codes_off))
+  EW_ARGS(ThreshEncodeArgs,
+          F(resid) F(chunks) F(slots) F(payload) F(state) F(dbg_passes) F(stream)
+          F(payload_bytes) F(total_slots) F(num_tensors) F(num_chunks) F(counts_off) F(idx_off)
+          F(codes_off))
+  EW_ARGS_STEP(ThreshDecodeArgs,
+               F(recv) F(chunks) F(slots) F(stream) F(stride) F(total_slots) F(nranks)
+               F(num_chunks) F(counts_off) F(idx_off) F(codes_off))
   EW_ARGS_STEP(PsgdArgs,
                F(mats) F(dense) F(items) F(stream) F(rank) F(num_mats) F(num_dense) F(num_items)
                F(bucket_len) F(p_floats) F(q_floats) F(grad) F(resid) F(p) F(q) F(slabs)
@@ -194,6 +201,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("sign_encode", &with_grads<SignEncodeArgs, ew_sign_encode>);
   m.def("mx_encode", &with_grads<MxEncodeArgs, ew_mx_encode>);
   m.def("tern_encode", &with_grads<TernEncodeArgs, ew_tern_encode>);
+  m.def("thresh_encode", &with_grads<ThreshEncodeArgs, ew_thresh_encode>);
   m.def("lion_encode", &with_grads<LionEncodeArgs, ew_lion_encode>);
   m.def("clip_norm", &with_grads<ClipArgs, ew_clip_norm>);
   m.def("clip_scale", &with_grads<ClipArgs, ew_clip_scale>);
@@ -207,6 +215,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("sign_decode_apply", &ew_sign_decode_apply);
   m.def("mx_decode_apply", &ew_mx_decode_apply);
   m.def("tern_decode_apply", &ew_tern_decode_apply);
+  m.def("thresh_decode_apply", &ew_thresh_decode_apply);
+  m.def("thresh_kernel_info", &ew_thresh_kernel_info);
   m.def("psgd_project", &ew_psgd_project);
   m.def("psgd_orth", &ew_psgd_orth);
   m.def("psgd_backproject", &ew_psgd_backproject);

@@ -240,6 +240,27 @@ struct TernDecodeArgs {
   StepArgs step;
 };
 
+// Threshold-search sparsifier (thresh_codec.hip): counts u16[C] | idx u16[total_slots] | values
+// f32[total_slots] at counts_off / idx_off / codes_off.  slots: int2 [C] {cap, slot0} per chunk row
+// (compress/plan.py thresh_table).  state (nullable int32[C]): the thresholds of the last encode,
+// read as the search's starting points and rewritten -- the payload does not depend on it.
+// dbg_passes (nullable int32[C], probes): the counting passes every chunk took
+struct ThreshEncodeArgs {
+  GradSrc src;
+  uintptr_t resid, chunks, slots, payload, state, dbg_passes, stream;  // resid 0: no error feedback
+  long long payload_bytes, total_slots;
+  int num_tensors, num_chunks;
+  int counts_off, idx_off, codes_off;
+};
+
+struct ThreshDecodeArgs {
+  uintptr_t recv, chunks, slots, stream;
+  long long stride, total_slots;
+  int nranks, num_chunks;
+  int counts_off, idx_off, codes_off;
+  StepArgs step;
+};
+
 // PowerSGD rank-r factors of one bucket (powersgd.hip; compress/plan.py LowRankPlan).  mats /
 // dense / items are the plan's device tables; p / q the factor buffers of p_floats / q_floats
 // fp32.  The bucket views (grad, resid, param, mom, grad_out, shadow) hold bucket_len elements.
@@ -424,6 +445,9 @@ void ew_mx_encode(const MxEncodeArgs& a);
 void ew_mx_decode_apply(const MxDecodeArgs& a);
 void ew_tern_encode(const TernEncodeArgs& a);
 void ew_tern_decode_apply(const TernDecodeArgs& a);
+void ew_thresh_encode(const ThreshEncodeArgs& a);
+void ew_thresh_decode_apply(const ThreshDecodeArgs& a);
+std::vector<int> ew_thresh_kernel_info();
 void ew_sign_decode_onebit(const SignOnebitArgs& a);
 void ew_sign_decode_lamb_stage(const SignLambArgs& a);
 void ew_lamb_onebit_apply(const SignLambArgs& a);

@@ -825,14 +825,16 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
                 "mx": bits / 8.0 + 1.0 / 32.0}.get(codec_kind)
     payload = grad_numel * (per_elem or 0.0)
     # top-k payload per rank (estimate): k entries of one code byte (4-bit: half) + a 2-byte index
-    pb = payload if per_elem is not None else grad_numel * topk_ratio * (2.0 + max(bits, 4) / 8.0)
+    # (thresh: an fp32 value and a 2-byte index; planned and predicted as the top-k payload it is)
+    pb = payload if per_elem is not None else grad_numel * topk_ratio * (
+        6.0 if codec_kind == "thresh" else 2.0 + max(bits, 4) / 8.0)
     if codec_kind in ("none", "fp16", "bf16"):
         wire = 2.0 * (world - 1) / max(world, 1) * payload  # ring all-reduce
     else:
         wire = (world - 1) * pb  # all-gather
     out = {"mode": "full", "splits": 1, "bucket_bytes": int(bucket_bytes), "wire_bytes": int(wire)}
     splits = overlap_splits(payload, OVERLAP_MAX_SPLITS, OVERLAP_BYTES_PER_SPLIT)
-    prof = profile_for(model, codec_kind, dtype)
+    prof = profile_for(model, "topk" if codec_kind == "thresh" else codec_kind, dtype)
     pred = None
     if prof is not None:
         # the all-reduce moves the wire dtype's bytes (fp16 / bf16 codecs: 2 per element)

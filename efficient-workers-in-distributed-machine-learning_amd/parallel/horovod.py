@@ -168,6 +168,13 @@ class Compression:
         return Codec("tern", clip=clip)
 
     @staticmethod
+    def thresh(ratio: float = 0.01):
+        """Threshold-search sparsification: per 8192-element chunk everything at or above a
+        bf16-level threshold, at most the chunk's share of ``ratio`` of each tensor, with exact
+        fp32 values; the optimizer wrapper keeps its error feedback."""
+        return Codec("thresh", ratio=ratio)
+
+    @staticmethod
     def powersgd(rank: int = 4):
         """PowerSGD rank-r factors.  Its two dependent all-reduces do not fit this wrapper's
         exchange: ``DistributedOptimizer`` refuses it (use ``--compress powersgd`` on the
@@ -291,7 +298,7 @@ class _DistributedOptimizer:
                                          overlap=(self.bpps == 1 and op != Adasum),
                                          # scaled sign and round-to-nearest block floating
                                          # point are biased without their residual
-                                         error_feedback=codec.kind in ("sign", "mx"),
+                                         error_feedback=codec.kind in ("sign", "mx", "thresh"),
                                          predivide=gradient_predivide_factor)
         self._synced = False
         self.exchange.begin()
