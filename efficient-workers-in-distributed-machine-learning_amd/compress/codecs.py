@@ -36,6 +36,11 @@
     2019): ``rows`` x W fp32 table summed by one all-reduce, the heavy coordinates of the *sum*
     recovered from it and their exact values summed by a second one (``parallel/sketch.py``; the
     ``sk_*`` methods below); ``ratio`` / ``dense_below`` give k per tensor as for ``topk``
+  * ``intsgd`` -- IntSGD (Mishchenko et al. 2022): every rank rounds ``g * alpha`` stochastically
+    to int8 codes in ``[-q, q]``, ``q = floor(127 / N)``, with one model-wide ``alpha`` that every
+    replica derives from the norm of the last update, and the codes are summed by one int8
+    all-reduce per bucket (``parallel/intsgd.py``; the ``int_*`` methods below); error feedback
+    optional (off by default)
 
 Device tensors go through the HIP kernels (``ops``); CPU tensors through the torch oracle.  On a
 GPU box a missing extension raises instead of silently falling back.
@@ -54,7 +59,7 @@ from .plan import POWERSGD_RANKS, SKETCH_ROWS, BucketPlan, Layout, SketchPlan
 from .rng import stream_key
 
 KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx",
-         "tern", "sketch", "thresh")
+         "tern", "sketch", "thresh", "intsgd")
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
 MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
@@ -105,7 +110,7 @@ class Codec:
                 raise ValueError(f"sketch width must be > 0, not {width!r}")
         self.rows, self.width = rows, width
         # the sign, vote and low-rank codecs have neither bits nor levels; tern's are fixed
-        if kind not in ("sign", "powersgd", "vote", "tern", "sketch", "thresh") \
+        if kind not in ("sign", "powersgd", "vote", "tern", "sketch", "thresh", "intsgd") \
                 and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
         if kind in ("qsgd", "topk_qsgd"):
@@ -153,6 +158,8 @@ class Codec:
             return f"sketch-r{self.rows}"
         if self.kind == "thresh":
             return f"thresh-k{self.ratio:g}"
+        if self.kind == "intsgd":
+            return "intsgd8"
         return self.kind
 
     # -- binding ----------------------------------------------------------------------------
@@ -166,6 +173,9 @@ class Codec:
         if self.kind == "sketch":
             raise ValueError("the sketch codec is bound by its own exchange (bind_sketch; "
                              "--compress sketch on the trainer)")
+        if self.kind == "intsgd":
+            raise ValueError("the intsgd codec is bound by its own exchange (bind_intsgd; "
+                             "--compress intsgd on the trainer)")
         if self.allreduce:
             self.layouts = [None] * len(self.plans)
             return self
@@ -669,6 +679,87 @@ class Codec:
         self.decode_apply_sgd(b, recv, inv_n, param, mom, hp, first, grad_out=grad_out,
                               shadow=shadow)
 
+    # -- IntSGD (parallel/intsgd.py): encode, int8 all-reduce, decode + step, the scale rule ------
+    def bind_intsgd(self, plans, device, world: int):
+        """Bind the buckets' plans for a job of ``world`` ranks: per bucket the ``intsgd`` layout
+        (one byte per position); model-wide the scale state, the saturation counts and the
+        update-norm partials, one entry per chunk row in bucket order, then chunk order."""
+        if self.kind != "intsgd":
+            raise ValueError("the IntSGD exchange needs the intsgd codec")
+        self.device = torch.device(device)
+        self.world, self.q = int(world), oracle.intsgd_q(world)
+        self.plans = list(plans)
+        self.layouts = [Layout.build("intsgd", p) for p in self.plans]
+        self.dplans = []
+        if self.device.type == "cuda" and not _FORCE_ORACLE:
+            if ops.hip_required():
+                ops.require()
+            self.dplans = [ops.DevicePlan(p, self.device) for p in self.plans]
+        self.int_chunk0, n = [], 0
+        for p in self.plans:
+            self.int_chunk0.append(n)
+            n += p.num_chunks
+        self.int_numel = sum(p.numel for p in self.plans)
+        self.int_state = IntSGDState(self.device)
+        self.int_sat = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.int_partials = torch.zeros(n, dtype=torch.float32, device=self.device)
+        return self
+
+    def _int_rows(self, b: int, t: torch.Tensor) -> torch.Tensor:
+        c0 = self.int_chunk0[b]
+        return t[c0:c0 + self.plans[b].num_chunks]
+
+    def int_encode(self, b: int, grad: torch.Tensor, payload: torch.Tensor, step: int, rank: int,
+                   resid: torch.Tensor = None, key_tensor: torch.Tensor = None):
+        """The int8 codes of bucket ``b`` under the current scale and its rows of ``int_sat``;
+        ``resid`` (error feedback) is updated in place.  One launch on the GPU."""
+        plan, lay, key = self.plans[b], self.layouts[b], self.key(step, rank)
+        sat = self._int_rows(b, self.int_sat)
+        if self._ts_kernel(payload):
+            ops.int_encode(self.dplans[b], grad, payload, lay, self.int_state.buf, sat, self.q,
+                           key, resid, key_tensor)
+            return
+        v = self.int_state.values()
+        out, s = oracle.encode_intsgd(grad, plan, lay, v["alpha"], v["inv_a"], self.q, key, resid)
+        payload[:lay.nbytes].copy_(out)
+        sat.copy_(s)
+
+    def int_decode_apply(self, b: int, summed: torch.Tensor, param: torch.Tensor,
+                         mom: torch.Tensor, hp: dict, first: bool, shadow=None, key_state=None,
+                         rank: int = 0):
+        """The fused receive side of bucket ``b`` on its summed codes: decode with ``inv_na``,
+        the SGD step, and the bucket's rows of ``int_partials``.  One launch on the GPU."""
+        if mom is None and hp["momentum"] != 0:
+            raise ValueError("a momentum step needs the momentum buffer")
+        plan, lay = self.plans[b], self.layouts[b]
+        part = self._int_rows(b, self.int_partials)
+        if self._ts_kernel(summed):
+            ops.int_decode_apply(self.dplans[b], summed[:lay.nbytes], lay, self.int_state.buf,
+                                 part, key_state=key_state, key_seed=self.seed, key_rank=rank,
+                                 **_sgd_kw(hp, first, shadow, param, mom))
+            return
+        oracle.intsgd_apply(summed, plan, lay, self.int_state.values()["inv_na"], param, mom, hp,
+                            first, part)
+
+    def int_update_norm(self, b: int, param: torch.Tensor, prev: torch.Tensor):
+        """Bucket ``b``'s rows of ``int_partials`` from its parameters and a previous copy."""
+        part = self._int_rows(b, self.int_partials)
+        if self._ts_kernel(param):
+            ops.int_update_norm(self.dplans[b], param, prev, part)
+            return
+        part.copy_(oracle.intsgd_update_partials(param, prev, self.plans[b]))
+
+    def int_alpha(self, lr: float, lr_tensor=None):
+        """The scale rule after a step (every bucket's partials are in place).  One single-block
+        launch on the GPU."""
+        if self._ts_kernel(self.int_partials):
+            ops.int_alpha(self.int_partials, self.int_state.buf, lr, self.int_numel, self.world,
+                          lr_tensor=lr_tensor)
+            return
+        v = self.int_state.values()
+        self.int_state.load(oracle.intsgd_alpha(self.int_partials, v["r"], v["steps"], lr,
+                                                self.int_numel, self.world))
+
     def decode_apply_onebit(self, b: int, recv: torch.Tensor, inv_n: float, param: torch.Tensor,
                             exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, hp: dict,
                             shadow=None, key_state=None, rank: int = 0):
@@ -773,6 +864,37 @@ class Codec:
                              g[off:off + n], hp["lr"],
                              hp["momentum"], hp["dampening"], hp["weight_decay"],
                              hp["nesterov"], first)
+
+
+class IntSGDState:
+    """IntSGD's scale state of one model, 32 bytes in the memory of ``device`` (the layout of
+    ``ops/csrc/intsgd_codec.hip IntState``): fp64 ``{r, S of the last step}``, fp32 ``{alpha,
+    inv_a, inv_na}`` and the int32 count of steps the rule has run.  The kernels read and write
+    it in place, so a captured step follows the scale."""
+
+    FIELDS = ("r", "s_last", "alpha", "inv_a", "inv_na", "steps")
+
+    def __init__(self, device):
+        self.buf = torch.zeros(ops.INTSGD_STATE_BYTES, dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def _views(buf):
+        return (buf[:16].view(torch.float64), buf[16:28].view(torch.float32),
+                buf[28:32].view(torch.int32))
+
+    def values(self) -> dict:
+        """The state as Python numbers (synchronises on the GPU)."""
+        d, f, i = self._views(self.buf.cpu())
+        return dict(r=float(d[0]), s_last=float(d[1]), alpha=float(f[0]), inv_a=float(f[1]),
+                    inv_na=float(f[2]), steps=int(i[0]))
+
+    def load(self, v: dict):
+        host = torch.zeros(ops.INTSGD_STATE_BYTES, dtype=torch.uint8)
+        d, f, i = self._views(host)
+        d[0], d[1] = float(v["r"]), float(v.get("s_last", 0.0))
+        f[0], f[1], f[2] = float(v["alpha"]), float(v["inv_a"]), float(v["inv_na"])
+        i[0] = int(v["steps"])
+        self.buf.copy_(host)
 
 
 def _sgd_kw(hp: dict, first: bool, shadow, param, mom) -> dict:

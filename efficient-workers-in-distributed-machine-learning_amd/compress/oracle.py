@@ -44,6 +44,10 @@ Reference semantics being reproduced:
     8192-element chunk everything at or above a canonical bf16-level threshold, with plain error
     feedback; the threshold does not depend on how it is searched, so payloads and residuals are
     bitwise the kernels'.
+  * IntSGD (no reference counterpart; Mishchenko et al., ICLR 2022): ``encode_intsgd`` --
+    stochastic int8 codes of ``g * alpha`` clamped to ``floor(127 / N)``, summed by all-reduce --
+    ``intsgd_apply`` and the scale rule ``intsgd_alpha``, whose sums run in the kernels' order;
+    bitwise the kernels'.
 """
 import numpy as np
 import torch
@@ -1508,3 +1512,122 @@ def sketch_gather(payload: torch.Tensor, grad: torch.Tensor, resid: torch.Tensor
             src[off:off + n] = grad[off:off + n]
     _section(payload, layout.codes, sp.plan.total_k, torch.float32).copy_(src[pos])
     resid[pos] = 0.0  # dense tensors' residual is 0 already
+
+
+# ---------------------------------------------------------------------------------------------
+# IntSGD (Mishchenko, Wang, Kovalev, Richtarik, ICLR 2022; no reference counterpart): every rank
+# multiplies its gradient by the same scale ``alpha``, rounds stochastically to integers and the
+# int8 codes are summed by a plain all-reduce.  The CPU path and the definition of every bit of
+# ``ops/csrc/intsgd_codec.hip``.
+# ---------------------------------------------------------------------------------------------
+INTSGD_BETA = 0.9  # the moving average of the squared update norm
+INTSGD_EPS2 = 1e-16
+
+
+def intsgd_q(world: int) -> int:
+    """The largest code of one rank: ``floor(127 / world)``, so no sum of ``world`` codes leaves
+    int8's [-127, 127]."""
+    if not 1 <= int(world) <= 127:
+        raise ValueError(f"IntSGD's int8 wire holds the sum of at most 127 ranks' codes, not of "
+                         f"{world} (q = floor(127 / world) would be 0)")
+    return 127 // int(world)
+
+
+def _f32t(v: float, device) -> torch.Tensor:
+    return torch.tensor(v, dtype=torch.float32, device=device)
+
+
+def encode_intsgd(g: torch.Tensor, plan: BucketPlan, layout: Layout, alpha: float, inv_a: float,
+                  q: int, key: int, residual: torch.Tensor = None):
+    """IntSGD of one bucket -> (uint8 payload ``codes i8[L]``, int32 saturation count per chunk
+    row); ``L = plan.length``, pads 0, every byte written.
+
+    ``acc = g`` (``g + residual`` under error feedback).  Per element of a tensor: ``y = acc *
+    alpha`` (one fp32 multiply), ``f = floorf(y)``, ``u = uniform(gidx, key)`` on QSGD's streams
+    (``gidx = bucket_offset + position``), ``code = f + (u < y - f)`` -- ``y - f`` is exact in
+    fp32, so an integer ``y`` never moves and negatives round correctly -- clamped to ``[-q, q]``;
+    an inf clamps, a NaN codes 0.  An element whose ``y`` was NaN or lay outside ``[-q, q]`` counts
+    as saturated.  ``residual = acc - float(code) * inv_a``: what clipping removes is fed back.
+    ``alpha`` / ``inv_a`` are fp32 values (:func:`intsgd_alpha`), the same on every rank."""
+    if layout.kind != "intsgd":
+        raise ValueError(f"encode_intsgd given a {layout.kind!r} layout")
+    L, dev = plan.length, g.device
+    acc = g.to(torch.float32)[:L]
+    if residual is not None:
+        acc = acc + residual[:L]
+    own = _mx_mask(plan, dev)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    y = acc * _f32t(alpha, dev)
+    fl = torch.floor(y)
+    u = rng.uniform(plan.bucket_offset + torch.arange(L, dtype=torch.int64, device=dev), key)
+    code = fl + (u < (y - fl)).to(torch.float32)
+    code = torch.clamp(code, -float(q), float(q))
+    code = torch.where(torch.isnan(y) | ~own, zero, code)
+    icode = code.to(torch.int32)
+    out = torch.zeros(layout.nbytes, dtype=torch.uint8, device=dev)
+    out[:L] = icode.to(torch.int8).view(torch.uint8)
+    satm = own & ~((y >= -float(q)) & (y <= float(q)))
+    sat = torch.tensor([int(satm[s0:s0 + n].sum()) for s0, n in
+                        zip(plan.chunk_start, plan.chunk_len)], dtype=torch.int32, device=dev)
+    if residual is not None:
+        left = acc - icode.to(torch.float32) * _f32t(inv_a, dev)
+        residual[:L][own] = left[own]
+    return out, sat
+
+
+def intsgd_update_partials(p_new: torch.Tensor, p_old: torch.Tensor,
+                           plan: BucketPlan) -> torch.Tensor:
+    """fp32 ``[C]``: per chunk row the sum of ``(p_new - p_old)^2`` over the tensor's own
+    elements -- each fp32 difference taken once, squared, and summed through ``k_clip_norm``'s
+    tree (:func:`_sign_chunk_sums`; a chain of ``ops.CLIP_SUM_CHAIN`` additions at most)."""
+    pos, valid, _ = _sign_gather(plan, p_new.device)
+    d = (p_new[:plan.length] - p_old[:plan.length])[pos]
+    d = torch.where(valid, d, torch.zeros((), dtype=torch.float32, device=d.device))
+    return _sign_chunk_sums(d * d)
+
+
+def intsgd_apply(summed: torch.Tensor, plan: BucketPlan, layout: Layout, inv_na: float,
+                 param: torch.Tensor, mom: torch.Tensor, hp: dict, first: bool,
+                 partials: torch.Tensor = None) -> None:
+    """The receive side on the bucket views ``param`` / ``mom``: ``s`` = the summed byte read as
+    int8 (0x80 is -128: nothing is special-cased), ``g^ = float(s) * inv_na``, then
+    :func:`sgd_apply` per tensor.  ``partials`` (fp32 ``[C]``) receives
+    :func:`intsgd_update_partials` of the step."""
+    if layout.kind != "intsgd":
+        raise ValueError(f"intsgd_apply given a {layout.kind!r} layout")
+    L = plan.length
+    g = summed[:L].view(torch.int8).to(torch.float32) * _f32t(inv_na, summed.device)
+    old = param[:L].clone() if partials is not None else None
+    for off, n in zip(plan.offsets, plan.numels):
+        sgd_apply(param[off:off + n], None if mom is None else mom[off:off + n], g[off:off + n],
+                  hp["lr"], hp["momentum"], hp["dampening"], hp["weight_decay"], hp["nesterov"],
+                  first)
+    if partials is not None:
+        partials.copy_(intsgd_update_partials(param, old, plan))
+
+
+def intsgd_alpha(partials: torch.Tensor, r: float, steps: int, lr: float, numel: int,
+                 world: int) -> dict:
+    """The scale after an update, this project's form of the paper's Algorithm 2.  ``S`` = all
+    chunk rows' partials (every bucket's, in index order) summed sequentially in fp64; ``r = S``
+    the first time (``steps == 0``), else ``beta r + (1 - beta) S``; in fp64 ``alpha = lr
+    sqrt(numel) / sqrt(2 world r + eps2)`` with the fp32 ``lr``, rounded to fp32; ``inv_a = fl32(1
+    / alpha)`` and ``inv_na = fl32(1 / (alpha world))`` of the rounded ``alpha``, both 0 when it is
+    0.  ``r`` stays fp64.  Returns the new state ``{r, s_last, alpha, inv_a, inv_na, steps}``."""
+    import math
+
+    s = 0.0
+    for v in partials.detach().to("cpu", torch.float64).tolist():
+        s += v
+    r = INTSGD_BETA * float(r) + (1.0 - INTSGD_BETA) * s if steps else s
+    den = 2.0 * float(world) * r + INTSGD_EPS2
+    num = float(np.float32(lr)) * math.sqrt(float(numel))
+    with np.errstate(all="ignore"):
+        a64 = num / math.sqrt(den) if den >= 0.0 else float("nan")  # a NaN r: a NaN scale
+        alpha = np.float32(a64)
+        inv_a = inv_na = np.float32(0.0)
+        if alpha != 0:
+            inv_a = np.float32(np.float64(1.0) / np.float64(alpha))
+            inv_na = np.float32(np.float64(1.0) / (np.float64(alpha) * np.float64(world)))
+    return dict(r=r, s_last=s, alpha=float(alpha), inv_a=float(inv_a), inv_na=float(inv_na),
+                steps=int(steps) + 1)

@@ -32,6 +32,9 @@ exchange is a fixed-size all-gather with no size handshake):
 ``tern``     : scales f32[T] | codes u32[D' / 16]  (TernGrad; D' as for ``qsgd``, so every tensor
                starts on a word; element i of a tensor is bits 2 (i & 15) .. 2 (i & 15) + 1 of word
                code0 / 16 + (i >> 4); 0 = 0, 1 = +1, 3 = -1, 2 is never written, pad codes are 0)
+``intsgd``   : codes i8[L]  (IntSGD; L as for ``mx``; element i of the bucket is byte i, a two's
+               complement integer in [-q, q], q = floor(127 / world); pads are written as 0; the
+               all-reduce sums the bytes in place)
 ``thresh``   : counts u16[C] | idx u16[S] | values f32[S]  (threshold-search sparsifier; chunk c owns
                the slots [slot0_c, slot0_c + cap_c) of both sections, S = the sum of cap_c
                (``thresh_slots``); its first counts[c] slots hold the sent entries in increasing
@@ -267,6 +270,18 @@ class Layout:
             off = _align(L // MX_BLOCK)
             counts = idx = codes = off
             off += L * bits // 8
+        elif kind == "intsgd":
+            # one int8 code per position of the padded bucket and nothing else: the all-reduce
+            # sums the whole payload.  Addressed by the bucket's flat index and packed as for mx
+            # (a chunk row owns the positions up to the next row's start)
+            bits = 8
+            L = plan.length
+            ends = [_align(o + n, 64) for o, n in zip(plan.offsets, plan.numels)]
+            if list(plan.offsets) + [L] != [0] + ends:
+                raise ValueError("the intsgd codec needs a bucket of tensors packed at multiples "
+                                 "of 64 elements from offset 0")
+            scales = counts = idx = codes = 0
+            off = L
         elif kind == "tern":
             # one scaler per tensor, then 2-bit codes, 16 to a word (`codes` is their byte offset)
             bits = 2

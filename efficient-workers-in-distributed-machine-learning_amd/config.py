@@ -59,7 +59,7 @@ class Config:
     # ---- exchange / compression ---------------------------------------------------------------
     method: Optional[int] = None
     # none | fp16 | bf16 | qsgd | topk | topk_qsgd | sign | powersgd | vote | mx | tern | sketch |
-    # thresh
+    # thresh | intsgd
     compress: str = "topk_qsgd"
     powersgd_rank: int = 4  # --compress powersgd: rank of the factors (1, 2, 4 or 8)
     # --compress sketch (count sketch, parallel/sketch.py): rows of the table, 1, 3 or 5 (None: 3;
@@ -327,6 +327,45 @@ class Config:
                 c.error_feedback = True
         if c.pull_compress == "thresh":
             raise ValueError("--pull-compress thresh: the thresh codec has no parameter-server "
+                             "form")
+        if c.compress == "intsgd":
+            # IntSGD (parallel/intsgd.py): int8 codes under one model-wide scale, summed by one
+            # all-reduce per bucket; the scale follows the norm of the last SGD update.  Error
+            # feedback either way; --qsgd-bits / --qsgd-levels and --ef-warmup none are accepted
+            # and unused (the wire is int8 with q = floor(127 / world) levels; no warm-up)
+            why = None
+            if c.optimizer != "sgd":
+                why = (f"ties its quantisation step to the last update's norm over lr, which is a "
+                       f"gradient only under SGD (about 1 per element under Adam-like rules, so "
+                       f"the step would dwarf every gradient): it needs --optimizer sgd, not "
+                       f"{c.optimizer!r}")
+            elif c.topology != "allgather":
+                why = (f"sums its codes by all-reduce on every rank: it does not run with "
+                       f"--topology {c.topology} (no ps, sharded or two-stage form is built)")
+            elif c.sync_every > 1:
+                why = ("measures the update of every step for its scale: it does not run with "
+                       "--sync-every > 1")
+            elif c.select_best:
+                why = "sums all workers' codes: it does not run with --select-best"
+            elif c.pull_compress is not None:
+                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
+            elif c.predivide != 1.0:
+                why = ("averages the summed codes with 1 / (alpha N) in its decode: it does not "
+                       "run with --predivide other than 1")
+            elif c.ef_mode != Config.ef_mode:
+                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
+                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
+            elif c.hip_graph in ("full", "segmented"):
+                why = (f"issues its all-reduces between two graphs: --hip-graph {c.hip_graph} is "
+                       f"not supported (auto resolves to split)")
+            if why is not None:
+                raise ValueError("--compress intsgd " + why)
+            if c.error_feedback is None:  # unbiased apart from clipping; the paper runs without
+                c.error_feedback = False
+            if c.hip_graph == "auto":  # graph A -> eager int8 all-reduces -> graph B
+                c.hip_graph = "split"
+        if c.pull_compress == "intsgd":
+            raise ValueError("--pull-compress intsgd: the intsgd codec has no parameter-server "
                              "form")
         if c.compress == "vote":
             # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
@@ -674,7 +713,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--method", type=int, default=None, choices=range(1, 7))
     a("--compress", type=str, default=d.compress,
       choices=["none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote",
-               "mx", "tern", "sketch", "thresh"])
+               "mx", "tern", "sketch", "thresh", "intsgd"])
     a("--sketch-rows", type=int, default=None)
     a("--sketch-width", type=float, default=None)
     a("--mx-format", type=str, default=None, choices=["fp8", "fp4"])

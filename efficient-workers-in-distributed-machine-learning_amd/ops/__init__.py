@@ -766,6 +766,109 @@ def thresh_kernel_info() -> dict:
             for i, n in enumerate(names)}
 
 
+# IntSGD's scale state of one model (csrc/intsgd_codec.hip IntState): f64 {r, S of the last step}
+# | f32 {alpha, inv_a, inv_na} | i32 steps the rule has run
+INTSGD_STATE_BYTES = 32
+
+
+def _check_int_layout(dp, layout):
+    """The layout must be the one the plan gives (the kernels take its packing rule for
+    granted); built once per plan."""
+    if layout.kind != "intsgd":
+        raise ValueError(f"intsgd codec given a {layout.kind!r} layout")
+    known = dp.__dict__.get("_int_layout")
+    if known is None:
+        from ..compress.plan import Layout
+        known = dp.__dict__["_int_layout"] = Layout.build("intsgd", dp.plan)
+    if layout != known:
+        raise ValueError("intsgd layout does not match the bucket plan")
+
+
+def _int_state(state):
+    _check(state, torch.uint8, "state", align=8)
+    if state.numel() != INTSGD_STATE_BYTES:
+        raise ValueError(f"the IntSGD state holds {INTSGD_STATE_BYTES} bytes")
+    return _ptr(state)
+
+
+def _int_rows(dp, t, dtype, name):
+    """A per-chunk-row side buffer of one bucket: ``num_chunks`` words."""
+    _check(t, dtype, name, align=4)
+    if t.numel() != dp.plan.num_chunks:
+        raise ValueError(f"{name} holds one entry per chunk row ({dp.plan.num_chunks})")
+    return _ptr(t)
+
+
+def int_encode(dp: DevicePlan, grad, payload, layout, state, sat, q: int, key: int, resid=None,
+               key_tensor=None):
+    """IntSGD of one bucket (``csrc/intsgd_codec.hip``): one int8 code per element of ``acc = grad
+    + resid``, ``round_stochastic(acc * alpha)`` clamped to ``[-q, q]``, with ``alpha`` / ``inv_a``
+    read from ``state`` on the device and ``resid`` (error feedback) overwritten by what was not
+    sent; ``sat`` (int32 per chunk row) receives the saturated elements' count.  One launch; every
+    byte of the payload is written; bitwise ``compress/oracle.py encode_intsgd``."""
+    C = require()
+    _check_int_layout(dp, layout)
+    ptrs, mask = grad_pointers(dp, grad)
+    _encode_dst(payload, layout)
+    if resid is not None:
+        _check_bucket(dp, resid, "resid")
+    if not 1 <= int(q) <= 127:
+        raise ValueError("q must be in [1, 127]")
+    C.int_encode(_args(
+        C.IntEncodeArgs, resid=_ptr(resid), chunks=_ptr(dp.chunks), payload=_ptr(payload),
+        state=_int_state(state), sat=_int_rows(dp, sat, torch.int32, "sat"),
+        payload_bytes=layout.nbytes, length=dp.plan.length, num_tensors=dp.plan.num_tensors,
+        num_chunks=dp.plan.num_chunks, q=int(q), key=key & 0xFFFFFFFF,
+        bucket_offset=dp.plan.bucket_offset & 0xFFFFFFFF, key_ptr=_keyp(key_tensor),
+        stream=_stream()), ptrs, mask)
+
+
+def int_decode_apply(dp: DevicePlan, summed, layout, state, partials, param, mom=None, lr=0.0,
+                     momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
+                     shadow=None, key_state=None, key_seed=0, key_rank=0, lr_tensor=None):
+    """The receive side of IntSGD: ``g^ = float(int8 of summed) * inv_na`` (``inv_na`` from
+    ``state``), the fused SGD step on ``param`` (``mom`` None: a step without momentum) and, into
+    ``partials`` (fp32 per chunk row), the sums of ``(p_new - p_old)^2``; bitwise
+    ``oracle.intsgd_apply``."""
+    C = require()
+    _check_int_layout(dp, layout)
+    _check(summed, torch.uint8, "summed")
+    if summed.numel() != layout.nbytes:
+        raise ValueError(f"the summed payload holds {layout.nbytes} bytes")
+    step = _step(dp, param, mom, None, shadow, lr, momentum, dampening, weight_decay, 1.0,
+                 nesterov, first, key_state, key_seed, key_rank, lr_tensor)
+    C.int_decode_apply(_args(
+        C.IntDecodeArgs, recv=_ptr(summed), chunks=_ptr(dp.chunks), state=_int_state(state),
+        partials=_int_rows(dp, partials, torch.float32, "partials"), length=dp.plan.length,
+        num_chunks=dp.plan.num_chunks, step=step, stream=_stream()))
+
+
+def int_update_norm(dp: DevicePlan, param, prev, partials):
+    """``partials`` (fp32 per chunk row) = the sums of ``(param - prev)^2`` of one bucket, the
+    very partials :func:`int_decode_apply` writes; bitwise ``oracle.intsgd_update_partials``."""
+    _check_bucket(dp, param, "param")
+    _check_bucket(dp, prev, "prev")
+    C = require()
+    C.int_update_norm(_args(
+        C.IntNormArgs, param=_ptr(param), prev=_ptr(prev), chunks=_ptr(dp.chunks),
+        partials=_int_rows(dp, partials, torch.float32, "partials"), length=dp.plan.length,
+        num_chunks=dp.plan.num_chunks, stream=_stream()))
+
+
+def int_alpha(partials, state, lr: float, numel: int, world: int, lr_tensor=None):
+    """One single-block launch: the model's ``partials`` summed in fp64 in index order, the
+    moving average ``r`` and ``alpha``, ``inv_a``, ``inv_na`` into ``state``; ``lr_tensor`` (device
+    fp32) overrides ``lr``.  Bitwise ``oracle.intsgd_alpha``."""
+    _check(partials, torch.float32, "partials", align=4)
+    if not 1 <= int(world) <= 127 or int(numel) < 1:
+        raise ValueError("world must be in [1, 127] and numel >= 1")
+    C = require()
+    C.int_alpha(_args(
+        C.IntAlphaArgs, partials=_ptr(partials), state=_int_state(state), lr_ptr=_lrp(lr_tensor),
+        total_chunks=partials.numel(), world=int(world), numel=float(numel), lr=float(lr),
+        stream=_stream()))
+
+
 def sign_encode_momentum(dp, grad, payload, layout, resid, exp_avg, beta1,
                          weight_decay=0.0, param=None, slots=None):
     """1-bit Adam's momentum encode: :func:`sign_encode` of ``exp_avg * beta1 + (1 - beta1) * (grad

@@ -157,6 +157,14 @@ PYBIND11_MODULE(_C, m) {
           F(sg_key) F(bucket_offset) F(grad) F(resid) F(table) F(est) F(chunks) F(tensors)
           F(payload) F(payload_bytes) F(total_k) F(total_idx) F(total_bm_words) F(num_tensors)
           F(counts_off) F(idx_off) F(codes_off) F(bitmap_off))
+  EW_ARGS(IntEncodeArgs,
+          F(resid) F(chunks) F(payload) F(state) F(sat) F(stream) F(payload_bytes) F(length)
+          F(num_tensors) F(num_chunks) F(q) F(key) F(bucket_offset) F(key_ptr))
+  EW_ARGS_STEP(IntDecodeArgs,
+               F(recv) F(chunks) F(state) F(partials) F(stream) F(length) F(num_chunks))
+  EW_ARGS(IntNormArgs, F(param) F(prev) F(chunks) F(partials) F(stream) F(length) F(num_chunks))
+  EW_ARGS(IntAlphaArgs,
+          F(partials) F(state) F(lr_ptr) F(stream) F(total_chunks) F(world) F(numel) F(lr))
   EW_ARGS(SgdFlatArgs,
           F(param) F(mom) F(grad) F(shadow) F(stream) F(n) F(grad_dtype) F(lr) F(momentum)
           F(dampening) F(weight_decay) F(grad_scale) F(nesterov) F(first) F(lr_ptr))
@@ -203,6 +211,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("tern_encode", &with_grads<TernEncodeArgs, ew_tern_encode>);
   m.def("thresh_encode", &with_grads<ThreshEncodeArgs, ew_thresh_encode>);
   m.def("lion_encode", &with_grads<LionEncodeArgs, ew_lion_encode>);
+  m.def("int_encode", &with_grads<IntEncodeArgs, ew_int_encode>);
   m.def("clip_norm", &with_grads<ClipArgs, ew_clip_norm>);
   m.def("clip_scale", &with_grads<ClipArgs, ew_clip_scale>);
 
@@ -226,6 +235,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("sketch_estimate", &ew_sketch_estimate);
   m.def("sketch_gather", &ew_sketch_gather);
   m.def("sketch_sum_group", &ew_sketch_sum_group);
+  m.def("int_decode_apply", &ew_int_decode_apply);
+  m.def("int_update_norm", &ew_int_update_norm);
+  m.def("int_alpha", &ew_int_alpha);
   m.def("sgd_flat", &ew_sgd_flat);
   m.def("adam_flat", &ew_adam_flat);
   m.def("lion_flat", &ew_lion_flat);

@@ -296,6 +296,46 @@ struct SketchArgs {
   int num_tensors, counts_off, idx_off, codes_off, bitmap_off;
 };
 
+// IntSGD (intsgd_codec.hip): payload codes i8[length], element i of the padded bucket is byte i.
+// state: the model's scale state, 32 bytes = f64 {r, S of the last step} | f32 {alpha, inv_a,
+// inv_na} | i32 steps the rule has run.  sat: u32 per chunk row of this bucket, rewritten by
+// every encode.  q = floor(127 / world): the clamp of a code
+struct IntEncodeArgs {
+  GradSrc src;
+  uintptr_t resid, chunks, payload, state, sat, stream;  // resid 0: no error feedback
+  long long payload_bytes, length;
+  int num_tensors, num_chunks, q;
+  uint32_t key, bucket_offset;
+  uintptr_t key_ptr;  // nullable device uint32 key (overrides key)
+};
+
+// The receive side: recv = the summed codes of one bucket (one row).  partials: fp32 per chunk row
+// of this bucket, the sum of (p_new - p_old)^2 in k_clip_norm's order.  step: always applies
+// (grad_scale must be 1, no grad_out)
+struct IntDecodeArgs {
+  uintptr_t recv, chunks, state, partials, stream;
+  long long length;
+  int num_chunks;
+  StepArgs step;
+};
+
+// The same partials from the bucket's parameters and a previous copy of them
+struct IntNormArgs {
+  uintptr_t param, prev, chunks, partials, stream;
+  long long length;
+  int num_chunks;
+};
+
+// One block: S = the partials summed in fp64 in index order, r = steps ? beta r + (1 - beta) S : S,
+// alpha = fl32(lr sqrt(numel) / sqrt(2 world r + eps2)), inv_a = fl32(1 / alpha), inv_na = fl32(1 /
+// (alpha world)) (both 0 when alpha == 0); lr_ptr (nullable device fp32) overrides lr
+struct IntAlphaArgs {
+  uintptr_t partials, state, lr_ptr, stream;
+  int total_chunks, world;
+  double numel;
+  float lr;
+};
+
 struct SgdFlatArgs {
   uintptr_t param, mom, grad, shadow, stream;
   long long n;
@@ -462,6 +502,10 @@ void ew_sketch_accum(const SketchArgs& a);
 void ew_sketch_estimate(const SketchArgs& a);
 void ew_sketch_gather(const SketchArgs& a);
 int ew_sketch_sum_group();
+void ew_int_encode(const IntEncodeArgs& a);
+void ew_int_decode_apply(const IntDecodeArgs& a);
+void ew_int_update_norm(const IntNormArgs& a);
+void ew_int_alpha(const IntAlphaArgs& a);
 
 void ew_sgd_flat(const SgdFlatArgs& a);
 void ew_adam_flat(const AdamFlatArgs& a);

@@ -52,6 +52,32 @@ def clip_final_grads(clipper, device):
     clipper.run()
 
 
+def upload_device_key(ex, s: int):
+    """Upload the RNG state {step, key} of stream step ``s`` into ``ex.key_state`` (``ex``: an
+    exchange with ``codec``, ``comm``, ``key_state`` and the ring slots ``_key_ring`` /
+    ``_key_slot``)."""
+    key = ex.codec.key(s, ex.comm.rank)
+    vals = [((v + (1 << 31)) % (1 << 32)) - (1 << 31) for v in (s & 0xFFFFFFFF, key)]
+    if ex.key_state.device.type != "cuda":
+        ex.key_state.copy_(torch.tensor(vals, dtype=torch.int32))
+        return
+    # asynchronous upload from a ring of pinned slots: a pageable host->device copy would
+    # block the host until the previous graph replay drained, leaving the GPU idle while the
+    # next replay is launched.  A slot is reused only after its previous copy completed.
+    if ex._key_ring is None:
+        ex._key_ring = [(torch.zeros(2, dtype=torch.int32).pin_memory(), None)
+                        for _ in range(8)]
+    host, ev = ex._key_ring[ex._key_slot]
+    if ev is not None:
+        ev.synchronize()
+    host[0], host[1] = vals[0], vals[1]
+    ex.key_state.copy_(host, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    ex._key_ring[ex._key_slot] = (host, ev)
+    ex._key_slot = (ex._key_slot + 1) % len(ex._key_ring)
+
+
 class GradientExchange:
     """All-to-all exchange: all-reduce for dense codecs, all-gather of payloads otherwise."""
 
@@ -445,27 +471,7 @@ class GradientExchange:
     def set_device_key(self, step: int = None):
         """Upload this step's RNG state {step, key} (graph replay reads the key from device
         memory; with ``dev_key_advance`` the decode kernel moves it on to the next step)."""
-        s = (self.step_idx if step is None else step) + self.seed_offset
-        key = self.codec.key(s, self.comm.rank)
-        vals = [((v + (1 << 31)) % (1 << 32)) - (1 << 31) for v in (s & 0xFFFFFFFF, key)]
-        if self.key_state.device.type != "cuda":
-            self.key_state.copy_(torch.tensor(vals, dtype=torch.int32))
-            return
-        # asynchronous upload from a ring of pinned slots: a pageable host->device copy would
-        # block the host until the previous graph replay drained, leaving the GPU idle while the
-        # next replay is launched.  A slot is reused only after its previous copy completed.
-        if self._key_ring is None:
-            self._key_ring = [(torch.zeros(2, dtype=torch.int32).pin_memory(), None)
-                              for _ in range(8)]
-        host, ev = self._key_ring[self._key_slot]
-        if ev is not None:
-            ev.synchronize()
-        host[0], host[1] = vals[0], vals[1]
-        self.key_state.copy_(host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._key_ring[self._key_slot] = (host, ev)
-        self._key_slot = (self._key_slot + 1) % len(self._key_ring)
+        upload_device_key(self, (self.step_idx if step is None else step) + self.seed_offset)
 
     def finish(self, apply: bool = True):
         """Complete every bucket's exchange and (by default) apply the optimizer step."""
@@ -819,6 +825,18 @@ def plan_graph_mode(world: int, comm_kind: str, codec_kind: str, grad_numel: int
         # tensors' shapes (LowRankPlan) and are reported by the exchange itself
         return {"mode": "split", "splits": 1, "bucket_bytes": int(bucket_bytes), "wire_bytes": 0,
                 "reason": "PowerSGD: collectives between two graphs"}
+    if codec_kind == "intsgd":
+        # parallel/intsgd.py: one int8 ring all-reduce per bucket between two graphs.  No N = 1
+        # profile of its own: the step is predicted as 8-bit qsgd's (the same bytes per element
+        # through one encode and one fused decode)
+        q = plan_graph_mode(world, comm_kind, "qsgd", grad_numel, 8, overlap, bucket_bytes, model,
+                            topk_ratio, dtype, clip)
+        out = {"mode": "split", "splits": 1, "bucket_bytes": int(bucket_bytes),
+               "wire_bytes": int(2.0 * (world - 1) / max(world, 1) * grad_numel),
+               "reason": "IntSGD: int8 all-reduces between two graphs (predicted as qsgd)"}
+        if "predicted_ms" in q:
+            out["predicted_ms"] = q["predicted_ms"]
+        return out
     # mx: one code of `bits` bits per element and one scale byte per 32 (33/32 and 17/32 bytes)
     per_elem ={"none": 4.0, "fp16": 2.0, "bf16": 2.0, "qsgd": bits / 8.0,
                 "sign": 1.0 / 8.0, "vote": 1.0 / 8.0, "tern": 0.25,

@@ -188,6 +188,13 @@ class Compression:
         ``DistributedOptimizer`` refuses it (use ``--compress sketch`` on the trainer)."""
         return Codec("sketch", rows=rows, width=width)
 
+    @staticmethod
+    def intsgd():
+        """IntSGD: int8 codes under one model-wide scale, summed by all-reduce.  The scale
+        follows the norm of the last model update, and this wrapper's wrapped optimizer owns the
+        step: ``DistributedOptimizer`` refuses it (use ``--compress intsgd`` on the trainer)."""
+        return Codec("intsgd")
+
 
 def _as_codec(compression) -> Codec:
     if isinstance(compression, Codec):
@@ -294,6 +301,11 @@ class _DistributedOptimizer:
             raise ValueError("Compression.sketch is not supported by DistributedOptimizer: the "
                              "count sketch exchanges two dependent all-reduces per bucket; train "
                              "with --compress sketch on the trainer (distributed_nn.py)")
+        if codec.kind == "intsgd":
+            raise ValueError("Compression.intsgd is not supported by DistributedOptimizer: the "
+                             "wrapped optimizer owns the step, so the update norm IntSGD's scale "
+                             "follows is not visible; train with --compress intsgd on the "
+                             "trainer (distributed_nn.py)")
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
                                          # scaled sign and round-to-nearest block floating

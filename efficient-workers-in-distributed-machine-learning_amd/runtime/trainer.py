@@ -32,6 +32,7 @@ from ..parallel.local_sgd import LocalSGDExchange
 from ..parallel.ps import PSExchange
 from ..parallel.sharded import ShardedPSExchange
 from ..parallel.powersgd import PowerSGDExchange
+from ..parallel.intsgd import IntSGDExchange
 from ..parallel.sketch import SketchExchange
 from ..parallel.twostage import TwoStageSignExchange, TwoStageVoteExchange
 from ..utils import checkpoint as ckpt
@@ -177,7 +178,8 @@ class Trainer:
         # vote, whose push encode does)
         vote_ts = cfg.compress == "vote" and cfg.vote_exchange == "twostage"
         ptr_grads = (self.cuda and cfg.topology == "allgather"
-                     and cfg.compress not in ("powersgd", "sketch")  # the sketch's stage too
+                     # the sketch's stage and IntSGD's encode and dense first step too
+                     and cfg.compress not in ("powersgd", "sketch", "intsgd")
                      and not vote_ts
                      and os.environ.get("EWDML_GRAD_VIEWS") != "1")
         bf16_params = (ptr_grads and cfg.amp == "bf16" and cfg.param_dtype == "auto"
@@ -194,7 +196,8 @@ class Trainer:
         # here because the segmented step wants smaller buckets
         self.graph_plan = None
         if (cfg.hip_graph == "auto" and self.cuda and not cfg.sync_debug
-                and cfg.compress not in ("powersgd", "sketch")  # always split graphs (below)
+                # always split graphs (below)
+                and cfg.compress not in ("powersgd", "sketch", "intsgd")
                 and cfg.topology == "allgather" and cfg.sync_every == 1 and not cfg.select_best):
             # EWDML_PLAN_AS_WORLD (test hook): plan as if the job had that many ranks, so the
             # N > 1 decision runs end to end on a one-GPU box (world of one, real communicator)
@@ -209,6 +212,16 @@ class Trainer:
                 {"bf16": "bf16", "fp16": "fp16"}.get(cfg.amp, "fp32"),
                 clip=cfg.clip_grad_norm is not None)
             bucket_bytes = self.graph_plan["bucket_bytes"]
+        elif cfg.compress == "intsgd" and cfg.hip_graph == "split" and self.cuda:
+            # always split graphs and the buckets as given; the plan carries the step model's
+            # prediction, which is 8-bit qsgd's
+            self.graph_plan = plan_graph_mode(
+                self.world, self.comm.kind, "intsgd",
+                sum(p.numel() for p in model.parameters() if p.requires_grad),
+                overlap=cfg.overlap, bucket_bytes=bucket_bytes, model=cfg.network,
+                dtype="fp32" if self.amp_kept_fp32 else
+                {"bf16": "bf16", "fp16": "fp16"}.get(cfg.amp, "fp32"),
+                clip=cfg.clip_grad_norm is not None)
         self.flat = FlatModel(model, bucket_bytes=bucket_bytes,
                               attach_grads=not ptr_grads, bf16_params=bf16_params)
         sync_params(self.flat, self.comm)
@@ -269,6 +282,11 @@ class Trainer:
                                                       rows=cfg.sketch_rows,
                                                       width=cfg.sketch_width), self.opt,
                                            clipper=self.clipper)
+        elif cfg.compress == "intsgd":
+            self.exchange = IntSGDExchange(self.flat, self.comm,
+                                           make_codec("intsgd", seed=cfg.seed), self.opt,
+                                           clipper=self.clipper,
+                                           error_feedback=cfg.error_feedback)
         elif vote_ts:
             self.exchange = TwoStageVoteExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt,
@@ -347,7 +365,10 @@ class Trainer:
                     or isinstance(self.exchange, PowerSGDExchange)
                     # the count sketch: graph A = ..., stage, table -> eager all-reduces,
                     # estimate, select and gather -> graph B = decode + step
-                    or isinstance(self.exchange, SketchExchange))
+                    or isinstance(self.exchange, SketchExchange)
+                    # IntSGD: graph A = ..., encode -> eager int8 all-reduces -> graph B = decode
+                    # + step and the scale launch
+                    or isinstance(self.exchange, IntSGDExchange))
         self.ps_graph = ps_split
         if self.graph_mode == "auto":
             # graphs wherever the step can be captured: the all-to-all exchange, local SGD's
@@ -357,7 +378,7 @@ class Trainer:
             # update); the k-of-n arrival polling stays eager
             if self.graph_plan is not None:
                 self.graph_mode = self.graph_plan["mode"]
-            elif cfg.topology == "twostage" or cfg.compress in ("powersgd", "sketch"):
+            elif cfg.topology == "twostage" or cfg.compress in ("powersgd", "sketch", "intsgd"):
                 self.graph_mode = "split"
             elif isinstance(self.exchange, GradientExchange) or self.local_sgd:
                 self.graph_mode = "full"
@@ -767,6 +788,8 @@ class Trainer:
         if not self.model.training:  # recursive; ~0.2 ms of host time per step otherwise
             self.model.train()
         graphed = self.graph_mode != "off" and self.step >= self.cfg.graph_warmup
+        if graphed and getattr(self.exchange, "dense_step", False):
+            graphed = False  # IntSGD without a scale yet (a resume without intsgd_state): eager
         if graphed and self.local_sgd and self.exchange.is_sync and not self._sync_graphable():
             graphed = False  # dense re-sync / best-worker choice (host decisions): eager
         if x is None and graphed and self.loader.fused:
@@ -1074,6 +1097,8 @@ class Trainer:
             extra["lion_momentum"] = allr
         if isinstance(inner, PowerSGDExchange):
             extra["powersgd_q"] = inner.q  # the warm start, the same on every rank: rank 0's
+        if isinstance(inner, IntSGDExchange) and inner.state() is not None:
+            extra["intsgd_state"] = inner.state()  # the scale, the same on every rank: rank 0's
         if self.local_sgd:
             # between syncs every replica (and its momentum) has drifted on its own: keep every
             # rank's row, the common anchor of the model-delta exchange and the sync count (the
@@ -1144,6 +1169,8 @@ class Trainer:
                 self.log.info("resume: world size changed, lion_momentum reset")
         if isinstance(inner, PowerSGDExchange) and st["extra"].get("powersgd_q") is not None:
             inner.q.copy_(st["extra"]["powersgd_q"].to(self.device))
+        if isinstance(inner, IntSGDExchange):
+            inner.load_state(st["extra"].get("intsgd_state"))
         if self.local_sgd:
             ex, ext = self.exchange, st["extra"]
             rows = [(ext.get("local_params"), self.flat.data),
