@@ -354,6 +354,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("wino_f32_bwd_data", &ew_wino_f32_bwd_data);
   m.def("wino_f32_wgrad", &ew_wino_f32_wgrad);
   m.def("wino_f32_wgrad_out", &ew_wino_f32_wgrad_out);
+  m.def("wino_f32_output", &ew_wino_f32_output);
+  m.def("wg_set_out_pipe", &ew_wg_set_out_pipe);
   m.def("wino_f32_fwd_bn", &ew_wino_f32_fwd_bn);
   m.def("wino_f32_bwd_data_bn", &ew_wino_f32_bwd_data_bn);
   m.def("sm_f32_ws_floats", &ew_sm_f32_ws_floats);

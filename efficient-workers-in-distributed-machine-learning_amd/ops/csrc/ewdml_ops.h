@@ -712,6 +712,17 @@ int ew_wino_f32_wgrad(uintptr_t dy, uintptr_t V, uintptr_t dw, uintptr_t D, int 
                       int W, int C, int Nc, int m, int defer_out, uintptr_t stream);
 void ew_wino_f32_wgrad_out(uintptr_t src, int split, uintptr_t dw, int Nc, int C, int m,
                            uintptr_t stream);
+// the output transform y = A^T Mo A alone, with the forward's (bn_h 0) or the backward-data
+// epilogue (tests, probes; any tile count); tpb > 0: that many tiles per block
+int ew_wino_f32_output(uintptr_t Mo, uintptr_t y, long long N, int H, int W, int Nc, int m,
+                       uintptr_t bn_h, uintptr_t bn_res, uintptr_t bn_code, uintptr_t bn_stats,
+                       int bn_relu, uintptr_t bnpart, long long bnpart_floats, uintptr_t addend,
+                       int tpb, uintptr_t stream);
+// which kernel runs the output transforms (EWDML_WG_OUT_PIPE at load): 0 the general one, 1 the
+// pipelined, mode-specialised one (an epilogue without an instance raises), 2 (default) the
+// pipelined one for the instances measured faster in a step, the general one otherwise;
+// on < 0: query; returns the previous
+int ew_wg_set_out_pipe(int on);
 
 // ---- fp32 3x3 convolutions over 2x2 maps as dense position GEMMs (smallmap_f32.hip): slab
 // workspace floats and ticket ints (zeroed once; the kernels leave them zero) for N, C, Nc

@@ -446,6 +446,192 @@ __global__ __launch_bounds__(EW_BLOCK) void k_wg_output(const float* __restrict_
   }
 }
 
+// What k_wg_output_p accumulates into bnpart (STAT): nothing; the output's own sum and sum of
+// squares (forward); CfBnBwd's backward sums with h (and res) at the output's own row; or at the
+// row the 2x2 pool's window code routed each channel from.
+enum { WO_NONE = 0, WO_FWD = 1, WO_BWD = 2, WO_BWDC = 3 };
+
+// k_wg_output with the epilogue's mode fixed at compile time and the tile loop software-pipelined:
+// the a^2 Mo loads of the thread's next tile are issued before the transform and stores of the
+// current one (two register sets, used alternately: no copy waits for the loads), and a tile's
+// epilogue operands (addend, pool code words, the h / res rows they can select) are all issued
+// ahead of its arithmetic instead of output by output behind run-time branches.  The old loop
+// was a chain of dependent memory round trips: one per tile plus, in the backward modes, one per
+// output.  Same grid, thread-to-(tile, channel) mapping, tile order, accumulation order (i outer,
+// j inner) and red[] reduction as k_wg_output, and the same expressions: y and bnpart are bitwise
+// the old kernel's (tests/kernels/test_wg_output_pipelined.py).
+// A prefetch never leaves Mo: the next tile is loaded only where it is below t1 (<= tiles).
+// That branch is wave-uniform where Nc / VW >= 64; at Nc = 64 two row groups share a wave and
+// the lanes without a next tile are masked off.
+// M = 4 loads the epilogue operands one output row at a time: beside two sets of 36 Mo vectors a
+// whole tile's would spill.
+template <int M, int VW, int STAT, bool RES, bool RELU, bool ADD>
+__global__ __launch_bounds__(EW_BLOCK) void k_wg_output_p(const float* __restrict__ Mo,
+                                                          float* __restrict__ y, int H, int W,
+                                                          int Nc, long long tiles, int tpb,
+                                                          float* __restrict__ bnpart, CfBnBwd bb,
+                                                          const float* __restrict__ addend) {
+  typedef float T __attribute__((ext_vector_type(VW)));
+  constexpr int A = Wg<M>::A;
+  constexpr bool BWD = STAT == WO_BWD || STAT == WO_BWDC;
+  constexpr int NQ = STAT == WO_BWDC ? 4 : 1;               // candidate rows per output
+  constexpr int ER = M == 4 ? 1 : M;                        // output rows per operand group
+  static_assert(BWD || (!RES && !RELU), "res / relu belong to the backward sums");
+  __shared__ __attribute__((aligned(16))) float red[2][EW_BLOCK * 4];
+  const int tpr = Nc / VW, rpi = EW_BLOCK / tpr;
+  const int t = threadIdx.x, rg = t / tpr, c0 = (t - rg * tpr) * VW;
+  const long long t0 = (long long)blockIdx.x * tpb;
+  const long long t1 = t0 + tpb < tiles ? t0 + tpb : tiles;
+  const int tw = W / M, tpi = (H / M) * tw;
+  const long long xs = tiles * Nc;
+  const uint32_t HoWo = (uint32_t)bb.Ho * bb.Wo;
+  float s1[VW], s2[VW], mean[VW], sc[VW], sh[VW];
+#pragma unroll
+  for (int j = 0; j < VW; ++j) s1[j] = s2[j] = 0.0f;
+  if constexpr (BWD) {
+#pragma unroll
+    for (int j = 0; j < VW; ++j) {
+      mean[j] = bb.stats[c0 + j];
+      sc[j] = bb.stats[2 * Nc + c0 + j];
+      sh[j] = bb.stats[3 * Nc + c0 + j];
+    }
+  }
+  // mo[b][a] = Mo[a * A + b][tile][c0..]
+  // (uniform position base + one 32-bit byte offset per thread: a^2 * tiles * Nc < 2^31 floats)
+  auto load_mo = [&](T (&mo)[A][A], long long tile) __attribute__((always_inline)) {
+    const uint32_t bo = ((uint32_t)tile * (uint32_t)Nc + (uint32_t)c0) * 4u;
+#pragma unroll
+    for (int b = 0; b < A; ++b)
+#pragma unroll
+      for (int a = 0; a < A; ++a)
+        mo[b][a] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(Mo + (a * A + b) * xs) + bo);
+  };
+  // one tile: prefetch the next into nxt, transform and store cur; false after the last
+  auto step = [&](long long tl, const T (&cur)[A][A], T (&nxt)[A][A]) __attribute__((always_inline)) {
+    const bool more = tl + rpi < t1;
+    if (more) load_mo(nxt, tl + rpi);
+    // tiles < 2^31: the old kernel's 64-bit quotient, by a 32-bit division
+    const int n = (int)((uint32_t)tl / (uint32_t)tpi), rem = (int)tl - n * tpi;
+    const int ty = rem / tw, tx = rem - ty * tw;
+    T u[M][A];  // A^T Mo, one column b at a time
+#pragma unroll
+    for (int i0 = 0; i0 < M; i0 += ER) {
+      // this group's epilogue operands, all in flight before anything below waits for one
+      T ad[ER][M], hq[ER][M][NQ], rq[ER][M][NQ];
+      uint32_t kw[ER][M];
+#pragma unroll
+      for (int ii = 0; ii < ER; ++ii)
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          const long long r = ((long long)n * H + M * ty + i0 + ii) * W + M * tx + j;
+          const long long off = r * Nc + c0;
+          if constexpr (ADD) ad[ii][j] = *reinterpret_cast<const T*>(addend + off);
+          if constexpr (STAT == WO_BWDC) {
+            const uint32_t p = (uint32_t)r, nn = p / HoWo, rm = p - nn * HoWo;
+            const uint32_t ho = rm / (uint32_t)bb.Wo, wo = rm - ho * (uint32_t)bb.Wo;
+            const uint32_t base = 4 * nn * HoWo + 4 * ho * (uint32_t)bb.Wo + 2 * wo;
+            if constexpr (VW == 4)
+              kw[ii][j] = *reinterpret_cast<const uint32_t*>(bb.code + off);
+            else
+              kw[ii][j] = *reinterpret_cast<const uint16_t*>(bb.code + off);
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) {
+              const size_t hr = base + (qq >> 1) * (2 * (uint32_t)bb.Wo) + (qq & 1);
+              hq[ii][j][qq] = *reinterpret_cast<const T*>(bb.h + hr * Nc + c0);
+              if constexpr (RES) rq[ii][j][qq] = *reinterpret_cast<const T*>(bb.res + hr * Nc + c0);
+            }
+          } else if constexpr (STAT == WO_BWD) {
+            hq[ii][j][0] = *reinterpret_cast<const T*>(bb.h + (size_t)r * Nc + c0);
+            if constexpr (RES) rq[ii][j][0] = *reinterpret_cast<const T*>(bb.res + (size_t)r * Nc + c0);
+          }
+        }
+      if (i0 == 0) {
+#pragma unroll
+        for (int b = 0; b < A; ++b)
+#pragma unroll
+          for (int i = 0; i < M; ++i)
+            u[i][b] = wg_dot<A>([&](int a) { return wg_at<M>(i, a); }, cur[b]);
+      }
+#pragma unroll
+      for (int ii = 0; ii < ER; ++ii)
+#pragma unroll
+        for (int j = 0; j < M; ++j) {  // (A^T Mo) A
+          const int i = i0 + ii;
+          T v = wg_dot<A>([&](int b) { return wg_at<M>(j, b); }, u[i]);
+          const long long r = ((long long)n * H + M * ty + i) * W + M * tx + j;
+          const long long off = r * Nc + c0;
+          if constexpr (ADD) v += ad[ii][j];
+          *reinterpret_cast<T*>(y + off) = v;
+          if constexpr (STAT == WO_FWD) {
+#pragma unroll
+            for (int q = 0; q < VW; ++q) {
+              s1[q] += v[q];
+              s2[q] += v[q] * v[q];
+            }
+          }
+          if constexpr (BWD) {
+            T xh, rr{};
+            if constexpr (STAT == WO_BWDC) {
+#pragma unroll
+              for (int q = 0; q < VW; ++q) {
+                const uint32_t k = (kw[ii][j] >> (8 * q)) & 3u;
+                const T(&hh)[4] = hq[ii][j];
+                xh[q] = k == 0 ? hh[0][q] : k == 1 ? hh[1][q] : k == 2 ? hh[2][q] : hh[3][q];
+                if constexpr (RES) {
+                  const T(&rs)[4] = rq[ii][j];
+                  rr[q] = k == 0 ? rs[0][q] : k == 1 ? rs[1][q] : k == 2 ? rs[2][q] : rs[3][q];
+                }
+              }
+            } else {
+              xh = hq[ii][j][0];
+              if constexpr (RES) rr = rq[ii][j][0];
+            }
+#pragma unroll
+            for (int q = 0; q < VW; ++q) {
+              float z = xh[q] * sc[q] + sh[q];
+              if constexpr (RES) z = z + rr[q];
+              const float dz = (!RELU || !(z <= 0.0f)) ? v[q] : 0.0f;
+              s1[q] += dz;
+              s2[q] += dz * (xh[q] - mean[q]);
+            }
+          }
+        }
+    }
+    return more;
+  };
+  long long tl = t0 + rg;
+  if (tl < t1) {
+    T ra[A][A], rb[A][A];
+    load_mo(ra, tl);
+    for (;; tl += 2 * rpi) {
+      if (!step(tl, ra, rb)) break;
+      if (!step(tl + rpi, rb, ra)) break;
+    }
+  }
+  if constexpr (STAT == WO_NONE) return;
+  {
+    T a, b;
+#pragma unroll
+    for (int q = 0; q < VW; ++q) {
+      a[q] = s1[q];
+      b[q] = s2[q];
+    }
+    *reinterpret_cast<T*>(&red[0][rg * Nc + c0]) = a;
+    *reinterpret_cast<T*>(&red[1][rg * Nc + c0]) = b;
+  }
+  __syncthreads();
+  const int nb = gridDim.x;
+  for (int c = t; c < Nc; c += EW_BLOCK) {
+    float a = 0.0f, q = 0.0f;
+    for (int i = 0; i < rpi; ++i) {  // fixed order
+      a += red[0][i * Nc + c];
+      q += red[1][i * Nc + c];
+    }
+    bnpart[(long long)blockIdx.x * Nc + c] = a;
+    bnpart[(long long)(nb + blockIdx.x) * Nc + c] = q;
+  }
+}
+
 // dw[o][r][s][i..] = (G^T (sum_z dU_z[xi]) G)[r][s], dU_z = src + z * A^2 * Nc * C
 
 template <int M>
@@ -468,31 +654,119 @@ void wg_check(int m, long long N, int H, int W, int Cin, int Cout, const char* w
                              "== 0, C_out a power of two in [64, 256 * (m == 2 ? 4 : 2)]");
 }
 
-// output transform launch: returns the BN partial rows written (0: none requested / no room)
+// Which kernel runs the output transform (EWDML_WG_OUT_PIPE at load, or ew_wg_set_out_pipe at
+// run time: tests compare the paths in one process):
+//  0: k_wg_output always;
+//  1: k_wg_output_p always -- an epilogue it has no instance for is an error;
+//  2 (default): k_wg_output_p for the instances whose step was measured faster with it
+//     (wg_out_pipe_measured: m = 2 at two channels per thread in the VGG-11 step's modes,
+//     profiles/ab/README.md), k_wg_output for everything else.
+int g_wg_out_pipe = -1;
+int wg_out_pipe_mode() {
+  if (g_wg_out_pipe < 0) {
+    const char* e = getenv("EWDML_WG_OUT_PIPE");
+    g_wg_out_pipe = (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2;
+  }
+  return g_wg_out_pipe;
+}
+
+// k_wg_output_p's instances: the epilogue modes the models reach (VGG-11, ResNet-50 at 32 and
+// 224 px, the basic-block ResNets) -- plain and forward statistics; the backward sums at the
+// output's own row with or without residual, ReLU and addend; through pool codes without residual
+// or addend (no model pools a residual block's output or hands a second gradient to a pooled
+// layer's input).  Anything else is an error under EWDML_WG_OUT_PIPE=1; the default never asks
+// for it (wg_out_pipe_measured).
+template <int M, int VW>
+void wg_output_p(int stat, bool res, bool relu, bool add, dim3 grid, hipStream_t s,
+                 const float* Mo, float* y, int H, int W, int Nc, long long tiles, int tpb,
+                 float* bnpart, const CfBnBwd& bb, const float* addend) {
+#define WO_CASE(S_, RES_, RELU_, ADD_)                                                          \
+  if (stat == S_ && res == RES_ && relu == RELU_ && add == ADD_) {                              \
+    hipLaunchKernelGGL((k_wg_output_p<M, VW, S_, RES_, RELU_, ADD_>), grid, dim3(EW_BLOCK), 0, s, \
+                       Mo, y, H, W, Nc, tiles, tpb, bnpart, bb, addend);                        \
+    return;                                                                                     \
+  }
+  WO_CASE(WO_NONE, false, false, false)
+  WO_CASE(WO_NONE, false, false, true)
+  WO_CASE(WO_FWD, false, false, false)
+  WO_CASE(WO_BWD, false, false, false)
+  WO_CASE(WO_BWD, false, false, true)
+  WO_CASE(WO_BWD, false, true, false)
+  WO_CASE(WO_BWD, false, true, true)
+  WO_CASE(WO_BWD, true, false, false)
+  WO_CASE(WO_BWD, true, false, true)
+  WO_CASE(WO_BWD, true, true, false)
+  WO_CASE(WO_BWD, true, true, true)
+  WO_CASE(WO_BWDC, false, false, false)
+  WO_CASE(WO_BWDC, false, true, false)
+#undef WO_CASE
+  throw std::runtime_error(
+      "ewdml winograd f32 output transform: no pipelined kernel for this epilogue (statistics " +
+      std::to_string(stat) + ", residual " + std::to_string((int)res) + ", relu " +
+      std::to_string((int)relu) + ", addend " + std::to_string((int)add) +
+      "); EWDML_WG_OUT_PIPE=0 or 2 runs the general kernel");
+}
+
+// the instances the default takes: forward sums, and the backward sums of a BN + ReLU layer
+// (direct or through pool codes) without residual or addend, at m = 2 and C_out <= 512
+bool wg_out_pipe_measured(int m, int ovw, int stat, bool res, bool relu, bool add) {
+  return m == 2 && ovw == 2 && !res && !add &&
+         (stat == WO_FWD || ((stat == WO_BWD || stat == WO_BWDC) && relu));
+}
+
+// output transform launch: returns the BN partial rows written (0: none requested / no room).
+// tpb_force > 0 (tests): that many tiles per block instead of the plan's
 template <int M>
 int wg_output(const float* Mo, float* y, long long N, int H, int W, int Nc, float* bnpart,
-              long long bnpart_floats, const CfBnBwd& bb, const float* addend, hipStream_t s) {
+              long long bnpart_floats, const CfBnBwd& bb, const float* addend, hipStream_t s,
+              int tpb_force = 0) {
   const long long tiles = wg_tiles(M, N, H, W);
   const int ovw = Nc <= 2 * EW_BLOCK ? 2 : 4;
   const int rpi = EW_BLOCK / (Nc / ovw);
   long long tpb = rpi, nblk = (tiles + tpb - 1) / tpb;
-  if (bnpart) {
-    while (nblk > 1024) {
-      tpb += rpi;
+  if (tpb_force > 0) {
+    tpb = tpb_force;
+    nblk = (tiles + tpb - 1) / tpb;
+    if (bnpart && 2LL * nblk * Nc > bnpart_floats)
+      throw std::runtime_error("ewdml winograd f32 output transform: bnpart too small");
+  } else {
+    if (bnpart) {
+      while (nblk > 1024) {
+        tpb += rpi;
+        nblk = (tiles + tpb - 1) / tpb;
+      }
+      if (2LL * nblk * Nc > bnpart_floats) bnpart = nullptr;
+    }
+    if (!bnpart) {
+      tpb = rpi;
       nblk = (tiles + tpb - 1) / tpb;
     }
-    if (2LL * nblk * Nc > bnpart_floats) bnpart = nullptr;
   }
-  if (!bnpart) {
-    tpb = rpi;
-    nblk = (tiles + tpb - 1) / tpb;
-  }
-  if (ovw == 2)
+  const int stat = !bnpart ? WO_NONE : !bb.h ? WO_FWD : bb.code ? WO_BWDC : WO_BWD;
+  const bool bwd = stat == WO_BWD || stat == WO_BWDC;
+  const bool res = bwd && bb.res, relu = bwd && bb.relu != 0;
+  const int pipe = wg_out_pipe_mode();
+  if (pipe == 1 || (pipe == 2 && wg_out_pipe_measured(M, ovw, stat, res, relu, addend != nullptr))) {
+    // its Mo loads take a 32-bit byte offset per thread
+    if (tiles * Nc >= (1LL << 30))
+      throw std::runtime_error("ewdml winograd f32 output transform: the pipelined kernel needs "
+                               "tiles * C_out < 2^30");
+    if (ovw == 2)
+      wg_output_p<M, 2>(stat, res, relu, addend != nullptr, dim3((unsigned)nblk), s, Mo, y, H, W,
+                        Nc, tiles, (int)tpb, bnpart, bb, addend);
+    else if constexpr (M == 2)
+      wg_output_p<M, 4>(stat, res, relu, addend != nullptr, dim3((unsigned)nblk), s, Mo, y, H, W,
+                        Nc, tiles, (int)tpb, bnpart, bb, addend);
+    else
+      throw std::runtime_error("ewdml winograd f32 output transform: no pipelined kernel for "
+                               "m = 4 with more than 512 output channels");
+  } else if (ovw == 2) {
     hipLaunchKernelGGL((k_wg_output<M, 2>), dim3((unsigned)nblk), dim3(EW_BLOCK), 0, s, Mo, y, H,
                        W, Nc, tiles, (int)tpb, bnpart, bb, addend);
-  else
+  } else {
     hipLaunchKernelGGL((k_wg_output<M, 4>), dim3((unsigned)nblk), dim3(EW_BLOCK), 0, s, Mo, y, H,
                        W, Nc, tiles, (int)tpb, bnpart, bb, addend);
+  }
   EW_CHECK_LAUNCH();
   return bnpart ? (int)nblk : 0;
 }
@@ -702,6 +976,39 @@ int ew_wino_f32_wgrad(uintptr_t dy, uintptr_t V, uintptr_t dw, uintptr_t D, int 
            reinterpret_cast<float*>(dw), reinterpret_cast<float*>(D), d_ready,
            reinterpret_cast<float*>(U_scratch), reinterpret_cast<float*>(ws), ws_floats, N, H, W,
            C, Nc, defer_out, (hipStream_t)stream);
+}
+
+int ew_wg_set_out_pipe(int on) {
+  const int prev = wg_out_pipe_mode();
+  if (on >= 0) g_wg_out_pipe = on > 2 ? 2 : on;
+  return prev;
+}
+
+// The output transform alone (tests, probes): y [N][H][W][Nc] from Mo [(m + 2)^2][tiles][Nc],
+// with the epilogue of ew_wino_f32_fwd (bn_h 0) or ew_wino_f32_bwd_data.  Needs only what the
+// kernels themselves need (any tile count; Mo within wg_check's 2^31 floats).  tpb > 0: that many
+// tiles per block.
+int ew_wino_f32_output(uintptr_t Mo, uintptr_t y, long long N, int H, int W, int Nc, int m,
+                       uintptr_t bn_h, uintptr_t bn_res, uintptr_t bn_code, uintptr_t bn_stats,
+                       int bn_relu, uintptr_t bnpart, long long bnpart_floats, uintptr_t addend,
+                       int tpb, uintptr_t stream) {
+  const bool pow2 = Nc >= 64 && Nc <= 4 * EW_BLOCK && (Nc & (Nc - 1)) == 0;
+  if ((m != 2 && m != 4) || N <= 0 || H <= 0 || W <= 0 || H % m || W % m || !pow2 || tpb < 0 ||
+      !Mo || !y || (bn_h && !bn_stats) || ((bn_res || bn_code) && !bn_h) ||
+      (long long)N * H * W >= (1LL << 29) ||  // pool rows (4x) in 32 bits
+      (long long)(m + 2) * (m + 2) * wg_tiles(m, N, H, W) * Nc >= (1LL << 31))
+    throw std::runtime_error("ewdml winograd f32 output transform: needs m in {2, 4}, H, W % m "
+                             "== 0, C_out a power of two in [64, 1024], Mo < 2^31 floats, stats with h");
+  const long long tiles = wg_tiles(m, N, H, W);
+  if (tpb > 0 && (tiles + tpb - 1) / tpb > 65535)
+    throw std::runtime_error("ewdml winograd f32 output transform: tpb too small");
+  const CfBnBwd bb{reinterpret_cast<const float*>(bn_h), reinterpret_cast<const float*>(bn_res),
+                   reinterpret_cast<const uint8_t*>(bn_code),
+                   reinterpret_cast<const float*>(bn_stats), bn_relu, H, W};
+  auto* f = m == 2 ? wg_output<2> : wg_output<4>;
+  return f(reinterpret_cast<const float*>(Mo), reinterpret_cast<float*>(y), N, H, W, Nc,
+           reinterpret_cast<float*>(bnpart), bnpart_floats, bb,
+           reinterpret_cast<const float*>(addend), (hipStream_t)stream, tpb);
 }
 
 void ew_wino_f32_wgrad_out(uintptr_t src, int split, uintptr_t dw, int Nc, int C, int m,
