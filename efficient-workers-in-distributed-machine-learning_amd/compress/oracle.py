@@ -1631,3 +1631,70 @@ def intsgd_alpha(partials: torch.Tensor, r: float, steps: int, lr: float, numel:
             inv_na = np.float32(np.float64(1.0) / (np.float64(alpha) * np.float64(world)))
     return dict(r=r, s_last=s, alpha=float(alpha), inv_a=float(inv_a), inv_na=float(inv_na),
                 steps=int(steps) + 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# Muon (Jordan et al., 2024): momentum SGD whose update of every matrix is the momentum
+# orthogonalised by a few Newton-Schulz iterations.  The definition of ``ops/csrc/muon.hip``.
+# ``p`` / ``mom`` / ``g`` are views of one flat range, ``tensors`` its ``(offset, numel, rows)``
+# rows with ``rows = shape[0]`` of a tensor that adapts (``ndim >= 2``, viewed as ``[rows, numel /
+# rows]``) and 0 of one that does not (biases, BatchNorm scales: momentum SGD).
+# ---------------------------------------------------------------------------------------------
+MUON_COEFFS = (3.4445, -4.7750, 2.0315)
+MUON_NS_DTYPES = ("fp32", "bf16")
+
+
+def _muon_bf16(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.bfloat16).to(x.dtype)  # round to nearest even
+
+
+def muon_orthogonalize(u: torch.Tensor, steps: int = 5, ns_dtype: str = "fp32") -> torch.Tensor:
+    """``steps`` Newton-Schulz iterations on the matrix ``u`` ([n, m]), in ``u``'s dtype::
+
+        X = u / (|u|_F + 1e-7), transposed when n > m
+        A = X X^T;  B = b A + c A A;  X = a X + B X
+
+    ``ns_dtype`` "bf16": the operands of the three products (X, A, B) are rounded to bf16 where a
+    product reads them; the sums, ``a X``, ``b A``, the norm and X / A / B themselves stay in
+    ``u``'s dtype.  A zero ``u`` gives zero."""
+    if ns_dtype not in MUON_NS_DTYPES:
+        raise ValueError(f"unknown Newton-Schulz dtype {ns_dtype!r}")
+    a, b, c = MUON_COEFFS
+    rd = _muon_bf16 if ns_dtype == "bf16" else (lambda t: t)
+    n, m = u.shape
+    x = u / ((u * u).sum().sqrt() + 1e-7)
+    if n > m:
+        x = x.t()
+    for _ in range(int(steps)):
+        xr = rd(x)
+        A = xr @ xr.t()
+        ar = rd(A)
+        B = b * A + c * (ar @ ar)
+        x = a * x + rd(B) @ xr
+    return x.t() if n > m else x
+
+
+def muon_apply(p, mom, g, tensors, lr, momentum, weight_decay, nesterov, aux_ratio=1.0,
+               ns_steps=5, ns_dtype="fp32"):
+    """One Muon step with the already scaled gradient ``g``: ``mom = momentum * mom + g``, ``u = g
+    + momentum * mom`` (Nesterov) or ``mom``; a vector takes ``p -= lr_aux (u + wd p)`` with
+    ``lr_aux = lr * aux_ratio`` (both rounded to fp32 first), a matrix ``p = p (1 - lr wd) - lr
+    sqrt(max(1, n / m)) O`` with ``O = muon_orthogonalize(u)``.  The state's dtype is the
+    arithmetic's (fp64 state: the tests' reference, with the same fp32 scalars)."""
+    f32 = np.float32
+    lr32, mu, wd = f32(lr), float(f32(momentum)), float(f32(weight_decay))
+    lr_aux = float(lr32 * f32(aux_ratio))
+    g = g.to(p.dtype)
+    for off, numel, rows in tensors:
+        pt, mt, gt = p[off:off + numel], mom[off:off + numel], g[off:off + numel]
+        mt.copy_(mt * mu + gt)
+        u = gt + mt * mu if nesterov else mt
+        if not rows:
+            d = u + pt * wd if wd != 0.0 else u
+            pt.copy_(pt - d * lr_aux)
+            continue
+        cols = numel // rows
+        o = muon_orthogonalize(u.reshape(rows, cols), ns_steps, ns_dtype).reshape(-1)
+        decay = float(f32(1.0) - lr32 * f32(wd))
+        step = float(lr32 * f32(np.sqrt(f32(max(1.0, rows / cols)))))
+        pt.copy_(pt * decay - o * step)

@@ -129,6 +129,12 @@ class Config:
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
     lars_eta: Optional[float] = None  # lars: trust coefficient (None: 0.001)
+    # muon (Newton-Schulz orthogonalised momentum on every dim >= 2 tensor): iterations (None: 5,
+    # 1..10), the products' operand precision fp32 | bf16 (None: fp32), and the lr of the vectors'
+    # momentum SGD (None: --lr)
+    muon_ns_steps: Optional[int] = None
+    muon_ns_dtype: Optional[str] = None
+    muon_aux_lr: Optional[float] = None
     # lion: "B1,B2" (None: 0.9,0.99), each in [0, 1); resolved to a tuple of two floats
     lion_betas: Optional[str] = None
     # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
@@ -600,6 +606,21 @@ class Config:
                 raise ValueError("--lars-eta must be > 0")
         elif c.lars_eta is not None:
             raise ValueError("--lars-eta belongs to --optimizer lars")
+        if c.optimizer == "muon":
+            c.muon_ns_steps = 5 if c.muon_ns_steps is None else int(c.muon_ns_steps)
+            c.muon_ns_dtype = c.muon_ns_dtype or "fp32"
+            if not 1 <= c.muon_ns_steps <= 10:
+                raise ValueError("--muon-ns-steps must lie in 1..10")
+            if c.muon_ns_dtype not in ("fp32", "bf16"):
+                raise ValueError("--muon-ns-dtype is fp32 or bf16")
+            if c.muon_aux_lr is not None and not c.muon_aux_lr > 0:
+                raise ValueError("--muon-aux-lr must be > 0")
+        else:
+            for flag, v in (("--muon-ns-steps", c.muon_ns_steps),
+                            ("--muon-ns-dtype", c.muon_ns_dtype),
+                            ("--muon-aux-lr", c.muon_aux_lr)):
+                if v is not None:
+                    raise ValueError(f"{flag} belongs to --optimizer muon")
         if c.clip_grad_norm is not None:
             # the clip scales every gradient of the rank once, after backward and before any
             # encode (parallel/clip.py); the exchanges below do not take a clipper
@@ -752,7 +773,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
       choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb", "lion",
-               "onebit_lamb"])
+               "onebit_lamb", "muon"])
+    a("--muon-ns-steps", type=int, default=None)
+    a("--muon-ns-dtype", type=str, default=None, choices=["fp32", "bf16"])
+    a("--muon-aux-lr", type=float, default=None)
     a("--lion-betas", type=str, default=None)
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)

@@ -1508,6 +1508,146 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
     C.layerwise_apply(args)
 
 
+# Muon (csrc/muon.hip): output tile edge and k-step of its products; the gram's long dimension is
+# cut into slabs of about MUON_SLAB_K columns (a multiple of MUON_K), MUON_MAX_SPLITS at the most
+MUON_TILE, MUON_K = 64, 32
+MUON_SLAB_K, MUON_MAX_SPLITS = 512, 16
+MUON_NS_DTYPES = {"fp32": 0, "bf16": 1}
+
+
+class MuonPlan:
+    """Tables of one flat range (a bucket or the whole model) for Muon: the range's ``BucketPlan``
+    chunk table, and for its matrices (``rows[t]`` = ``shape[0]`` of tensor t, 0 for a vector) the
+    matrix table and the three work lists of ``csrc/muon.hip`` (``MuonMat`` / ``MuonItem``).  The
+    host lists (``mats``, ``gram``, ``poly``, ``update``, the ``*_floats`` / ``num_tickets``
+    workspace sizes) are built without a device; :meth:`to` makes the device tables."""
+
+    def __init__(self, plan, rows):
+        if len(rows) != plan.num_tensors:
+            raise ValueError("one row count per tensor of the range")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        self.plan = plan
+        self.mats, self.xoff = [], []
+        self.gram, self.poly, self.update = [], [], []
+        x = a = slab = tick = 0
+        for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
+            if not n:
+                self.xoff.append(-1)
+                continue
+            if n < 0 or numel % n:
+                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
+            m = numel // n
+            r, c = min(n, m), max(n, m)
+            rs, cs = (m, 1) if n <= m else (1, m)
+            tr, tc = -(-r // MUON_TILE), -(-c // MUON_TILE)
+            want = max(1, min(MUON_MAX_SPLITS, c // MUON_SLAB_K))
+            kper = -(-(-(-c // want)) // MUON_K) * MUON_K
+            splits = -(-c // kper)
+            mi, tiles = len(self.mats), tr * (tr + 1) // 2
+            self.mats.append([off, n, m, r, c, rs, cs, x, a, slab if splits > 1 else 0,
+                              tick if splits > 1 else 0, splits, kper, plan.tensor_chunk0[t],
+                              plan.tensor_nchunks[t], 0])
+            self.xoff.append(x)
+            tile = 0
+            for ti in range(tr):
+                for tj in range(ti, tr):
+                    self.gram += [[mi, ti, tj, s, tile, 0] for s in range(splits)]
+                    self.poly.append([mi, ti, tj, 0, tile, 0])
+                    tile += 1
+            self.update += [[mi, ti, tj, 0, 0, 0] for ti in range(tr) for tj in range(tc)]
+            x += -(-numel // 4) * 4
+            a += -(-r * r // 4) * 4
+            if splits > 1:
+                slab += tiles * splits * MUON_TILE * MUON_TILE
+                tick += tiles
+        self.x_floats, self.a_floats, self.slab_floats, self.num_tickets = x, a, slab, tick
+        if max(x, a, slab, plan.length) >= 1 << 31:
+            raise ValueError("Muon plan of 2^31 elements or more")
+        self.chunks = self.xoff_t = self.mats_t = self.gram_t = self.poly_t = self.update_t = None
+
+    def to(self, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.chunks = self.plan.chunk_table(device)
+        self.xoff_t = torch.tensor(self.xoff, **i32)
+        if self.mats:
+            self.mats_t = torch.tensor(self.mats, **i32)
+            self.gram_t = torch.tensor(self.gram, **i32)
+            self.poly_t = torch.tensor(self.poly, **i32)
+            self.update_t = torch.tensor(self.update, **i32)
+        return self
+
+
+class MuonWorkspace:
+    """Muon's device workspaces, allocated once for the largest of ``plans``: the two X buffers,
+    the r x r buffers A and B, the gram's slabs and its arrival counters (zero at allocation;
+    every gram launch leaves them zeroed)."""
+
+    def __init__(self, plans, device):
+        self.x_floats = max(4, max(p.x_floats for p in plans))
+        self.a_floats = max(4, max(p.a_floats for p in plans))
+        self.slab_floats = max(4, max(p.slab_floats for p in plans))
+        self.num_tickets = max(1, max(p.num_tickets for p in plans))
+        f32 = dict(dtype=torch.float32, device=device)
+        self.x = torch.zeros(2, self.x_floats, **f32)
+        self.a = torch.zeros(self.a_floats, **f32)
+        self.b = torch.zeros(self.a_floats, **f32)
+        self.slabs = torch.zeros(self.slab_floats, **f32)
+        self.tickets = torch.zeros(self.num_tickets, dtype=torch.int32, device=device)
+
+    def fits(self, mp: MuonPlan) -> bool:
+        return (mp.x_floats <= self.x_floats and mp.a_floats <= self.a_floats
+                and mp.slab_floats <= self.slab_floats and mp.num_tickets <= self.num_tickets)
+
+
+def muon_step(mp: MuonPlan, ws: MuonWorkspace, param, grad, mom, partials, *, lr, aux_ratio=1.0,
+              momentum=0.95, weight_decay=0.0, grad_scale=1.0, nesterov=False, ns_steps=5,
+              ns_dtype="fp32", lr_tensor=None, shadow=None):
+    """One Muon step of the flat range ``mp`` describes (``compress/oracle.py muon_apply``), in 1 +
+    3 * ``ns_steps`` launches: ``k_muon_momentum`` (the momentum; the vectors' step; every
+    matrix's u into the X workspace and its chunk sums of squares into ``partials``), then per
+    Newton-Schulz iteration ``k_muon_gram``, ``k_muon_poly`` and ``k_muon_update``, whose last
+    instance steps the matrices' parameters."""
+    C = require()
+    n = mp.plan.length
+    if mp.chunks is None or not ws.fits(mp):
+        raise ValueError("the Muon plan has no device tables or does not fit the workspace")
+    if ns_dtype not in MUON_NS_DTYPES or not 1 <= int(ns_steps) <= 10:
+        raise ValueError(f"Muon takes 1..10 Newton-Schulz steps in fp32 or bf16, not "
+                         f"{ns_steps!r} in {ns_dtype!r}")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(mom, torch.float32, "mom")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check(partials, torch.float32, "partials", align=4)
+    for s, nm in ((param, "param"), (grad, "grad"), (mom, "mom")):
+        if s.numel() < n:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {n}")
+    if partials.numel() < mp.plan.num_chunks:
+        raise ValueError("partials holds fewer entries than the range has chunks")
+    _check_shadow(mp, shadow)
+    common = dict(param=_ptr(param), shadow=_ptr(shadow), partials=_ptr(partials), lr=float(lr),
+                  lr_ptr=_lrp(lr_tensor), weight_decay=float(weight_decay), stream=_stream())
+    C.muon_momentum(_args(
+        C.MuonArgs, mom=_ptr(mom), grad=_ptr(grad), grad_dtype=_GDT[grad.dtype],
+        chunks=_ptr(mp.chunks), num_chunks=mp.plan.num_chunks, xoff=_ptr(mp.xoff_t),
+        x_out=_ptr(ws.x[0]), aux_ratio=float(aux_ratio), momentum=float(momentum),
+        grad_scale=float(grad_scale), nesterov=int(bool(nesterov)), **common))
+    if not mp.mats:
+        return
+    for s in range(int(ns_steps)):
+        it = dict(mats=_ptr(mp.mats_t), x_in=_ptr(ws.x[s & 1]), x_out=_ptr(ws.x[(s + 1) & 1]),
+                  a_buf=_ptr(ws.a), b_buf=_ptr(ws.b), slabs=_ptr(ws.slabs),
+                  tickets=_ptr(ws.tickets), ns_bf16=MUON_NS_DTYPES[ns_dtype], first=int(s == 0),
+                  last=int(s == int(ns_steps) - 1), **common)
+        for launch, items in ((C.muon_gram, mp.gram_t), (C.muon_poly, mp.poly_t),
+                              (C.muon_update, mp.update_t)):
+            launch(_args(C.MuonArgs, items=_ptr(items), num_items=items.shape[0], **it))
+
+
 # Longest chain of fp32 additions behind one chunk's sum of squares in k_clip_norm
 # (csrc/clip.hip), k_lw_stage's tree: 32 serial terms per thread + 6 shuffle levels + 3 across
 # the waves.  The model-wide sum over the chunks is fp64.

@@ -20,6 +20,10 @@ HIP_FLAGS = [
     "-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off",
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
 ]
+# per-source additions: muon.hip is built without the packed fp32 instructions
+FILE_FLAGS = {
+    "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def ext_path() -> str:
@@ -58,7 +62,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
         if not force and not _stale(obj, src):
             continue
         if f.endswith(".hip"):
-            cmd = [HIPCC, "-c", *HIP_FLAGS, "-I", CSRC, "-o", obj, src]
+            cmd = [HIPCC, "-c", *HIP_FLAGS, *FILE_FLAGS.get(f, []), "-I", CSRC, "-o", obj, src]
         else:
             cmd = ["g++", "-c", "-O2", "-fPIC", "-std=c++17", "-I", CSRC,
                    "-I", pybind11.get_include(), "-I", sysconfig.get_paths()["include"],

@@ -191,6 +191,11 @@ PYBIND11_MODULE(_C, m) {
           F(partials) F(ratio) F(stream) F(num_chunks) F(kind) F(grad_dtype) F(lr) F(beta1)
           F(beta2) F(eps) F(weight_decay) F(grad_scale) F(eta) F(momentum) F(dampening) F(bc1)
           F(bc2) F(beta1d) F(beta2d) F(nesterov) F(first) F(step) F(lr_ptr))
+  EW_ARGS(MuonArgs,
+          F(param) F(mom) F(grad) F(shadow) F(chunks) F(xoff) F(partials) F(stream) F(mats)
+          F(items) F(x_in) F(x_out) F(a_buf) F(b_buf) F(slabs) F(tickets) F(num_chunks)
+          F(num_items) F(grad_dtype) F(ns_bf16) F(nesterov) F(first) F(last) F(lr) F(aux_ratio)
+          F(momentum) F(weight_decay) F(grad_scale) F(lr_ptr))
   EW_ARGS(ClipArgs,
           F(num_tensors) F(num_chunks) F(chunk0) F(total_chunks) F(chunks) F(partials) F(state)
           F(stream) F(max_norm))
@@ -245,6 +250,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("vote_reduce", &ew_vote_reduce);
   m.def("layerwise_stage", &ew_layerwise_stage);
   m.def("layerwise_apply", &ew_layerwise_apply);
+  m.def("muon_momentum", &ew_muon_momentum);
+  m.def("muon_gram", &ew_muon_gram);
+  m.def("muon_poly", &ew_muon_poly);
+  m.def("muon_update", &ew_muon_update);
   m.def("outer_apply", &ew_outer_apply);
 
   m.def("cast_scale", &ew_cast_scale);

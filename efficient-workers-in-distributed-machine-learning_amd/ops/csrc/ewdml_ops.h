@@ -436,6 +436,29 @@ struct LayerwiseArgs {
 void ew_layerwise_stage(const LayerwiseArgs& a);
 void ew_layerwise_apply(const LayerwiseArgs& a);
 
+// Muon over a flat range (muon.hip; ops.MuonPlan builds the tables).  The momentum launch walks
+// the range's chunk table (param, mom, grad, shadow: its views; xoff int32[T]: a matrix's offset in
+// the X workspace, -1 for a vector) and writes u into x_out and the chunk sums of u^2 into
+// partials fp32[num_chunks].  The gram / poly / update launches walk `items` (int32 [num_items, 6])
+// over the matrix table `mats` (int32 [M, 16]): x_in / x_out are the two X workspaces, a_buf /
+// b_buf the r x r workspaces, slabs / tickets the gram's split-K slabs and zeroed arrival
+// counters.  first: x_in holds u, every load of it applies 1 / (|u| + 1e-7) from the partials;
+// last: the update writes param (and shadow) instead of x_out.
+struct MuonArgs {
+  uintptr_t param, mom, grad, shadow, chunks, xoff, partials, stream;
+  uintptr_t mats, items, x_in, x_out, a_buf, b_buf, slabs, tickets;
+  int num_chunks, num_items;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  int ns_bf16;     // the products' operands rounded to bf16 (v_mfma_f32_16x16x32_bf16) or fp32
+  int nesterov, first, last;
+  float lr, aux_ratio, momentum, weight_decay, grad_scale;
+  uintptr_t lr_ptr;  // nullable device fp32 lr (overrides lr)
+};
+void ew_muon_momentum(const MuonArgs& a);
+void ew_muon_gram(const MuonArgs& a);
+void ew_muon_poly(const MuonArgs& a);
+void ew_muon_update(const MuonArgs& a);
+
 // Global-norm gradient clipping (clip.hip), one bucket per call: the bucket's gradients through
 // the pointer table of pack_grads, its chunk table, and the model-wide partials fp32[total_chunks]
 // in which this bucket's rows start at chunk0.  ew_clip_norm of every bucket comes before any

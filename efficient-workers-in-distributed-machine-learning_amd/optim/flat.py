@@ -588,8 +588,97 @@ class FlatOnebitLamb(FlatLAMB):
                 setattr(self, k, float(sd[k]))
 
 
+class FlatMuon(_Layerwise):
+    """Muon (Jordan et al., 2024): ``mom = momentum * mom + g`` and ``u = mom`` (Nesterov: ``g +
+    momentum * mom``) on every tensor, with no first-step special case.  A tensor that adapts
+    (``dim() >= 2``, viewed as ``[shape[0], numel / shape[0]]``) steps by ``u`` orthogonalised
+    with ``ns_steps`` Newton-Schulz iterations (``compress/oracle.py muon_orthogonalize``), ``p =
+    p (1 - lr wd) - lr sqrt(max(1, n / m)) O``; the others take momentum SGD at ``lr_aux = lr *
+    aux_lr / (the lr at construction)``, so a schedule moves both rates together.  On the GPU a
+    step is ``ops.muon_step`` (``csrc/muon.hip``), on the CPU the torch oracle."""
+    kind = "muon"
+
+    def __init__(self, flat, lr=0.02, momentum=0.95, weight_decay=0.0, nesterov=False,
+                 ns_steps=5, ns_dtype="fp32", aux_lr=None):
+        if not 1 <= int(ns_steps) <= 10:
+            raise ValueError(f"Muon takes 1..10 Newton-Schulz steps, not {ns_steps!r}")
+        if ns_dtype not in oracle.MUON_NS_DTYPES:
+            raise ValueError(f"Muon's Newton-Schulz dtype is fp32 or bf16, not {ns_dtype!r}")
+        if not lr > 0 or (aux_lr is not None and not aux_lr > 0):
+            raise ValueError("Muon needs lr > 0 and aux_lr > 0")
+        super().__init__(flat, lr, weight_decay)
+        self.momentum, self.nesterov = momentum, nesterov
+        self.ns_steps, self.ns_dtype = int(ns_steps), ns_dtype
+        self.aux_ratio = 1.0 if aux_lr is None else float(aux_lr) / float(lr)
+        self.mom = torch.zeros_like(flat.data)
+        self.rows = [p.shape[0] if a else 0 for p, a in zip(flat.params, self.adapts)]
+        self._ws = None
+        if flat.data.is_cuda:  # every bucket's plan now, so the workspace fits the largest
+            plans = [self._plan(b.start, b.length) for b in flat.buckets]
+            self._ws = ops.MuonWorkspace([mp for mp, _ in plans], flat.data.device)
+            for key, (mp, _) in list(self._plans.items()):
+                self._plans[key] = (mp, self._ws)
+
+    def trust_ratio_range(self):
+        return None  # no trust ratios
+
+    def _plan(self, start, length):
+        """The range's device plan and workspace (built once).  The whole model steps in the
+        buckets' workspace when it fits and in one of its own otherwise."""
+        got = self._plans.get((start, length))
+        if got is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            dev = self.flat.data.device
+            mp = ops.MuonPlan(plan, self.rows[t0:t0 + nt]).to(dev)
+            ws = self._ws
+            if ws is not None and not ws.fits(mp):
+                ws = ops.MuonWorkspace([mp], dev)
+            got = self._plans[(start, length)] = (mp, ws)
+        return got
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        sl = slice(start, start + length)
+        p, m = self.flat.data[sl], self.mom[sl]
+        hp = dict(lr=self.lr, aux_ratio=self.aux_ratio, momentum=self.momentum,
+                  weight_decay=self.weight_decay, nesterov=self.nesterov,
+                  ns_steps=self.ns_steps, ns_dtype=self.ns_dtype)
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            mp, ws = self._plan(start, length)
+            c0 = self._chunk0[self._range(start, length)[0]]
+            ops.muon_step(mp, ws, p, grad, m, self._partials[c0:c0 + mp.plan.num_chunks],
+                          grad_scale=grad_scale, lr_tensor=self.lr_t, shadow=sh, **hp)
+            return
+        t0, tensors = self._tensors(start, length)
+        rows = [(off, n, self.rows[t0 + i]) for i, (off, n, _) in enumerate(tensors)]
+        oracle.muon_apply(p, m, grad.to(torch.float32) * grad_scale, rows, **hp)
+
+    def state_dict(self):
+        return {"kind": "muon", "mom": self.mom, "steps": self.steps, "lr": self.lr,
+                "momentum": self.momentum, "weight_decay": self.weight_decay,
+                "nesterov": self.nesterov, "ns_steps": self.ns_steps, "ns_dtype": self.ns_dtype,
+                "aux_ratio": self.aux_ratio}
+
+    def load_state_dict(self, sd):
+        self.mom.copy_(sd["mom"])
+        self._load_common(sd)
+        for k in ("momentum", "nesterov", "ns_steps", "ns_dtype", "aux_ratio"):
+            if k in sd:
+                setattr(self, k, sd[k])
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "muon":
+        return FlatMuon(flat, aux_lr=kw.get("aux_lr"), ns_steps=kw.get("ns_steps") or 5,
+                        ns_dtype=kw.get("ns_dtype") or "fp32",
+                        **{k: v for k, v in kw.items()
+                           if k in ("lr", "momentum", "weight_decay", "nesterov")})
     if name == "onebit_lamb":
         return FlatOnebitLamb(flat, lr=kw.get("lr", 1e-3),
                               weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),
