@@ -409,6 +409,9 @@ def topk_decode_apply(dp: DevicePlan, recv, layout, levels: int, param=None, mom
 def qsgd_encode(dp: DevicePlan, grad, payload, layout, levels: int, norm: str, key: int,
                 resid=None, key_tensor=None):
     C = require()
+    if layout.kind != "qsgd" or layout.bits not in (4, 8):
+        # another kind's scales_off / codes_off would address the payload in another format
+        raise ValueError(f"qsgd codec given a {layout.kind!r} layout of {layout.bits} bits")
     ptrs, mask = grad_pointers(dp, grad)
     _encode_dst(payload, layout)
     if resid is not None:

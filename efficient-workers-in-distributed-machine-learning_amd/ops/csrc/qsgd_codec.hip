@@ -5,6 +5,15 @@
 // tensor, fixed-order reduction -> bitwise reproducible), quant (one read, one code write with
 // per-element counter RNG).  Each thread owns a group of 4 consecutive elements, so int8 codes are
 // one 32-bit store and int4 codes one 16-bit store per group.
+//
+// Supported range of the L2 norm: the squares are summed in fp32, as the reference's fp32
+// tensor.norm() sums them, so the scale is that of the tensor only while every x * x and their sum
+// stay normal fp32 numbers (|x| between about 2^-63 and 2^63, less log2(numel) / 2 at the top).
+// Below that the squares go subnormal or to zero (a scale too small, down to 0: the codes saturate
+// or the tensor is sent as zeros), above it the sum overflows (scale inf: the decode is non-finite).
+// Inside the range the scale is within ((adds on the longest path + 1) / 2 + 1) * 2^-24 of the
+// exact norm, about 1.7e-6 (tests/kernels/test_qsgd_codec_hip.py derives the count); everything
+// after the scale is exact.  The max norm has no such limit: it is a bit pattern, not a sum.
 #include "common.h"
 #include "ewdml_ops.h"
 

@@ -19,6 +19,7 @@ DEV = "cuda"
 NUMELS = (8192 + 5, 37)
 N = 2
 LEVELS = 127
+LEVELS4 = 7  # the 4-bit rows' own levels
 ROT_KEY = oracle.hsign_rot_key(3, 1)
 SEED, STEP, RANK = 5, 41, 3
 # lr = 2^-4 and dampening = 0: lr * d and (1 - dampening) * d are exact, so the reference does not
@@ -34,10 +35,18 @@ CODECS = {
                    lambda dp, g, pay, lay, r: ops.topk_encode(dp, g, pay, lay, LEVELS, "max",
                                                               stream_key(SEED, STEP, r)),
                    ops.topk_decode_apply, (LEVELS,), {}, None, False),
+    "topk_qsgd4": ("topk_qsgd", 4,
+                   lambda dp, g, pay, lay, r: ops.topk_encode(dp, g, pay, lay, LEVELS4, "max",
+                                                              stream_key(SEED, STEP, r)),
+                   ops.topk_decode_apply, (LEVELS4,), {}, None, False),
     "qsgd8": ("qsgd", 8,
               lambda dp, g, pay, lay, r: ops.qsgd_encode(dp, g, pay, lay, LEVELS, "max",
                                                          stream_key(SEED, STEP, r)),
               ops.qsgd_decode_apply, (LEVELS,), {}, None, True),
+    "qsgd4": ("qsgd", 4,
+              lambda dp, g, pay, lay, r: ops.qsgd_encode(dp, g, pay, lay, LEVELS4, "max",
+                                                         stream_key(SEED, STEP, r)),
+              ops.qsgd_decode_apply, (LEVELS4,), {}, None, True),
     "sign": ("sign", 8, lambda dp, g, pay, lay, r: ops.sign_encode(dp, g, pay, lay),
              ops.sign_decode_apply, (), {}, None, False),
     "sign_rot": ("sign", 8,
@@ -64,6 +73,8 @@ def _case(name):
     computed once per codec and only read."""
     if name not in _CASES:
         kind, bits, encode = CODECS[name][:3]
+        args = CODECS[name][4]
+        levels = args[0] if args else LEVELS  # the row's own levels, where its codec has any
         offs, o = [], 0
         for n in NUMELS:
             offs.append(o)
@@ -78,7 +89,7 @@ def _case(name):
             for off, n in zip(plan.offsets, plan.numels):
                 g[off:off + n] = torch.randn(n, generator=gen) * (0.1 * 3.0 ** r)
             encode(dp, g.to(DEV), recv[r], lay, r)
-        mean = oracle.decode_sum(recv.cpu(), plan, lay, LEVELS, 1.0 / N, CODECS[name][6])
+        mean = oracle.decode_sum(recv.cpu(), plan, lay, levels, 1.0 / N, CODECS[name][6])
         p0 = torch.randn(plan.length, generator=gen)
         m0 = torch.randn(plan.length, generator=gen)
         _CASES[name] = (plan, lay, dp, recv, mean, p0, m0)

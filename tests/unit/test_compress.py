@@ -302,3 +302,62 @@ def test_plan_candidate_capacity_and_blocks():
     for t, nb in enumerate(plan.tensor_cblocks):
         rows = cb[cb[:, 0] == t]
         assert rows[:, 1].tolist() == list(range(nb))
+
+
+# ---- dense QSGD: the properties tests/kernels/test_qsgd_codec_hip.py leans on -------------------
+@pytest.mark.parametrize("bits,levels", [(8, 127), (4, 7)])
+@pytest.mark.parametrize("norm", ["max", "l2"])
+def test_qsgd_error_feedback_conserves_the_gradient(norm, bits, levels):
+    """sent + new residual == g + old residual: the new residual is the one fp32 rounding of
+    ``e - sent``, so the identity holds to half an ulp of it, and exactly wherever that
+    subtraction is exact."""
+    from tests import qsgd_sim as sim
+
+    plan = sim.make_plan([8192 + 13, 10, 5000, 1])
+    lay = Layout.build("qsgd", plan, bits)
+    g, r = sim.bucket(plan, 1), sim.bucket(plan, 2)
+    e = g + r
+    pay = oracle.encode_qsgd(g.clone(), plan, lay, levels, norm, rng.stream_key(3, 1, 0), r)
+    sent = oracle.decode_sum(pay[None], plan, lay, levels, 1.0)
+    for off, n in zip(plan.offsets, plan.numels):
+        s, rn, x = (t[off:off + n].double() for t in (sent, r, e))
+        assert bool(((s + rn - x).abs() <= 2.0 ** -24 * rn.abs()).all())
+        assert int((s + rn == x).sum()) > n // 2  # Sterbenz: exact for every code but the smallest
+        assert float(rn.abs().max()) <= float(x.abs().max() if norm == "max" else x.norm()) / levels
+
+
+@pytest.mark.parametrize("norm,exps", [("max", (-70, -40, 40, 70)), ("l2", (-40, 40))])
+def test_quantize_is_invariant_to_powers_of_two(norm, exps):
+    """A gradient times 2^e has the codes of the gradient and 2^e times its scale, bit for bit."""
+    n = 5000
+    x = torch.randn(n, generator=torch.Generator().manual_seed(4)) * 0.1
+    gidx, key = 77 + torch.arange(n), rng.stream_key(3, 2, 1)
+    scale = oracle._scale_of(x, norm)
+    for levels in (127, 7):
+        q = oracle.quantize(x, scale, levels, gidx, key)
+        assert int(q.abs().max()) == levels or norm == "l2"
+        for e in exps:
+            f = 2.0 ** e
+            assert oracle._scale_of(x * f, norm) == float(np.float32(scale) * np.float32(f))
+            assert torch.equal(oracle.quantize(x * f, oracle._scale_of(x * f, norm), levels, gidx,
+                                               key), q)
+            assert oracle.dequant_step(levels, scale * f) == oracle.dequant_step(levels, scale) * f
+
+
+@pytest.mark.parametrize("bits,levels", [(8, 127), (4, 7)])
+def test_qsgd_l2_unbiased(bits, levels):
+    """The mean over K = 64 keys of the decoded L2-norm payload, every element, within 6 standard
+    deviations' bound of the gradient (tests/qsgd_sim.py worst_z; the keys are counter-based, so
+    the figure is deterministic: 3.6 at worst).  The kernels are held to the same 6."""
+    from tests import qsgd_sim as sim
+
+    plan = sim.make_plan(sim.UNBIASED)
+    lay = Layout.build("qsgd", plan, bits)
+    g = sim.bucket(plan, sim.UNBIASED_SEED)
+    acc = torch.zeros(plan.length, dtype=torch.float64)
+    for key in sim.UNBIASED_KEYS:
+        pay = oracle.encode_qsgd(g.clone(), plan, lay, levels, "l2", key)
+        acc += oracle.decode_sum(pay[None], plan, lay, levels, 1.0).double()
+    z = sim.worst_z(plan, g, acc / len(sim.UNBIASED_KEYS), levels)
+    print(f"\nqsgd-l2-unbiased oracle bits={bits} worst_z={z:.3f}")
+    assert 1.0 < z <= sim.UNBIASED_Z
