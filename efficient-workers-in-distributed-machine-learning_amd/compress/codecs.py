@@ -54,15 +54,14 @@ from .. import ops
 # EWDML_ORACLE=1: run the torch oracle on device tensors too (eager experiments with codec
 # variants before they have kernels; needs flat gradient views, EWDML_GRAD_VIEWS=1)
 _FORCE_ORACLE = os.environ.get("EWDML_ORACLE") == "1"
-from . import oracle
+from . import kinds, oracle
+from .kinds import MX_FORMATS
 from .plan import POWERSGD_RANKS, SKETCH_ROWS, BucketPlan, Layout, SketchPlan
 from .rng import stream_key
 
-KINDS = ("none", "fp16", "bf16", "qsgd", "topk", "topk_qsgd", "sign", "powersgd", "vote", "mx",
-         "tern", "sketch", "thresh", "intsgd")
+KINDS = tuple(kinds.KINDS)
 VOTE_AGGREGATES = ("majority", "average")
 SIGN_ROTATIONS = ("none", "hadamard")
-MX_FORMATS = tuple(oracle.MX_NAMES)  # fp8 | fp4
 
 
 class Codec:
@@ -72,6 +71,8 @@ class Codec:
                  fmt: str = None, clip: float = 2.5, rows: int = None, width: float = None):
         if kind not in KINDS:
             raise ValueError(f"unknown codec {kind!r}; choose from {KINDS}")
+        self.spec = kinds.KINDS[kind]  # what the kind is and runs with: compress/kinds.py
+        default = {f.kw: f.default for f in self.spec.flags}  # of the keywords the kind owns
         if kind == "powersgd" and rank not in POWERSGD_RANKS:
             raise ValueError(f"PowerSGD rank must be one of {POWERSGD_RANKS}, not {rank!r}")
         self.rank = int(rank)
@@ -88,7 +89,7 @@ class Codec:
         if fmt is not None and kind != "mx":
             raise ValueError("the element format belongs to the mx codec")
         if kind == "mx":  # the element width is the format's, whatever `bits` says
-            fmt = "fp8" if fmt is None else fmt
+            fmt = default["fmt"] if fmt is None else fmt
             if fmt not in MX_FORMATS:
                 raise ValueError(f"mx format must be one of {MX_FORMATS}, not {fmt!r}")
             bits = oracle.MX_NAMES[fmt]
@@ -102,18 +103,17 @@ class Codec:
         if (rows is not None or width is not None) and kind != "sketch":
             raise ValueError("rows and width belong to the sketch codec")
         if kind == "sketch":
-            rows = 3 if rows is None else rows
-            width = 2.0 if width is None else float(width)
+            rows = default["rows"] if rows is None else rows
+            width = default["width"] if width is None else float(width)
             if rows not in SKETCH_ROWS:
                 raise ValueError(f"sketch rows must be one of {SKETCH_ROWS}, not {rows!r}")
             if not width > 0.0:
                 raise ValueError(f"sketch width must be > 0, not {width!r}")
         self.rows, self.width = rows, width
         # the sign, vote and low-rank codecs have neither bits nor levels; tern's are fixed
-        if kind not in ("sign", "powersgd", "vote", "tern", "sketch", "thresh", "intsgd") \
-                and bits not in (4, 8):
+        if self.spec.bits and bits not in (4, 8):
             raise ValueError("bits must be 8 or 4")
-        if kind in ("qsgd", "topk_qsgd"):
+        if self.spec.levels:
             lim = 127 if bits == 8 else 7
             if not 1 <= levels <= lim:
                 raise ValueError(f"QSGD levels must be in [1, {lim}] for {bits}-bit codes")
@@ -131,61 +131,32 @@ class Codec:
     @property
     def allreduce(self) -> bool:
         """Dense codecs are summed by the collective itself (all-reduce)."""
-        return self.kind in ("none", "fp16", "bf16")
+        return self.spec.wire_dtype is not None
 
     @property
     def wire_dtype(self):
-        return {"none": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}.get(self.kind)
+        return self.spec.wire_dtype
 
     def describe(self) -> str:
-        if self.kind == "topk_qsgd":
-            return f"topk{self.ratio:g}+qsgd{self.bits}b(s={self.levels},{self.norm})"
-        if self.kind == "qsgd":
-            return f"qsgd{self.bits}b(s={self.levels},{self.norm})"
-        if self.kind == "topk":
-            return f"topk{self.ratio:g}"
-        if self.kind == "sign":
-            return "sign1b-h" if self.rotate == "hadamard" else "sign1b"
-        if self.kind == "powersgd":
-            return f"powersgd-r{self.rank}"
-        if self.kind == "vote":
-            return "vote1b"
-        if self.kind == "mx":
-            return "mx" + self.fmt
-        if self.kind == "tern":
-            return f"tern2b(c={self.clip:g})" if self.clip > 0 else "tern2b"
-        if self.kind == "sketch":
-            return f"sketch-r{self.rows}"
-        if self.kind == "thresh":
-            return f"thresh-k{self.ratio:g}"
-        if self.kind == "intsgd":
-            return "intsgd8"
-        return self.kind
+        return self.spec.describe(self)
 
     # -- binding ----------------------------------------------------------------------------
     def bind(self, plans, device):
         self.device = torch.device(device)
         self.plans = list(plans)
         self._bound = {}  # ratio -> (plans, layouts, device plans): see set_ratio
-        if self.kind == "powersgd":
-            raise ValueError("the PowerSGD codec is bound by its own exchange (bind_powersgd; "
-                             "--compress powersgd on the trainer)")
-        if self.kind == "sketch":
-            raise ValueError("the sketch codec is bound by its own exchange (bind_sketch; "
-                             "--compress sketch on the trainer)")
-        if self.kind == "intsgd":
-            raise ValueError("the intsgd codec is bound by its own exchange (bind_intsgd; "
-                             "--compress intsgd on the trainer)")
+        if self.spec.own_exchange is not None:
+            raise ValueError(f"the {self.spec.own_exchange.label} codec is bound by its own "
+                             f"exchange (bind_{self.kind}; --compress {self.kind} on the trainer)")
         if self.allreduce:
             self.layouts = [None] * len(self.plans)
             return self
-        lk = "qsgd" if self.kind == "qsgd" else self.kind
-        if self.kind in ("topk", "topk_qsgd", "thresh"):
+        if self.spec.density:
             # the plans carry k; rebuild with this codec's ratio if needed
             self.plans = [p if (p.ratio == self.ratio and p.dense_below == self.dense_below)
                           else BucketPlan(p.numels, p.offsets, self.ratio, p.bucket_offset,
                                           p.length, self.dense_below) for p in self.plans]
-        self.layouts = [Layout.build(lk, p, self.bits) for p in self.plans]
+        self.layouts = [Layout.build(self.kind, p, self.bits) for p in self.plans]
         if self.device.type == "cuda":
             if ops.hip_required():
                 ops.require()
@@ -202,7 +173,7 @@ class Codec:
     def set_ratio(self, ratio: float):
         """Switch a bound top-k codec to another density (top-k warm-up): the per-tensor k, the
         payload layouts and the device tables change; bindings are cached per ratio."""
-        if self.kind not in ("topk", "topk_qsgd", "sketch", "thresh"):
+        if not self.spec.density:
             raise ValueError("only top-k codecs have a density")
         if not 0.0 < ratio <= 1.0:
             raise ValueError("top-k ratio must be in (0, 1]")
@@ -260,7 +231,6 @@ class Codec:
         if self.kind == "vote":
             raise ValueError("the vote codec sends the sign of Lion's update direction: "
                              "encode_vote, with the rank's momentum")
-        plan, lay = self.plans[b], self.layouts[b]
         key = self.key(step, rank)
         on_dev = (grad[0] if isinstance(grad, (list, tuple)) else grad).is_cuda
         if ef21 and (resid is None or self.kind not in ("topk", "topk_qsgd")):
@@ -268,41 +238,14 @@ class Codec:
         if on_dev and not _FORCE_ORACLE:
             if ef21:
                 raise NotImplementedError("EF21 encode on the GPU: run with EWDML_ORACLE=1")
-            if self.kind == "sign":
-                ops.sign_encode(self.dplans[b], grad, payload, lay, resid,
-                                rot_key=self.rot_key(b))
-            elif self.kind == "mx":
-                ops.mx_encode(self.dplans[b], grad, payload, lay, resid)
-            elif self.kind == "tern":
-                ops.tern_encode(self.dplans[b], grad, payload, lay, self.clip, key, resid,
-                                key_tensor)
-            elif self.kind == "thresh":
-                ops.thresh_encode(self.dplans[b], grad, payload, lay, resid, self.thr_state[b])
-            elif self.kind == "qsgd":
-                ops.qsgd_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
-                                resid, key_tensor)
-            else:
-                ops.topk_encode(self.dplans[b], grad, payload, lay, self.levels, self.norm, key,
-                                resid, key_tensor, dgc=dgc, apply=apply)
+            self.spec.gpu_encode(self, b, grad, payload, key, resid, key_tensor, dgc, apply)
             return
         if apply is not None:
             raise ValueError("the encode-side apply runs on the GPU codec only")
         if isinstance(grad, (list, tuple)):
             raise TypeError("CPU encode takes the bucket's flat gradient view")
-        if self.kind == "sign":
-            out = oracle.encode_sign(grad, plan, lay, resid, self.rot_key(b))
-        elif self.kind == "mx":
-            out = oracle.encode_mx(grad, plan, lay, resid)
-        elif self.kind == "tern":
-            out = oracle.encode_tern(grad, plan, lay, self.clip, key, resid)
-        elif self.kind == "thresh":
-            out = oracle.encode_thresh(grad, plan, lay, resid)
-        elif self.kind == "qsgd":
-            out = oracle.encode_qsgd(grad, plan, lay, self.levels, self.norm, key, resid)
-        else:
-            out = oracle.encode_topk(grad, plan, lay, self.levels, self.norm, key, resid, dgc,
-                                     ef21)
-        payload[:lay.nbytes].copy_(out)
+        out = self.spec.cpu_encode(self, b, grad, key, resid, dgc, ef21)
+        payload[:self.layouts[b].nbytes].copy_(out)
 
     def encode_momentum(self, b: int, grad, payload: torch.Tensor, resid: torch.Tensor,
                         exp_avg: torch.Tensor, beta1: float, weight_decay: float = 0.0,
@@ -816,18 +759,7 @@ class Codec:
 
     def _gpu_decode(self, b: int, recv: torch.Tensor, **kw):
         """The codec's ``ops.*_decode_apply`` on bucket ``b``; ``kw``: what to do with the mean."""
-        dp, lay = self.dplans[b], self.layouts[b]
-        if self.kind == "sign":
-            ops.sign_decode_apply(dp, recv, lay, rot_key=self.rot_key(b), **kw)
-        elif self.kind == "mx":
-            ops.mx_decode_apply(dp, recv, lay, **kw)
-        elif self.kind == "tern":
-            ops.tern_decode_apply(dp, recv, lay, **kw)
-        elif self.kind == "thresh":
-            ops.thresh_decode_apply(dp, recv, lay, **kw)
-        else:
-            fn = ops.qsgd_decode_apply if self.kind == "qsgd" else ops.topk_decode_apply
-            fn(dp, recv, lay, self.levels, **kw)
+        self.spec.gpu_decode(self, b, recv, **kw)
 
     def decode(self, b: int, recv: torch.Tensor, out: torch.Tensor, scale: float):
         """``out`` (bucket view) = scale * sum over ranks of the decoded payloads in ``recv``."""

@@ -19,6 +19,8 @@ import dataclasses
 from dataclasses import dataclass, field
 from typing import Optional
 
+from .compress import kinds
+
 
 def _str2bool(v) -> bool:
     if isinstance(v, bool):
@@ -203,6 +205,30 @@ class Config:
     sync_debug: bool = False  # synchronise after every custom kernel (race / fault localisation)
     quiet: bool = False
 
+    @staticmethod
+    def _resolve_kinds(c: "Config", names):
+        """The codec kinds' own rules (compress/kinds.py), kind by kind in the order of
+        ``names``.  The chosen kind: its flags' defaults, then the first of its refusals that
+        holds, then what --hip-graph auto means for it.  Every other kind: its flags are orphans,
+        and it may have no --pull-compress form."""
+        for k in map(kinds.KINDS.get, names):
+            if c.compress == k.name:
+                for f in k.flags:
+                    if getattr(c, f.field) is None:
+                        setattr(c, f.field, f.default)
+                for refuses, why in k.refusals:
+                    if refuses(c):
+                        raise ValueError(f"--compress {k.name} " + why.format(c=c))
+                if c.hip_graph == "auto" and k.auto_graph is not None:
+                    c.hip_graph = k.auto_graph
+            else:
+                for f in k.flags:
+                    if getattr(c, f.field) != getattr(Config, f.field):
+                        raise ValueError(f"{f.option} belongs to --compress {k.name}")
+            if k.no_ps_form and c.pull_compress == k.name:
+                raise ValueError(f"--pull-compress {k.name}: the {k.name} codec has no "
+                                 f"parameter-server form")
+
     def resolved(self) -> "Config":
         c = dataclasses.replace(self)
         if c.method is not None:
@@ -243,166 +269,11 @@ class Config:
                        f"rotated")
             if why is not None:
                 raise ValueError("--sign-rotate " + c.sign_rotate + " " + why)
-        if c.compress == "mx":
-            # MXFP8 / MXFP4 (compress/oracle.py encode_mx): the all-gather exchange's encode and
-            # fused decode, with that exchange's residual; nothing else has an mx form
-            if c.mx_format is None:
-                c.mx_format = "fp8"
-            why = None
-            if c.mx_format not in ("fp8", "fp4"):
-                why = f"sends fp8 or fp4 elements: --mx-format {c.mx_format!r} is neither"
-            elif c.topology != "allgather":
-                why = (f"runs the all-gather exchange, which keeps its residual: it does not run "
-                       f"with --topology {c.topology} (no ps, sharded or two-stage form is built)")
-            elif c.sync_every > 1:
-                why = ("keeps its residual in the all-gather exchange: it does not run with "
-                       "--sync-every > 1")
-            elif c.select_best:
-                why = ("keeps its residual in the all-gather exchange: it does not run with "
-                       "--select-best")
-            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
-                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
-                       f"sign-compressed momentum (--compress sign)")
-            elif c.pull_compress is not None:
-                why = ("has no parameter-server form: --pull-compress belongs to --topology ps")
-            if why is not None:
-                raise ValueError("--compress mx " + why)
-            if c.error_feedback is None:  # block floating point rounds to nearest: biased
-                c.error_feedback = True
-        elif c.mx_format is not None:
-            raise ValueError("--mx-format belongs to --compress mx")
-        if c.pull_compress == "mx":
-            raise ValueError("--pull-compress mx: the mx codec has no parameter-server form")
-        if c.compress == "tern":
-            # TernGrad (compress/oracle.py encode_tern): the all-gather exchange's encode and fused
-            # decode, every rank's codes decoded with its own scaler; nothing else has a tern form
-            if c.tern_clip is None:
-                c.tern_clip = 2.5
-            why = None
-            if not float(c.tern_clip) >= 0.0:
-                why = f"clips at a multiple of the rms: --tern-clip {c.tern_clip!r} must be >= 0"
-            elif c.topology != "allgather":
-                why = (f"decodes every rank's codes with that rank's scaler in the all-gather "
-                       f"exchange: it does not run with --topology {c.topology} (no ps, sharded or "
-                       f"two-stage form is built)")
-            elif c.sync_every > 1:
-                why = ("is built into the all-gather exchange's every-step path: it does not run "
-                       "with --sync-every > 1")
-            elif c.select_best:
-                why = ("is built into the all-gather exchange's every-step path: it does not run "
-                       "with --select-best")
-            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
-                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
-                       f"sign-compressed momentum (--compress sign)")
-            elif c.pull_compress is not None:
-                why = ("has no parameter-server form: --pull-compress belongs to --topology ps")
-            if why is not None:
-                raise ValueError("--compress tern " + why)
-            if c.error_feedback is None:  # unbiased apart from clipping; the paper runs without
-                c.error_feedback = False
-        elif c.tern_clip is not None:
-            raise ValueError("--tern-clip belongs to --compress tern")
-        if c.pull_compress == "tern":
-            raise ValueError("--pull-compress tern: the tern codec has no parameter-server form")
-        if c.compress == "thresh":
-            # the threshold-search sparsifier (compress/oracle.py encode_thresh): the all-gather
-            # exchange's encode and fused decode with that exchange's plain residual; k per tensor
-            # is --topk-ratio / --topk-dense-below's.  --qsgd-bits / --qsgd-levels and --ef-warmup
-            # none are accepted and unused (the values travel as fp32; there is no warm-up)
-            why = None
-            if c.topology != "allgather":
-                why = (f"runs the all-gather exchange, which keeps its residual: it does not run "
-                       f"with --topology {c.topology} (no ps, sharded or two-stage form is built)")
-            elif c.sync_every > 1:
-                why = ("keeps its residual in the all-gather exchange's every-step path: it does "
-                       "not run with --sync-every > 1")
-            elif c.select_best:
-                why = ("keeps its residual in the all-gather exchange's every-step path: it does "
-                       "not run with --select-best")
-            elif c.pull_compress is not None:
-                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
-            elif c.ef_mode != Config.ef_mode:
-                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
-                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
-            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
-                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
-                       f"sign-compressed momentum (--compress sign)")
-            if why is not None:
-                raise ValueError("--compress thresh " + why)
-            if c.error_feedback is None:  # what lies below the threshold is never sent without it
-                c.error_feedback = True
-        if c.pull_compress == "thresh":
-            raise ValueError("--pull-compress thresh: the thresh codec has no parameter-server "
-                             "form")
-        if c.compress == "intsgd":
-            # IntSGD (parallel/intsgd.py): int8 codes under one model-wide scale, summed by one
-            # all-reduce per bucket; the scale follows the norm of the last SGD update.  Error
-            # feedback either way; --qsgd-bits / --qsgd-levels and --ef-warmup none are accepted
-            # and unused (the wire is int8 with q = floor(127 / world) levels; no warm-up)
-            why = None
-            if c.optimizer != "sgd":
-                why = (f"ties its quantisation step to the last update's norm over lr, which is a "
-                       f"gradient only under SGD (about 1 per element under Adam-like rules, so "
-                       f"the step would dwarf every gradient): it needs --optimizer sgd, not "
-                       f"{c.optimizer!r}")
-            elif c.topology != "allgather":
-                why = (f"sums its codes by all-reduce on every rank: it does not run with "
-                       f"--topology {c.topology} (no ps, sharded or two-stage form is built)")
-            elif c.sync_every > 1:
-                why = ("measures the update of every step for its scale: it does not run with "
-                       "--sync-every > 1")
-            elif c.select_best:
-                why = "sums all workers' codes: it does not run with --select-best"
-            elif c.pull_compress is not None:
-                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
-            elif c.predivide != 1.0:
-                why = ("averages the summed codes with 1 / (alpha N) in its decode: it does not "
-                       "run with --predivide other than 1")
-            elif c.ef_mode != Config.ef_mode:
-                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
-                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
-            elif c.hip_graph in ("full", "segmented"):
-                why = (f"issues its all-reduces between two graphs: --hip-graph {c.hip_graph} is "
-                       f"not supported (auto resolves to split)")
-            if why is not None:
-                raise ValueError("--compress intsgd " + why)
-            if c.error_feedback is None:  # unbiased apart from clipping; the paper runs without
-                c.error_feedback = False
-            if c.hip_graph == "auto":  # graph A -> eager int8 all-reduces -> graph B
-                c.hip_graph = "split"
-        if c.pull_compress == "intsgd":
-            raise ValueError("--pull-compress intsgd: the intsgd codec has no parameter-server "
-                             "form")
+        self._resolve_kinds(c, kinds.RESOLVED_FIRST)
         if c.compress == "vote":
-            # Distributed Lion (parallel/engine.py GradientExchange, vote mode): every rank sends
-            # the sign of its own Lion update, one bit per element and no magnitude, so only Lion
-            # can step on it and nothing that scales or compensates a magnitude applies
-            why = None
-            if c.optimizer != "lion":
-                why = (f"carries no magnitudes, only Lion's sign update can step on it: it needs "
-                       f"--optimizer lion, not {c.optimizer!r}")
-            elif c.topology != "allgather":
-                why = (f"is an all-gather of every rank's bits: it does not run with --topology "
-                       f"{c.topology} (the vote's own sharded form is --vote-exchange twostage)")
-            elif c.sync_every > 1:
-                why = "votes every step: it does not run with --sync-every > 1"
-            elif c.select_best:
-                why = "takes the vote of all workers: it does not run with --select-best"
-            elif c.predivide != 1.0:
-                why = ("counts signs, there is nothing to pre-divide: it does not run with "
-                       "--predivide other than 1")
-            elif c.error_feedback:
-                why = ("sends no magnitude that a residual could compensate: it does not run "
-                       "with --error-feedback")
-            if why is not None:
-                raise ValueError("--compress vote " + why)
-            c.error_feedback = False
-            if c.vote_aggregate is None:
-                c.vote_aggregate = "majority"
+            # the flags of the vote's own exchanges (parallel/engine.py, parallel/twostage.py)
             if c.vote_aggregate not in ("majority", "average"):
                 raise ValueError("--vote-aggregate must be majority or average")
-            if c.vote_exchange is None:
-                c.vote_exchange = "allgather"
             if c.vote_exchange not in ("allgather", "twostage"):
                 raise ValueError("--vote-exchange must be allgather or twostage")
             if c.vote_exchange == "twostage":
@@ -418,10 +289,6 @@ class Config:
                     raise ValueError("--vote-exchange twostage " + why)
                 if c.hip_graph == "auto":  # graph A -> eager collectives + owner step -> graph B
                     c.hip_graph = "split"
-        elif c.vote_aggregate is not None:
-            raise ValueError("--vote-aggregate belongs to --compress vote")
-        elif c.vote_exchange is not None:
-            raise ValueError("--vote-exchange belongs to --compress vote")
         if c.optimizer == "lion":
             try:
                 raw = c.lion_betas or "0.9,0.99"  # a tuple when an already resolved Config
@@ -438,10 +305,10 @@ class Config:
             # only the all-gather exchange keeps a residual (parallel/engine.py
             # GradientExchange); the parameter-server / sharded exchanges have none, so their
             # top-k runs keep the reference's schedule (no EF warm-up) and record no EF
-            c.error_feedback = ((c.compress in ("topk", "topk_qsgd", "sign")
-                                 and c.topology == "allgather")
-                                or (c.compress == "sign" and c.topology == "twostage")
-                                or c.compress in ("powersgd", "sketch"))
+            ef = kinds.KINDS[c.compress].ef_default if c.compress in kinds.KINDS else None
+            c.error_feedback = ef if ef is not None else (
+                (c.compress in ("topk", "topk_qsgd", "sign") and c.topology == "allgather")
+                or (c.compress == "sign" and c.topology == "twostage"))
         if c.optimizer == "onebit_lamb":
             # 1-bit LAMB's compressed stage is the sign codec's all-gather with its residual, as
             # 1-bit Adam's; refused ahead of the exchanges' own checks so the reason names it
@@ -499,87 +366,7 @@ class Config:
                              "not run with --topology ps / sharded, --sync-every > 1 or "
                              "--select-best (those exchanges keep no error feedback); "
                              "--topology twostage is the sign codec's sharded exchange")
-        if c.compress == "powersgd":
-            # PowerSGD (parallel/powersgd.py): two dependent all-reduces of rank-r factors per
-            # bucket, always with its residual, averaged with 1/N inside its kernels
-            why = None
-            if c.powersgd_rank not in (1, 2, 4, 8):
-                why = f"supports ranks 1, 2, 4 and 8, not --powersgd-rank {c.powersgd_rank}"
-            elif c.topology != "allgather":
-                why = (f"averages its factors by all-reduce on every rank: it does not run with "
-                       f"--topology {c.topology}")
-            elif c.sync_every > 1:
-                why = "exchanges every step: it does not run with --sync-every > 1"
-            elif c.select_best:
-                why = "averages all workers: it does not run with --select-best"
-            elif not c.error_feedback:
-                why = ("is a biased compressor that relies on its residual: it does not run with "
-                       "--no-error-feedback")
-            elif c.predivide != 1.0:
-                why = ("averages its factors with 1/N in its kernels: it does not run with "
-                       "--predivide other than 1")
-            elif c.hip_graph in ("full", "segmented"):
-                why = (f"issues its two all-reduces, the orthogonalisation and the back-projection "
-                       f"between two graphs: --hip-graph {c.hip_graph} is not supported (auto "
-                       f"resolves to split)")
-            elif c.optimizer == "onebit_adam":
-                why = ("is not the sign codec: --optimizer onebit_adam exchanges sign-compressed "
-                       "momentum (--compress sign)")
-            if why is not None:
-                raise ValueError("--compress powersgd " + why)
-        elif c.powersgd_rank != Config.powersgd_rank:
-            raise ValueError("--powersgd-rank belongs to --compress powersgd")
-        if c.compress == "sketch":
-            # the count sketch (parallel/sketch.py): two dependent all-reduces per bucket (the
-            # table, then the selected coordinates' values), always with its plain residual,
-            # averaged with 1/N in its decode
-            if c.sketch_rows is None:
-                c.sketch_rows = 3
-            if c.sketch_width is None:
-                c.sketch_width = 2.0
-            why = None
-            if c.sketch_rows not in (1, 3, 5):
-                why = (f"takes the median of an odd number of rows: --sketch-rows must be 1, 3 or "
-                       f"5, not {c.sketch_rows}")
-            elif not float(c.sketch_width) > 0.0:
-                why = (f"sizes its table in columns per selected element: --sketch-width must be "
-                       f"> 0, not {c.sketch_width!r}")
-            elif c.topology != "allgather":
-                why = (f"sums its tables by all-reduce on every rank: it does not run with "
-                       f"--topology {c.topology}")
-            elif c.sync_every > 1:
-                why = "exchanges every step: it does not run with --sync-every > 1"
-            elif c.select_best:
-                why = "sums all workers' sketches: it does not run with --select-best"
-            elif not c.error_feedback:
-                why = ("sends only the heavy coordinates and relies on its residual for the rest: "
-                       "it does not run with --no-error-feedback")
-            elif c.ef_mode != Config.ef_mode:
-                why = (f"keeps a plain residual with the momentum on the receiver: --ef-mode "
-                       f"{c.ef_mode} is not supported (leave --ef-mode unset)")
-            elif c.predivide != 1.0:
-                why = ("averages the summed values with 1/N in its decode: it does not run with "
-                       "--predivide other than 1")
-            elif c.pull_compress is not None:
-                why = "has no parameter-server form: --pull-compress belongs to --topology ps"
-            elif c.hip_graph in ("full", "segmented"):
-                why = (f"issues its two all-reduces, the estimate, the selection and the gather "
-                       f"between two graphs: --hip-graph {c.hip_graph} is not supported (auto "
-                       f"resolves to split)")
-            elif c.optimizer in ("onebit_adam", "onebit_lamb"):
-                why = (f"is not the sign codec: --optimizer {c.optimizer} exchanges "
-                       f"sign-compressed momentum (--compress sign)")
-            if why is not None:
-                raise ValueError("--compress sketch " + why)
-            if c.hip_graph == "auto":  # graph A -> eager all-reduces, select, gather -> graph B
-                c.hip_graph = "split"
-        elif c.sketch_rows is not None:
-            raise ValueError("--sketch-rows belongs to --compress sketch")
-        elif c.sketch_width is not None:
-            raise ValueError("--sketch-width belongs to --compress sketch")
-        if c.pull_compress == "sketch":
-            raise ValueError("--pull-compress sketch: the sketch codec has no parameter-server "
-                             "form")
+        self._resolve_kinds(c, kinds.RESOLVED_LAST)
         if c.optimizer == "onebit_adam":
             # the compressed stage is the sign codec's all-gather with its residual; every option
             # that changes what is exchanged, or that scales it, breaks the momentum's linearity

@@ -291,21 +291,12 @@ class _DistributedOptimizer:
         self.op = op
         self.bpps = max(1, int(backward_passes_per_step))
         codec = Codec("none") if op == Adasum else _as_codec(compression)
-        if codec.kind == "powersgd":
-            # GradientExchange's encode -> one collective -> decode protocol has no place for two
-            # dependent all-reduces (as 1-bit Adam, PowerSGD runs through the trainer only)
-            raise ValueError("Compression.powersgd is not supported by DistributedOptimizer: "
-                             "PowerSGD exchanges two dependent all-reduces per bucket; train "
-                             "with --compress powersgd on the trainer (distributed_nn.py)")
-        if codec.kind == "sketch":
-            raise ValueError("Compression.sketch is not supported by DistributedOptimizer: the "
-                             "count sketch exchanges two dependent all-reduces per bucket; train "
-                             "with --compress sketch on the trainer (distributed_nn.py)")
-        if codec.kind == "intsgd":
-            raise ValueError("Compression.intsgd is not supported by DistributedOptimizer: the "
-                             "wrapped optimizer owns the step, so the update norm IntSGD's scale "
-                             "follows is not visible; train with --compress intsgd on the "
-                             "trainer (distributed_nn.py)")
+        if codec.spec.own_exchange is not None:
+            # GradientExchange's encode -> one collective -> decode protocol has no place for an
+            # exchange of the kind's own (as 1-bit Adam, these run through the trainer only)
+            raise ValueError(f"Compression.{codec.kind} is not supported by DistributedOptimizer: "
+                             f"{codec.spec.own_exchange.no_wrapper}; train with --compress "
+                             f"{codec.kind} on the trainer (distributed_nn.py)")
         self.exchange = GradientExchange(self.flat, self.comm, codec, _OptAdapter(),
                                          overlap=(self.bpps == 1 and op != Adasum),
                                          # scaled sign and round-to-nearest block floating

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from ..compress.codecs import make_codec
+from ..compress.kinds import KINDS
 from ..config import Config
 from ..data import DeviceLoader, load_dataset
 from ..models import build_model, canonical_name, input_shape
@@ -41,6 +42,8 @@ from ..utils.metrics import MetricsLogger, accuracy, byte_summary
 # full-step graph replays on the caller's stream (0: on the graph stream, with an event hop each
 # way per step)
 _SAME_STREAM_REPLAY = os.environ.get("EWDML_GRAPH_SAME_STREAM", "1") != "0"
+# the exchange of every kind that is bound by one of its own (compress/kinds.py own_exchange)
+OWN_EXCHANGES = {"powersgd": PowerSGDExchange, "sketch": SketchExchange, "intsgd": IntSGDExchange}
 
 
 def resolve_device(cfg: Config) -> torch.device:
@@ -177,9 +180,11 @@ class Trainer:
         # (and PowerSGD, whose project launch reads the flat gradient buffer, and the two-stage
         # vote, whose push encode does)
         vote_ts = cfg.compress == "vote" and cfg.vote_exchange == "twostage"
+        kind = KINDS[cfg.compress]
+        own = kind.own_exchange is not None  # powersgd, sketch, intsgd: compress/kinds.py
         ptr_grads = (self.cuda and cfg.topology == "allgather"
                      # the sketch's stage and IntSGD's encode and dense first step too
-                     and cfg.compress not in ("powersgd", "sketch", "intsgd")
+                     and not own
                      and not vote_ts
                      and os.environ.get("EWDML_GRAD_VIEWS") != "1")
         bf16_params = (ptr_grads and cfg.amp == "bf16" and cfg.param_dtype == "auto"
@@ -196,8 +201,7 @@ class Trainer:
         # here because the segmented step wants smaller buckets
         self.graph_plan = None
         if (cfg.hip_graph == "auto" and self.cuda and not cfg.sync_debug
-                # always split graphs (below)
-                and cfg.compress not in ("powersgd", "sketch", "intsgd")
+                and not own  # always split graphs (below)
                 and cfg.topology == "allgather" and cfg.sync_every == 1 and not cfg.select_best):
             # EWDML_PLAN_AS_WORLD (test hook): plan as if the job had that many ranks, so the
             # N > 1 decision runs end to end on a one-GPU box (world of one, real communicator)
@@ -250,14 +254,13 @@ class Trainer:
         # exchange ---------------------------------------------------------------------------------
         ckw = dict(ratio=cfg.topk_ratio, levels=cfg.qsgd_levels, bits=cfg.qsgd_bits,
                    norm=cfg.qsgd_norm, seed=cfg.seed, dense_below=cfg.topk_dense_below)
-        if cfg.compress == "vote":
-            ckw["aggregate"] = cfg.vote_aggregate
+        if own:  # only what the kind itself reads: the seed, a density if it has one, its flags
+            ckw = dict(seed=cfg.seed)
+            if kind.density:
+                ckw.update(ratio=cfg.topk_ratio, dense_below=cfg.topk_dense_below)
+        ckw.update({f.kw: getattr(cfg, f.field) for f in kind.flags if f.kw is not None})
         if cfg.sign_rotate != "none":
             ckw["rotate"] = cfg.sign_rotate
-        if cfg.compress == "mx":
-            ckw["fmt"] = cfg.mx_format
-        if cfg.compress == "tern":
-            ckw["clip"] = cfg.tern_clip
         if cfg.topk_warmup and cfg.topology != "allgather":
             raise ValueError("--topk-warmup needs the all-to-all topology")
         self._stages = ()  # 1-bit Adam: (dense warm-up exchange, sign exchange)
@@ -270,24 +273,12 @@ class Trainer:
                                        else None)
         elif cfg.topology == "sharded":
             self.exchange = ShardedPSExchange(self.flat, self.comm, cfg.compress, self.opt, **ckw)
-        elif cfg.compress == "powersgd":
-            self.exchange = PowerSGDExchange(self.flat, self.comm,
-                                             make_codec("powersgd", seed=cfg.seed,
-                                                        rank=cfg.powersgd_rank), self.opt,
-                                             clipper=self.clipper)
-        elif cfg.compress == "sketch":
-            self.exchange = SketchExchange(self.flat, self.comm,
-                                           make_codec("sketch", seed=cfg.seed,
-                                                      ratio=cfg.topk_ratio,
-                                                      dense_below=cfg.topk_dense_below,
-                                                      rows=cfg.sketch_rows,
-                                                      width=cfg.sketch_width), self.opt,
-                                           clipper=self.clipper)
-        elif cfg.compress == "intsgd":
-            self.exchange = IntSGDExchange(self.flat, self.comm,
-                                           make_codec("intsgd", seed=cfg.seed), self.opt,
-                                           clipper=self.clipper,
-                                           error_feedback=cfg.error_feedback)
+        elif own:
+            # IntSGD's residual is optional; PowerSGD and the sketch always keep theirs
+            ekw = {"error_feedback": cfg.error_feedback} if cfg.compress == "intsgd" else {}
+            self.exchange = OWN_EXCHANGES[cfg.compress](
+                self.flat, self.comm, make_codec(cfg.compress, **ckw), self.opt,
+                clipper=self.clipper, **ekw)
         elif vote_ts:
             self.exchange = TwoStageVoteExchange(self.flat, self.comm,
                                                  make_codec(cfg.compress, **ckw), self.opt,
@@ -361,15 +352,10 @@ class Trainer:
                     # 1-bit Adam's dense warm-up runs split too: one graph mode for both stages
                     or cfg.topology == "twostage"
                     or isinstance(self.exchange, TwoStageVoteExchange)
-                    # PowerSGD: graph A = ..., project -> eager all-reduces, orthogonalise and
-                    # back-project -> graph B = reconstruct + step
-                    or isinstance(self.exchange, PowerSGDExchange)
-                    # the count sketch: graph A = ..., stage, table -> eager all-reduces,
-                    # estimate, select and gather -> graph B = decode + step
-                    or isinstance(self.exchange, SketchExchange)
-                    # IntSGD: graph A = ..., encode -> eager int8 all-reduces -> graph B = decode
-                    # + step and the scale launch
-                    or isinstance(self.exchange, IntSGDExchange))
+                    # the kinds with an exchange of their own: graph A = ..., project / stage +
+                    # table / encode -> eager all-reduces and what lies between them -> graph B =
+                    # reconstruct or decode + step (IntSGD: and the scale launch)
+                    or isinstance(self.exchange, tuple(OWN_EXCHANGES.values())))
         self.ps_graph = ps_split
         if self.graph_mode == "auto":
             # graphs wherever the step can be captured: the all-to-all exchange, local SGD's
@@ -379,7 +365,7 @@ class Trainer:
             # update); the k-of-n arrival polling stays eager
             if self.graph_plan is not None:
                 self.graph_mode = self.graph_plan["mode"]
-            elif cfg.topology == "twostage" or cfg.compress in ("powersgd", "sketch", "intsgd"):
+            elif cfg.topology == "twostage" or own:
                 self.graph_mode = "split"
             elif isinstance(self.exchange, GradientExchange) or self.local_sgd:
                 self.graph_mode = "full"
