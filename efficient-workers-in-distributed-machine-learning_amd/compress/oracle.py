@@ -1698,3 +1698,125 @@ def muon_apply(p, mom, g, tensors, lr, momentum, weight_decay, nesterov, aux_rat
         decay = float(f32(1.0) - lr32 * f32(wd))
         step = float(lr32 * f32(np.sqrt(f32(max(1.0, rows / cols)))))
         pt.copy_(pt * decay - o * step)
+
+
+# ---------------------------------------------------------------------------------------------
+# 8-bit Adam (Dettmers et al., "8-bit Optimizers via Block-wise Quantization", ICLR 2022): both
+# moments as one byte per element plus one fp32 absmax per block.  The definition of
+# ``ops/csrc/adam8.hip`` and the CPU path of ``optim.FlatAdam8bit``.
+#
+# A block is ADAM8_BLOCK = 256 consecutive elements of one tensor counted from its first element
+# (the last may be short); a chunk of CHUNK elements holds 32, so block j of a tensor whose first
+# chunk is global chunk c owns absmax slot 32 c + j.  Quantise: ``x = value / absmax`` (fp32),
+# ``code = #{k : mid[k] < x}``; a block with absmax 0 takes the code of 0.0; a ``v > 0`` takes
+# code 1 at least (it must not dequantise to 0: sqrt(v) = 0 would step by m / eps).  Dequantise:
+# ``map[code] * absmax``.  fp32 throughout, every product and sum rounded on its own, the square
+# root correctly rounded (numpy's; ``torch.sqrt`` on the CPU is not).
+# ---------------------------------------------------------------------------------------------
+ADAM8_BLOCK = 256
+ADAM8_SLOTS = CHUNK // ADAM8_BLOCK  # absmax slots per chunk
+ADAM8_ZERO = 127  # code of 0.0 in the signed map (of the unsigned map: 0)
+_ADAM8_BOOKS = []
+
+
+def _adam8_map(signed: bool) -> torch.Tensor:
+    """A dynamic-tree map in float64: for decade i = 0..6, n_i equal bins on [0.1, 1] (n_i = 2^i
+    signed, 2^(i+1) unsigned), each bin's mean scaled by 10^(i-6); plus 0 and 1; the signed map
+    with both signs of every mean (so +1 has no partner).  Ascending, 256 entries."""
+    vals = [0.0, 1.0]
+    for i in range(7):
+        n = 2 ** i if signed else 2 ** (i + 1)
+        edges = 0.1 + 0.9 * np.arange(n + 1) / n
+        means = (edges[:-1] + edges[1:]) / 2.0 * 10.0 ** (i - 6)
+        vals += means.tolist()
+        if signed:
+            vals += (-means).tolist()
+    out = torch.tensor(sorted(vals), dtype=torch.float64)
+    assert out.numel() == 256
+    return out
+
+
+def adam8_codebooks():
+    """(map_m, mid_m, map_v, mid_v): the signed map of the first moment and the unsigned map of
+    the second (fp32 [256], ascending) and their midpoints (fp32 [255]: the float64 mean of
+    neighbouring entries, rounded once)."""
+    if not _ADAM8_BOOKS:
+        for signed in (True, False):
+            m32 = _adam8_map(signed).to(torch.float32)
+            m64 = m32.to(torch.float64)
+            _ADAM8_BOOKS.extend([m32, ((m64[:-1] + m64[1:]) / 2.0).to(torch.float32)])
+        assert float(_ADAM8_BOOKS[0][ADAM8_ZERO]) == 0.0 and float(_ADAM8_BOOKS[2][0]) == 0.0
+    return tuple(_ADAM8_BOOKS)
+
+
+def adam8_lr_step(lr, beta1, beta2, step) -> float:
+    """Adam's step size of the 1-based ``step`` from the fp32-rounded betas, in double: what the
+    kernel's device-step path computes (``adam_apply`` above does the same)."""
+    import math
+    b1, b2 = float(np.float32(beta1)), float(np.float32(beta2))
+    return lr * math.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
+
+
+def adam8_state(numel: int, total_chunks: int, device="cpu"):
+    """Fresh (code_m, code_v, absmax_m, absmax_v): every moment 0."""
+    return (torch.full((numel,), ADAM8_ZERO, dtype=torch.uint8, device=device),
+            torch.zeros(numel, dtype=torch.uint8, device=device),
+            torch.zeros(ADAM8_SLOTS * total_chunks, dtype=torch.float32, device=device),
+            torch.zeros(ADAM8_SLOTS * total_chunks, dtype=torch.float32, device=device))
+
+
+def _adam8_quantize(x, amax, mid, zero):
+    """Codes of the [blocks, 256] values ``x`` under the per-block ``amax``."""
+    code = torch.bucketize(x / amax[:, None], mid)
+    return torch.where(amax[:, None] == 0, torch.full_like(code, zero), code)
+
+
+def adam8_apply(p, code_m, code_v, absmax_m, absmax_v, g, blocks, lr, beta1, beta2, eps,
+                weight_decay, step, lr_step=None):
+    """One 8-bit Adam step in place on the flat views ``p`` (fp32), ``code_m`` / ``code_v``
+    (uint8, indexed like ``p``) and the range's ``absmax_m`` / ``absmax_v`` with the already scaled
+    fp32 gradient ``g``.  ``blocks``: one ``(offset, numel, slot0)`` per tensor of the range, its
+    block j owning absmax slot ``slot0 + j``.  ``step`` is 1-based; ``lr_step`` overrides
+    :func:`adam8_lr_step`.  ``ew_adam``'s rule on the dequantised moments, the parameter stepping
+    from the unquantised new ones::
+
+        g = g + wd * p                        (wd != 0)
+        m = m * b1 + (1 - b1) * g             v = v * b2 + (1 - b2) * (g * g)
+        p = p - lr_step * (m / (sqrt(v) + eps))"""
+    map_m, mid_m, map_v, mid_v = adam8_codebooks()
+    f32 = torch.float32
+    one = torch.ones((), dtype=f32)
+    b1, b2 = torch.tensor(beta1, dtype=f32), torch.tensor(beta2, dtype=f32)
+    c1, c2 = one - b1, one - b2
+    eps, wd = torch.tensor(eps, dtype=f32), torch.tensor(weight_decay, dtype=f32)
+    ls = torch.tensor(adam8_lr_step(lr, beta1, beta2, step) if lr_step is None else lr_step,
+                      dtype=f32)
+    B = ADAM8_BLOCK
+    for off, n, slot0 in blocks:
+        nb = (n + B - 1) // B
+        pad = nb * B - n
+
+        def rows(x, fill=0):
+            return torch.nn.functional.pad(x[off:off + n], (0, pad), value=fill).view(nb, B)
+
+        sl = slice(slot0, slot0 + nb)
+        m = map_m[rows(code_m, ADAM8_ZERO).long()] * absmax_m[sl, None]
+        v = map_v[rows(code_v).long()] * absmax_v[sl, None]
+        pt, gt = rows(p), rows(g.to(f32))
+        if float(wd) != 0.0:
+            gt = gt + wd * pt
+        m = m * b1 + c1 * gt
+        v = v * b2 + c2 * (gt * gt)
+        d = torch.from_numpy(np.sqrt(v.numpy())) + eps
+        p[off:off + n] = (pt - ls * (m / d)).view(-1)[:n]
+        if pad:
+            m.view(-1)[n:] = 0.0
+            v.view(-1)[n:] = 0.0
+        am, av = m.abs().amax(dim=1), v.amax(dim=1)
+        cm = _adam8_quantize(m, am, mid_m, ADAM8_ZERO)
+        cv = _adam8_quantize(v, av, mid_v, 0)
+        cv = torch.where((v > 0) & (cv == 0), torch.ones_like(cv), cv)
+        code_m[off:off + n] = cm.view(-1)[:n].to(torch.uint8)
+        code_v[off:off + n] = cv.view(-1)[:n].to(torch.uint8)
+        absmax_m[sl] = am
+        absmax_v[sl] = av

@@ -123,10 +123,10 @@ class Config:
     sync_bn: bool = False  # broadcast BN running stats from rank 0 at every checkpoint/eval
     # ---- optimizer -------------------------------------------------------------------------------
     # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
-    # onebit_lamb (1-bit LAMB) |
+    # onebit_lamb (1-bit LAMB) | adam8bit (8-bit Adam: block-wise quantised moments) |
     # lion: optim/flat.py
     optimizer: str = "sgd"
-    adam_eps: float = 1e-8  # epsilon of adam / amsgrad / onebit_adam
+    adam_eps: float = 1e-8  # epsilon of adam / amsgrad / adam8bit / onebit_adam
     # onebit_adam / onebit_lamb: dense steps before the variance is frozen and the sign-compressed
     # momentum exchange starts (required, >= 1)
     onebit_warmup_steps: Optional[int] = None
@@ -559,7 +559,7 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
-      choices=["sgd", "adam", "amsgrad", "onebit_adam", "lars", "lamb", "lion",
+      choices=["sgd", "adam", "amsgrad", "adam8bit", "onebit_adam", "lars", "lamb", "lion",
                "onebit_lamb", "muon"])
     a("--muon-ns-steps", type=int, default=None)
     a("--muon-ns-dtype", type=str, default=None, choices=["fp32", "bf16"])

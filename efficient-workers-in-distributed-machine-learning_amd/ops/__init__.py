@@ -1511,6 +1511,97 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
     C.layerwise_apply(args)
 
 
+# 8-bit Adam (csrc/adam8.hip): absmax slots per chunk and the floats of the quantiser's table
+ADAM8_SLOTS = 32
+ADAM8_TABLE_FLOATS = 1088  # EW_ADAM8_TABLE_FLOATS in csrc/ewdml_ops.h
+_ADAM8_TABLES = {}
+
+
+def adam8_table(device) -> torch.Tensor:
+    """The kernel's table (fp32, built once per device) from the oracle's codebooks: the signed
+    map, the unsigned map, their midpoints (255 entries, then +inf), and per map the closed-form
+    quantiser's 8 decade rows ``{lower edge, bins per unit, first rank, 0}``: row 0 serves values
+    below 1e-7 (rank 0), row j >= 1 decade i = j - 1 = [10^(i-7), 10^(i-6)] of ``n_i`` bins, whose
+    first mean has rank ``2^i`` among the signed map's positive entries and ``2^(i+1) - 1`` in the
+    unsigned map."""
+    key = torch.device(device)
+    t = _ADAM8_TABLES.get(key)
+    if t is None:
+        from ..compress import oracle
+
+        map_m, mid_m, map_v, mid_v = oracle.adam8_codebooks()
+        inf = torch.full((1,), float("inf"))
+        dec = []
+        for signed in (True, False):
+            rows = [[0.0, 0.0, 0.0, 0.0]]
+            for i in range(7):
+                n = 2 ** i if signed else 2 ** (i + 1)
+                rows.append([10.0 ** (i - 7), n / (0.9 * 10.0 ** (i - 6)),
+                             float(n if signed else n - 1), 0.0])
+            dec.append(torch.tensor(rows, dtype=torch.float32).view(-1))
+        t = torch.cat([map_m, map_v, mid_m, inf, mid_v, inf] + dec).to(key)
+        assert t.numel() == ADAM8_TABLE_FLOATS
+        _ADAM8_TABLES[key] = t
+    return t
+
+
+class Adam8Plan:
+    """Device tables of one flat range (a bucket or the whole model) for 8-bit Adam: the range's
+    ``BucketPlan`` chunk table and its views of the two absmax arrays (fp32, ``ADAM8_SLOTS``
+    entries per chunk row: block j of row c owns slot ``32 c + j``)."""
+
+    def __init__(self, plan, absmax_m, absmax_v):
+        C = plan.num_chunks
+        _check(absmax_m, torch.float32, "absmax_m", align=4)
+        _check(absmax_v, torch.float32, "absmax_v", align=4)
+        if absmax_m.numel() != ADAM8_SLOTS * C or absmax_v.numel() != ADAM8_SLOTS * C:
+            raise ValueError(f"8-bit Adam plan of {C} chunks: absmax_m and absmax_v must hold "
+                             f"{ADAM8_SLOTS * C} entries each")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        if plan.length >= 1 << 31:
+            raise ValueError("flat range of 2^31 elements or more")
+        self.plan = plan
+        self.absmax_m, self.absmax_v = absmax_m, absmax_v
+        self.chunks = plan.chunk_table(absmax_m.device)
+        self.table = adam8_table(absmax_m.device)
+
+
+def adam8_step(plan: Adam8Plan, param, grad, code_m, code_v, *, lr_step=0.0, betas=(0.9, 0.999),
+               eps=1e-8, weight_decay=0.0, grad_scale=1.0, shadow=None, step=None, lr=0.0,
+               lr_tensor=None):
+    """One 8-bit Adam step of the flat range ``plan`` describes, in one launch
+    (``csrc/adam8.hip``; bitwise ``compress/oracle.py adam8_apply`` on ``grad * grad_scale`` with
+    a host ``lr_step``).  ``code_m`` / ``code_v``: the uint8 moments, indexed like ``param``.
+    ``step`` (int32 device tensor, optional): the kernel reads t = step + 1 and derives
+    ``lr_step`` from ``lr`` / ``lr_tensor`` on the device, as :func:`adam_flat` does."""
+    C = require()
+    n = plan.plan.length
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check(code_m, torch.uint8, "code_m", align=4)
+    _check(code_v, torch.uint8, "code_v", align=4)
+    for s, nm in ((param, "param"), (grad, "grad"), (code_m, "code_m"), (code_v, "code_v")):
+        if s.numel() < n:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {n}")
+    _check_shadow(plan, shadow)
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    b1, b2 = betas
+    C.adam8_step(_args(
+        C.Adam8Args, param=_ptr(param), grad=_ptr(grad), code_m=_ptr(code_m),
+        code_v=_ptr(code_v), absmax_m=_ptr(plan.absmax_m), absmax_v=_ptr(plan.absmax_v),
+        shadow=_ptr(shadow), chunks=_ptr(plan.chunks), table=_ptr(plan.table),
+        num_chunks=plan.plan.num_chunks, grad_dtype=_GDT[grad.dtype], lr_step=float(lr_step),
+        beta1=float(b1), beta2=float(b2), eps=float(eps), weight_decay=float(weight_decay),
+        grad_scale=float(grad_scale), step=_ptr(step), lr=float(lr), lr_ptr=_lrp(lr_tensor),
+        stream=_stream()))
+
+
 # Muon (csrc/muon.hip): output tile edge and k-step of its products; the gram's long dimension is
 # cut into slabs of about MUON_SLAB_K columns (a multiple of MUON_K), MUON_MAX_SPLITS at the most
 MUON_TILE, MUON_K = 64, 32

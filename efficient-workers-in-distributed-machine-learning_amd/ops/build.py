@@ -20,9 +20,11 @@ HIP_FLAGS = [
     "-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off",
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
 ]
-# per-source additions: muon.hip is built without the packed fp32 instructions
+# per-source additions: muon.hip and adam8.hip are built without the packed fp32 instructions
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {
-    "muon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "muon.hip": _NO_PACKED_FP32,
+    "adam8.hip": _NO_PACKED_FP32,
 }
 
 

@@ -191,6 +191,10 @@ PYBIND11_MODULE(_C, m) {
           F(partials) F(ratio) F(stream) F(num_chunks) F(kind) F(grad_dtype) F(lr) F(beta1)
           F(beta2) F(eps) F(weight_decay) F(grad_scale) F(eta) F(momentum) F(dampening) F(bc1)
           F(bc2) F(beta1d) F(beta2d) F(nesterov) F(first) F(step) F(lr_ptr))
+  EW_ARGS(Adam8Args,
+          F(param) F(grad) F(code_m) F(code_v) F(absmax_m) F(absmax_v) F(shadow) F(chunks)
+          F(table) F(stream) F(num_chunks) F(grad_dtype) F(lr_step) F(beta1) F(beta2) F(eps)
+          F(weight_decay) F(grad_scale) F(step) F(lr) F(lr_ptr))
   EW_ARGS(MuonArgs,
           F(param) F(mom) F(grad) F(shadow) F(chunks) F(xoff) F(partials) F(stream) F(mats)
           F(items) F(x_in) F(x_out) F(a_buf) F(b_buf) F(slabs) F(tickets) F(num_chunks)
@@ -250,6 +254,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("vote_reduce", &ew_vote_reduce);
   m.def("layerwise_stage", &ew_layerwise_stage);
   m.def("layerwise_apply", &ew_layerwise_apply);
+  m.def("adam8_step", &ew_adam8_step);
   m.def("muon_momentum", &ew_muon_momentum);
   m.def("muon_gram", &ew_muon_gram);
   m.def("muon_poly", &ew_muon_poly);

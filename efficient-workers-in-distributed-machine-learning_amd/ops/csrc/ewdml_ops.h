@@ -436,6 +436,23 @@ struct LayerwiseArgs {
 void ew_layerwise_stage(const LayerwiseArgs& a);
 void ew_layerwise_apply(const LayerwiseArgs& a);
 
+// 8-bit Adam over a flat range (adam8.hip): chunks is the range's BucketPlan chunk table; param,
+// grad, code_m, code_v (uint8) and shadow its views, indexed alike.  absmax_m / absmax_v fp32
+// [32 * num_chunks]: slot 32 c + j belongs to the 256-element block j of chunk c.  table fp32
+// [EW_ADAM8_TABLE_FLOATS]: the signed map, the unsigned map, their midpoints (255 + one pad each)
+// and the quantiser's two decade tables (8 x {lower edge, bins per unit, first rank, 0}).
+#define EW_ADAM8_TABLE_FLOATS 1088
+struct Adam8Args {
+  uintptr_t param, grad, code_m, code_v, absmax_m, absmax_v, shadow, chunks, table, stream;
+  int num_chunks;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  float lr_step, beta1, beta2, eps, weight_decay, grad_scale;
+  uintptr_t step;    // int32 device step counter (nullable: use lr_step as given)
+  double lr;         // base lr for the device-side bias correction
+  uintptr_t lr_ptr;  // nullable device fp32 base lr (overrides lr)
+};
+void ew_adam8_step(const Adam8Args& a);
+
 // Muon over a flat range (muon.hip; ops.MuonPlan builds the tables).  The momentum launch walks
 // the range's chunk table (param, mom, grad, shadow: its views; xoff int32[T]: a matrix's offset in
 // the X workspace, -1 for a vector) and writes u into x_out and the chunk sums of u^2 into

@@ -187,6 +187,106 @@ class FlatAdam(_LrMixin):
         self.lr = sd.get("lr", self.lr)
 
 
+class FlatAdam8bit(_LrMixin):
+    """8-bit Adam (Dettmers et al., ICLR 2022): :class:`FlatAdam`'s rule with both moments kept
+    as one byte per element (``code_m`` / ``code_v``, indexed like ``flat.data``) plus one fp32
+    absmax per 256-element block of a tensor (``absmax_m`` / ``absmax_v``, 32 slots per global
+    8192-element chunk), about 2.03 B of state per element instead of 8
+    (``compress/oracle.py adam8_apply`` defines the format).  A step covers one bucket or the
+    whole model, as blocks are counted per tensor: one HIP kernel on the GPU
+    (``ops.adam8_step``), the torch oracle on the CPU.  No AMSGrad."""
+    fusable = False
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        from ..compress.plan import CHUNK
+
+        self.flat = flat
+        dev = flat.data.device
+        self._init_lr(lr, dev)
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        self._chunk0 = [0]
+        for p in flat.params:
+            self._chunk0.append(self._chunk0[-1] + (p.numel() + CHUNK - 1) // CHUNK)
+        self.code_m, self.code_v, self.absmax_m, self.absmax_v = oracle.adam8_state(
+            flat.data.numel(), self._chunk0[-1], dev)
+        # flat ranges a step may cover -> (first tensor, tensors): the whole model and each bucket
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        self._plans = {}
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            raise ValueError(f"an 8-bit Adam step covers a bucket or the whole model (blocks are "
+                             f"per tensor), not the range [{start}, {start + length})") from None
+
+    def _plan(self, start, length):
+        """The range's device plan (built once): its chunk table and absmax views."""
+        ap = self._plans.get((start, length))
+        if ap is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            s0, s1 = (oracle.ADAM8_SLOTS * self._chunk0[t] for t in (t0, t0 + nt))
+            ap = ops.Adam8Plan(plan, self.absmax_m[s0:s1], self.absmax_v[s0:s1])
+            self._plans[(start, length)] = ap
+        return ap
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state (the codes and the absmax arrays)."""
+        return sum(t.numel() * t.element_size()
+                   for t in (self.code_m, self.code_v, self.absmax_m, self.absmax_v))
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        t0, nt = self._range(start, length)
+        sl = slice(start, start + length)
+        p, cm, cv = self.flat.data[sl], self.code_m[sl], self.code_v[sl]
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.adam8_step(self._plan(start, length), p, grad, cm, cv,
+                           lr_step=oracle.adam8_lr_step(self.lr, *self.betas, self.steps + 1),
+                           betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                           grad_scale=grad_scale, shadow=sh, step=self.step_t, lr=self.lr,
+                           lr_tensor=self.lr_t)
+            return
+        blocks = [(self.flat.offsets[t] - start, self.flat.params[t].numel(),
+                   oracle.ADAM8_SLOTS * self._chunk0[t]) for t in range(t0, t0 + nt)]
+        g = grad.to(torch.float32) * grad_scale
+        oracle.adam8_apply(p, cm, cv, self.absmax_m, self.absmax_v, g, blocks, self.lr,
+                           *self.betas, self.eps, self.weight_decay, self.steps + 1)
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    def state_dict(self):
+        return {"kind": "adam8bit", "code_m": self.code_m, "code_v": self.code_v,
+                "absmax_m": self.absmax_m, "absmax_v": self.absmax_v, "steps": self.steps,
+                "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        for k in ("code_m", "code_v", "absmax_m", "absmax_v"):
+            getattr(self, k).copy_(sd[k])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+
+
 class FlatOnebitAdam(FlatAdam):
     """1-bit Adam (Tang et al., ICML 2021; DeepSpeed ``OnebitAdam``).  Steps 1..``freeze_step`` are
     :class:`FlatAdam` on the dense averaged gradient.  From then on (``frozen``) ``exp_avg_sq`` is
@@ -698,6 +798,12 @@ def make_optimizer(name, flat, **kw):
         return FlatAdam(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
                         eps=kw.get("eps", 1e-8),
                         amsgrad=(name == "amsgrad") or kw.get("amsgrad", False))
+    if name == "adam8bit":
+        if kw.get("amsgrad", False):
+            raise ValueError("8-bit Adam has no AMSGrad: a running maximum of the second moment "
+                             "would be a third quantised state")
+        return FlatAdam8bit(flat, lr=kw.get("lr", 1e-3),
+                            weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8))
     if name == "lion":
         return FlatLion(flat, lr=kw.get("lr", 1e-4), betas=kw.get("betas") or (0.9, 0.99),
                         weight_decay=kw.get("weight_decay", 0.0))
