@@ -1820,3 +1820,69 @@ def adam8_apply(p, code_m, code_v, absmax_m, absmax_v, g, blocks, lr, beta1, bet
         code_v[off:off + n] = cv.view(-1)[:n].to(torch.uint8)
         absmax_m[sl] = am
         absmax_v[sl] = av
+
+
+# ---------------------------------------------------------------------------------------------
+# Adafactor (Shazeer and Stern, "Adafactor: Adaptive Learning Rates with Sublinear Memory Cost",
+# ICML 2018) with an external learning rate.  The definition of ``ops/csrc/adafactor.hip`` (up to
+# the order of the sums) and the CPU path of ``optim.FlatAdafactor``.
+#
+# ``p`` / ``g`` / ``mom`` are views of one flat range, ``tensors`` its ``(offset, numel, rows, s0,
+# s1)`` rows.  ``rows = shape[0]`` of a factored tensor (``ndim >= 2``, viewed as ``[n, m] = [rows,
+# numel / rows]``): its statistics are ``row[s0:s0 + n]`` and ``col[s1:s1 + m]``.  ``rows = 0``: a
+# vector with a full second moment ``v[s0:s0 + numel]``.  With q = g^2 + 1e-30::
+#
+#     R = R b2 + (1 - b2) mean_j q      C = C b2 + (1 - b2) mean_i q      b2 = 1 - t^-decay
+#     u = (g / sqrt(R / mean R)) / sqrt(C)           (a vector: v = v b2 + (1 - b2) q, u = g / sqrt v)
+#     a = alpha / max(1, RMS(u) / clip)   alpha = lr max(1e-3, RMS(p)) with scale_parameter, else lr
+#     step = a u, or with beta1 > 0 mom = mom beta1 + (1 - beta1) a u;   p = p (1 - alpha wd) - step
+#
+# The scalars are formed in double from the fp32 hyper-parameters and rounded to fp32 once; the
+# state's dtype is the arithmetic's (fp64 state: the tests' reference, with the same fp32 scalars).
+# ---------------------------------------------------------------------------------------------
+ADAFACTOR_EPS1, ADAFACTOR_EPS2 = 1e-30, 1e-3
+
+
+def adafactor_beta2(step: int, decay: float = 0.8):
+    """``(b2, 1 - b2)`` of the 1-based ``step``: formed in double, each rounded to fp32."""
+    b2 = 1.0 - float(step) ** -float(decay)
+    return float(np.float32(b2)), float(np.float32(1.0 - b2))
+
+
+def adafactor_apply(p, row, col, v, mom, g, tensors, lr, step, beta1=0.0, clip=1.0,
+                    scale_parameter=False, weight_decay=0.0, decay=0.8):
+    """One Adafactor step in place with the already scaled gradient ``g``; ``mom`` (indexed like
+    ``p``) is None when ``beta1 == 0``."""
+    import math
+    f32 = np.float32
+    b2, c2 = adafactor_beta2(step, decay)
+    lr32, wd, b1, d = (float(f32(x)) for x in (lr, weight_decay, beta1, clip))
+    c1, eps1 = float(f32(1.0 - b1)), float(f32(ADAFACTOR_EPS1))
+    g = g.to(p.dtype)
+    for off, numel, n, s0, s1 in tensors:
+        pt, gt = p[off:off + numel], g[off:off + numel]
+        if n:
+            m = numel // n
+            g2 = gt.reshape(n, m)
+            q = g2 * g2 + eps1
+            R, C = row[s0:s0 + n], col[s1:s1 + m]
+            R.copy_(R * b2 + q.mean(dim=1) * c2)
+            C.copy_(C * b2 + q.mean(dim=0) * c2)
+            mean_r = (R.double().sum() / n).to(p.dtype)
+            u = ((g2 * (1.0 / (R / mean_r).sqrt())[:, None])
+                 * (1.0 / C.sqrt())[None, :]).reshape(-1)
+        else:
+            vt = v[s0:s0 + numel]
+            vt.copy_(vt * b2 + (gt * gt + eps1) * c2)
+            u = gt / vt.sqrt()
+        den = max(1.0, math.sqrt(float((u.double() ** 2).sum()) / numel) / d)
+        alpha = lr32
+        if scale_parameter:
+            alpha = float(f32(lr32 * max(ADAFACTOR_EPS2, math.sqrt(
+                float((pt.double() ** 2).sum()) / numel))))
+        s = u * float(f32(alpha / den))
+        if mom is not None:
+            mt = mom[off:off + numel]
+            mt.copy_(mt * b1 + s * c1)
+            s = mt
+        pt.copy_(pt * float(f32(1.0 - alpha * wd)) - s)

@@ -124,7 +124,7 @@ class Config:
     # ---- optimizer -------------------------------------------------------------------------------
     # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
     # onebit_lamb (1-bit LAMB) | adam8bit (8-bit Adam: block-wise quantised moments) |
-    # lion: optim/flat.py
+    # lion | muon | adafactor (factored second moments): optim/flat.py
     optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / adam8bit / onebit_adam
     # onebit_adam / onebit_lamb: dense steps before the variance is frozen and the sign-compressed
@@ -137,6 +137,12 @@ class Config:
     muon_ns_steps: Optional[int] = None
     muon_ns_dtype: Optional[str] = None
     muon_aux_lr: Optional[float] = None
+    # adafactor (factored second moments on every dim >= 2 tensor, external lr): first-moment
+    # decay in [0, 1) (None: 0, no first moment), the update's RMS clip threshold (None: 1.0), and
+    # the step scaled by max(1e-3, RMS(p)) per tensor
+    adafactor_beta1: Optional[float] = None
+    adafactor_clip: Optional[float] = None
+    adafactor_scale_parameter: bool = False
     # lion: "B1,B2" (None: 0.9,0.99), each in [0, 1); resolved to a tuple of two floats
     lion_betas: Optional[str] = None
     # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
@@ -408,6 +414,19 @@ class Config:
                             ("--muon-aux-lr", c.muon_aux_lr)):
                 if v is not None:
                     raise ValueError(f"{flag} belongs to --optimizer muon")
+        if c.optimizer == "adafactor":
+            c.adafactor_beta1 = 0.0 if c.adafactor_beta1 is None else float(c.adafactor_beta1)
+            c.adafactor_clip = 1.0 if c.adafactor_clip is None else float(c.adafactor_clip)
+            if not 0.0 <= c.adafactor_beta1 < 1.0:
+                raise ValueError("--adafactor-beta1 must lie in [0, 1)")
+            if not c.adafactor_clip > 0:
+                raise ValueError("--adafactor-clip must be > 0")
+        else:
+            for flag, v in (("--adafactor-beta1", c.adafactor_beta1),
+                            ("--adafactor-clip", c.adafactor_clip),
+                            ("--adafactor-scale-parameter", c.adafactor_scale_parameter or None)):
+                if v is not None:
+                    raise ValueError(f"{flag} belongs to --optimizer adafactor")
         if c.clip_grad_norm is not None:
             # the clip scales every gradient of the rank once, after backward and before any
             # encode (parallel/clip.py); the exchanges below do not take a clipper
@@ -560,7 +579,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
       choices=["sgd", "adam", "amsgrad", "adam8bit", "onebit_adam", "lars", "lamb", "lion",
-               "onebit_lamb", "muon"])
+               "onebit_lamb", "muon", "adafactor"])
+    a("--adafactor-beta1", type=float, default=None)
+    a("--adafactor-clip", type=float, default=None)
+    a("--adafactor-scale-parameter", action="store_true")
     a("--muon-ns-steps", type=int, default=None)
     a("--muon-ns-dtype", type=str, default=None, choices=["fp32", "bf16"])
     a("--muon-aux-lr", type=float, default=None)

@@ -1602,6 +1602,160 @@ def adam8_step(plan: Adam8Plan, param, grad, code_m, code_v, *, lr_step=0.0, bet
         stream=_stream()))
 
 
+# Adafactor (csrc/adafactor.hip): a matrix tile is ADAFACTOR_ROWS x ADAFACTOR_COLS elements, and
+# the longest chain of fp32 additions behind a row sum (4 values per lane + 6 shuffle levels = 10)
+# and behind a column sum (8 rows per lane + 3 across the waves = 11); the sums over the tiles are
+# fp64, rounded to fp32 once with the mean's division.  A chain's first addition, into a zero
+# accumulator, is exact: that one pays for the rounding of the term's own g * g.
+ADAFACTOR_ROWS, ADAFACTOR_COLS = 32, 256
+ADAFACTOR_SUM_CHAIN = 11
+ADAFACTOR_SEG = 256  # rows or columns per block of k_af_factor
+
+
+def _up4(n: int) -> int:
+    return -(-n // 4) * 4
+
+
+class AdafactorPlan:
+    """Tables of one flat range (a bucket or the whole model) for Adafactor.  ``rows[t]`` is
+    ``shape[0]`` of a factored tensor (viewed as ``[n, m] = [rows, numel / rows]``) and 0 of a
+    vector.  State offsets, each segment padded to 4 floats and counted in tensor order, so a
+    bucket's offsets are the whole model's minus those of its first tensor: ``r0`` / ``c0`` (R and
+    C of the matrices in ``row`` / ``col``), ``v0`` (the vectors' second moments); each list has
+    one entry per tensor and the total at the end.  ``items`` (matrix tiles first, ``num_tiles``
+    of them, then the vectors' chunk rows), ``tens`` and ``fitems`` are ``csrc/adafactor.hip``'s
+    ``AfItem`` / ``AfTen`` / ``AfFItem``; ``rowpart_floats`` / ``colpart_floats`` /
+    ``rsum_doubles`` size the workspaces.  Built without a device; :meth:`to` makes the device
+    tables."""
+
+    def __init__(self, plan, rows):
+        from ..compress.plan import CHUNK
+
+        if len(rows) != plan.num_tensors:
+            raise ValueError("one row count per tensor of the range")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        self.plan = plan
+        self.r0, self.c0, self.v0 = [0], [0], [0]
+        self.tens, tiles, chunks, self.fitems = [], [], [], []
+        rp = cp = rs = 0
+        for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
+            if numel < 1:
+                raise ValueError(f"tensor {t} has no elements")
+            if n < 0 or (n and numel % n):
+                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
+            m = numel // n if n else 0
+            self.r0.append(self.r0[-1] + _up4(n))
+            self.c0.append(self.c0[-1] + _up4(m))
+            self.v0.append(self.v0[-1] + (0 if n else _up4(numel)))
+            if not n:
+                mine = [[t, off + CHUNK * j, min(CHUNK, numel - CHUNK * j), 0]
+                        for j in range(-(-numel // CHUNK))]
+                chunks.append(mine)
+                self.tens.append([off, numel, 0, 0, 0, len(mine), self.v0[t], 0, 0, 0, 0, 0, 0,
+                                  0, 0, 0])
+                continue
+            nb, ns, nseg = -(-n // ADAFACTOR_ROWS), -(-m // ADAFACTOR_COLS), -(-n // ADAFACTOR_SEG)
+            mine = [[t, b, s, 0] for b in range(nb) for s in range(ns)]
+            tiles.append(mine)
+            self.tens.append([off, numel, n, m, 0, len(mine), self.r0[t], self.c0[t], rp, cp, rs,
+                              nb, ns, nseg, 0, 0])
+            self.fitems += [[t, 0, s, 0] for s in range(nseg)]
+            self.fitems += [[t, 1, s, 0] for s in range(-(-m // ADAFACTOR_SEG))]
+            rp, cp, rs = rp + ns * n, cp + nb * m, rs + nseg
+        self.items = []
+        for mine in tiles + chunks:  # a tensor's items are consecutive: item0, nitems
+            self.tens[mine[0][0]][4] = len(self.items)
+            self.items += mine
+        self.num_tiles = sum(len(x) for x in tiles)
+        self.rowpart_floats, self.colpart_floats, self.rsum_doubles = rp, cp, rs
+        if max(rp, cp, plan.length, self.r0[-1], self.c0[-1], 2 * len(self.items)) >= 1 << 31:
+            raise ValueError("Adafactor plan of 2^31 elements or more")
+        self.items_t = self.tens_t = self.fitems_t = None
+
+    def to(self, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.items_t = torch.tensor(self.items, **i32)
+        self.tens_t = torch.tensor(self.tens, **i32)
+        self.fitems_t = torch.tensor(self.fitems, **i32) if self.fitems else None
+        return self
+
+
+class AdafactorWorkspace:
+    """Adafactor's device workspaces for the plan ``ap`` (the whole model's serves every bucket):
+    the row and column partials, 1 / sqrt(C), the fp64 sums of R and the per-item partials."""
+
+    def __init__(self, ap: AdafactorPlan, device):
+        f32 = dict(dtype=torch.float32, device=device)
+        self.sizes = (ap.rowpart_floats, ap.colpart_floats, ap.c0[-1], ap.rsum_doubles,
+                      2 * len(ap.items))
+        self.rowpart = torch.zeros(max(4, self.sizes[0]), **f32)
+        self.colpart = torch.zeros(max(4, self.sizes[1]), **f32)
+        self.cfac = torch.zeros(max(4, self.sizes[2]), **f32)
+        self.rsum = torch.zeros(max(2, self.sizes[3]), dtype=torch.float64, device=device)
+        self.partials = torch.zeros(max(4, self.sizes[4]), **f32)
+
+    def fits(self, ap: AdafactorPlan) -> bool:
+        need = (ap.rowpart_floats, ap.colpart_floats, ap.c0[-1], ap.rsum_doubles,
+                2 * len(ap.items))
+        return all(n <= s for n, s in zip(need, self.sizes))
+
+
+def adafactor_step(ap: AdafactorPlan, ws: AdafactorWorkspace, param, grad, row, col, v, mom=None,
+                   *, lr, t=1, beta1=0.0, clip=1.0, scale_parameter=False, weight_decay=0.0,
+                   grad_scale=1.0, decay=0.8, step=None, lr_tensor=None, shadow=None):
+    """One Adafactor step of the flat range ``ap`` describes (``compress/oracle.py
+    adafactor_apply``), in four launches: ``k_af_stats`` (the tiles' row and column partials of
+    g^2 + 1e-30), ``k_af_factor`` (R, C in place; 1 / sqrt(C)), ``k_af_rms`` (per-item sums of u^2
+    and p^2; the vectors' v) and ``k_af_apply`` (clip, alpha, the step, ``mom`` when ``beta1 >
+    0``, the bf16 shadow).  ``row`` / ``col`` / ``v``: the range's views of the state (``ap.r0``
+    / ``c0`` / ``v0``).  ``step`` (int32 device tensor, optional): the kernels read the 0-based
+    step count from it (``t = step + 1``) instead of the host's ``t``."""
+    from ..compress import oracle
+
+    C = require()
+    n = ap.plan.length
+    if ap.items_t is None or not ws.fits(ap):
+        raise ValueError("the Adafactor plan has no device tables or does not fit the workspace")
+    if not clip > 0 or not 0.0 <= beta1 < 1.0:
+        raise ValueError(f"Adafactor needs clip > 0 and beta1 in [0, 1), not {clip!r}, {beta1!r}")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    states = [(row, "row", ap.r0[-1]), (col, "col", ap.c0[-1]), (v, "v", ap.v0[-1])]
+    if beta1 != 0.0:
+        if mom is None:
+            raise ValueError("the Adafactor step with beta1 > 0 needs mom")
+        states.append((mom, "mom", n))
+    for s, nm, need in states + [(param, "param", n), (grad, "grad", n)]:
+        if nm in ("row", "col", "v", "mom"):
+            _check(s, torch.float32, nm)
+        if s.numel() < need:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
+    _check_shadow(ap, shadow)
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    b2, omb2 = oracle.adafactor_beta2(t, decay)
+    args = _args(
+        C.AdafactorArgs, param=_ptr(param), grad=_ptr(grad), row=_ptr(row), col=_ptr(col),
+        v=_ptr(v), mom=_ptr(mom) if beta1 != 0.0 else 0, shadow=_ptr(shadow),
+        items=_ptr(ap.items_t), tensors=_ptr(ap.tens_t), fitems=_ptr(ap.fitems_t),
+        rowpart=_ptr(ws.rowpart), colpart=_ptr(ws.colpart), cfac=_ptr(ws.cfac),
+        rsum=_ptr(ws.rsum), partials=_ptr(ws.partials), num_items=len(ap.items),
+        num_tiles=ap.num_tiles, num_fitems=len(ap.fitems), grad_dtype=_GDT[grad.dtype],
+        scale_parameter=int(bool(scale_parameter)), lr=float(lr), beta1=float(beta1),
+        clip=float(clip), weight_decay=float(weight_decay), grad_scale=float(grad_scale),
+        beta2=b2, omb2=omb2, decay=float(decay), step=_ptr(step), lr_ptr=_lrp(lr_tensor),
+        stream=_stream())
+    C.adafactor_stats(args)
+    C.adafactor_factor(args)
+    C.adafactor_rms(args)
+    C.adafactor_apply(args)
+
+
 # Muon (csrc/muon.hip): output tile edge and k-step of its products; the gram's long dimension is
 # cut into slabs of about MUON_SLAB_K columns (a multiple of MUON_K), MUON_MAX_SPLITS at the most
 MUON_TILE, MUON_K = 64, 32

@@ -195,6 +195,11 @@ PYBIND11_MODULE(_C, m) {
           F(param) F(grad) F(code_m) F(code_v) F(absmax_m) F(absmax_v) F(shadow) F(chunks)
           F(table) F(stream) F(num_chunks) F(grad_dtype) F(lr_step) F(beta1) F(beta2) F(eps)
           F(weight_decay) F(grad_scale) F(step) F(lr) F(lr_ptr))
+  EW_ARGS(AdafactorArgs,
+          F(param) F(grad) F(row) F(col) F(v) F(mom) F(shadow) F(items) F(tensors) F(fitems)
+          F(stream) F(rowpart) F(colpart) F(cfac) F(rsum) F(partials) F(num_items) F(num_tiles)
+          F(num_fitems) F(grad_dtype) F(scale_parameter) F(lr) F(beta1) F(clip) F(weight_decay)
+          F(grad_scale) F(beta2) F(omb2) F(decay) F(step) F(lr_ptr))
   EW_ARGS(MuonArgs,
           F(param) F(mom) F(grad) F(shadow) F(chunks) F(xoff) F(partials) F(stream) F(mats)
           F(items) F(x_in) F(x_out) F(a_buf) F(b_buf) F(slabs) F(tickets) F(num_chunks)
@@ -255,6 +260,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("layerwise_stage", &ew_layerwise_stage);
   m.def("layerwise_apply", &ew_layerwise_apply);
   m.def("adam8_step", &ew_adam8_step);
+  m.def("adafactor_stats", &ew_adafactor_stats);
+  m.def("adafactor_factor", &ew_adafactor_factor);
+  m.def("adafactor_rms", &ew_adafactor_rms);
+  m.def("adafactor_apply", &ew_adafactor_apply);
   m.def("muon_momentum", &ew_muon_momentum);
   m.def("muon_gram", &ew_muon_gram);
   m.def("muon_poly", &ew_muon_poly);

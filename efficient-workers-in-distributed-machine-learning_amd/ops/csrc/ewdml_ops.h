@@ -453,6 +453,32 @@ struct Adam8Args {
 };
 void ew_adam8_step(const Adam8Args& a);
 
+// Adafactor over a flat range (adafactor.hip; ops.AdafactorPlan builds the tables).  items int32
+// [num_items, 4]: the matrix tiles (EW_AF_ROWS x EW_AF_COLS elements: tensor, band, strip) first,
+// num_tiles of them, then the vectors' chunk rows (tensor, start, len).  tensors int32 [T, 16],
+// fitems int32 [num_fitems, 4]: the factor launch's blocks of 256 rows or columns.  param, grad,
+// mom (beta1 > 0 only) and shadow are the range's views; row / col / v the range's views of the
+// factored statistics and of the vectors' second moments.  Workspaces: rowpart / colpart fp32,
+// cfac fp32 (indexed like col), rsum fp64, partials fp32 [2 * num_items].
+#define EW_AF_ROWS 32
+#define EW_AF_COLS 256
+struct AdafactorArgs {
+  uintptr_t param, grad, row, col, v, mom, shadow, items, tensors, fitems, stream;
+  uintptr_t rowpart, colpart, cfac, rsum, partials;
+  int num_items, num_tiles, num_fitems;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  int scale_parameter;
+  float lr, beta1, clip, weight_decay, grad_scale;
+  float beta2, omb2;  // beta2_t and 1 - beta2_t of this step (used when step is 0)
+  double decay;       // beta2_t = 1 - t^-decay
+  uintptr_t step;     // nullable int32 device step counter: t = *step + 1
+  uintptr_t lr_ptr;   // nullable device fp32 lr (overrides lr)
+};
+void ew_adafactor_stats(const AdafactorArgs& a);
+void ew_adafactor_factor(const AdafactorArgs& a);
+void ew_adafactor_rms(const AdafactorArgs& a);
+void ew_adafactor_apply(const AdafactorArgs& a);
+
 // Muon over a flat range (muon.hip; ops.MuonPlan builds the tables).  The momentum launch walks
 // the range's chunk table (param, mom, grad, shadow: its views; xoff int32[T]: a matrix's offset in
 // the X workspace, -1 for a vector) and writes u into x_out and the chunk sums of u^2 into

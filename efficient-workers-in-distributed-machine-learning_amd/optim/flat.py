@@ -772,8 +772,139 @@ class FlatMuon(_Layerwise):
                 setattr(self, k, sd[k])
 
 
+class FlatAdafactor(_LrMixin):
+    """Adafactor (Shazeer and Stern, ICML 2018) with an external learning rate
+    (``compress/oracle.py adafactor_apply``).  A tensor with ``dim() >= 2``, viewed as ``[n, m] =
+    [shape[0], numel / shape[0]]`` like :class:`FlatMuon`'s, keeps ``n + m`` floats of
+    second-moment statistics in the flat ``row`` / ``col``; a vector keeps its full second moment
+    in ``v``; ``m`` (indexed like ``flat.data``) exists only when ``beta1 > 0``.  ``beta2_t = 1 -
+    t^-decay``; the update is clipped to an RMS of ``clip`` per tensor and, with
+    ``scale_parameter``, scaled by ``max(1e-3, RMS(p))``.  A step covers one bucket or the whole
+    model: four HIP launches on the GPU (``ops.adafactor_step``, which reads ``t`` from the
+    device counter ``step_t``), the torch oracle on the CPU."""
+    fusable = False
+
+    def __init__(self, flat, lr=1e-3, beta1=0.0, clip=1.0, scale_parameter=False,
+                 weight_decay=0.0, decay=0.8):
+        from ..compress.plan import BucketPlan
+
+        if not 0.0 <= beta1 < 1.0 or not clip > 0 or not decay > 0:
+            raise ValueError(f"Adafactor needs beta1 in [0, 1), clip > 0 and decay > 0, not "
+                             f"{beta1!r}, {clip!r}, {decay!r}")
+        self.flat = flat
+        dev = flat.data.device
+        self._init_lr(lr, dev)
+        self.beta1, self.clip, self.decay = float(beta1), float(clip), float(decay)
+        self.scale_parameter, self.weight_decay = bool(scale_parameter), weight_decay
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        # the whole model's plan lays the state out; a bucket's plan sees views of it
+        self._whole = ops.AdafactorPlan(
+            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
+            self.rows)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.row = torch.zeros(self._whole.r0[-1], **f32)
+        self.col = torch.zeros(self._whole.c0[-1], **f32)
+        self.v = torch.zeros(self._whole.v0[-1], **f32)
+        self.m = torch.zeros_like(flat.data) if self.beta1 > 0 else None
+        self._plans = {}
+        self._ws = ops.AdafactorWorkspace(self._whole, dev) if dev.type == "cuda" else None
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            raise ValueError(f"an Adafactor step covers a bucket or the whole model (statistics "
+                             f"are per tensor), not the range [{start}, {start + length})") from None
+
+    def _plan(self, start, length):
+        """The range's device plan (built once)."""
+        ap = self._plans.get((start, length))
+        if ap is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            ap = ops.AdafactorPlan(plan, self.rows[t0:t0 + nt]).to(self.flat.data.device)
+            self._plans[(start, length)] = ap
+        return ap
+
+    def _state(self, t0, nt):
+        """The views of ``row`` / ``col`` / ``v`` that belong to tensors ``t0 .. t0 + nt``."""
+        w = self._whole
+        return (self.row[w.r0[t0]:w.r0[t0 + nt]], self.col[w.c0[t0]:w.c0[t0 + nt]],
+                self.v[w.v0[t0]:w.v0[t0 + nt]])
+
+    def _tensors(self, start, length):
+        """The oracle's ``(offset, numel, rows, s0, s1)`` rows of a range, the state offsets
+        counted from the range's views."""
+        t0, nt = self._range(start, length)
+        w = self._whole
+        return [(self.flat.offsets[t] - start, self.flat.params[t].numel(), self.rows[t],
+                 (w.r0[t] - w.r0[t0]) if self.rows[t] else (w.v0[t] - w.v0[t0]),
+                 w.c0[t] - w.c0[t0]) for t in range(t0, t0 + nt)]
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state: ``row``, ``col``, ``v`` and, with ``beta1 > 0``, ``m``."""
+        return sum(t.numel() * t.element_size()
+                   for t in (self.row, self.col, self.v, self.m) if t is not None)
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        t0, nt = self._range(start, length)
+        sl = slice(start, start + length)
+        p = self.flat.data[sl]
+        m = self.m[sl] if self.m is not None else None
+        row, col, v = self._state(t0, nt)
+        hp = dict(lr=self.lr, beta1=self.beta1, clip=self.clip, decay=self.decay,
+                  scale_parameter=self.scale_parameter, weight_decay=self.weight_decay)
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.adafactor_step(self._plan(start, length), self._ws, p, grad, row, col, v, m,
+                               t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
+                               lr_tensor=self.lr_t, shadow=sh, **hp)
+            return
+        oracle.adafactor_apply(p, row, col, v, m, grad.to(torch.float32) * grad_scale,
+                               self._tensors(start, length), step=self.steps + 1, **hp)
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    def state_dict(self):
+        return {"kind": "adafactor", "row": self.row, "col": self.col, "v": self.v, "m": self.m,
+                "steps": self.steps, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        for k in ("row", "col", "v"):
+            getattr(self, k).copy_(sd[k])
+        if self.m is not None:
+            self.m.copy_(sd["m"])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "adafactor":
+        return FlatAdafactor(flat, lr=kw.get("lr", 1e-3), beta1=kw.get("adafactor_beta1") or 0.0,
+                             clip=kw.get("adafactor_clip") or 1.0,
+                             scale_parameter=bool(kw.get("adafactor_scale_parameter")),
+                             weight_decay=kw.get("weight_decay", 0.0))
     if name == "muon":
         return FlatMuon(flat, aux_lr=kw.get("aux_lr"), ns_steps=kw.get("ns_steps") or 5,
                         ns_dtype=kw.get("ns_dtype") or "fp32",

@@ -238,7 +238,10 @@ class Trainer:
                                   nesterov=cfg.nesterov, eps=cfg.adam_eps,
                                   freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta,
                                   betas=cfg.lion_betas, ns_steps=cfg.muon_ns_steps,
-                                  ns_dtype=cfg.muon_ns_dtype, aux_lr=cfg.muon_aux_lr)
+                                  ns_dtype=cfg.muon_ns_dtype, aux_lr=cfg.muon_aux_lr,
+                                  adafactor_beta1=cfg.adafactor_beta1,
+                                  adafactor_clip=cfg.adafactor_clip,
+                                  adafactor_scale_parameter=cfg.adafactor_scale_parameter)
 
         # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
         # Adam share it); it runs once per step, after backward and before the first encode
