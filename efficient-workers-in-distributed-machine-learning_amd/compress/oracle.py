@@ -1886,3 +1886,109 @@ def adafactor_apply(p, row, col, v, mom, g, tensors, lr, step, beta1=0.0, clip=1
             mt.copy_(mt * b1 + s * c1)
             s = mt
         pt.copy_(pt * float(f32(1.0 - alpha * wd)) - s)
+
+
+# ---------------------------------------------------------------------------------------------
+# GaLore (Zhao et al., "GaLore: Memory-Efficient LLM Training by Gradient Low-Rank Projection",
+# ICML 2024): Adam whose moments live in a rank-r subspace of each weight matrix.  The definition
+# of ``ops/csrc/galore.hip`` (up to the order of the sums) and the CPU path of ``optim.FlatGalore``.
+#
+# ``p`` / ``g`` are views of one flat range, ``tensors`` its ``(offset, numel, rows, p0, s0)``
+# rows.  ``rows = shape[0]`` of a projected tensor, viewed as ``[n, m] = [rows, numel / rows]``
+# with s = min(n, m) > rank: its projector P [s, rank] is ``proj[p0:]`` and acts on the short
+# side, R = P^T G ([rank, m], n <= m) or G P ([n, rank]); its moments, of R's shape, are
+# ``m_lr[s0:]`` / ``v_lr[s0:]``.  ``rows = 0``: a dense tensor with full moments ``m[s0:]`` /
+# ``v[s0:]``, R = G.  With t the 1-based step::
+#
+#     M = b1 M + (1 - b1) R      V = b2 V + (1 - b2) R R
+#     N = (M / (1 - b1^t)) / (sqrt(V / (1 - b2^t)) + eps)
+#     p = p (1 - lr wd) - lr scale back(N)        back(N) = P N or N P^T; dense: N, scale = 1
+#
+# Before the step, when (t - 1) % update_gap == 0, P is refreshed by ``iters`` rounds of subspace
+# iteration on the gradient, warm-started from itself: Z = G^T P, Y = G Z, P = orth(Y) (in the
+# oriented form [s, l] of G).  The weight decay is decoupled.  The scalars are formed in double
+# from the fp32 hyper-parameters and rounded to fp32 once; the state's dtype is the arithmetic's.
+# ---------------------------------------------------------------------------------------------
+GALORE_ZERO = 2.0 ** -12
+
+
+def galore_orth(Y, ratios=None):
+    """Classical Gram-Schmidt with one re-orthogonalisation, in column order.  A column whose
+    norm after the first projection pass is at most ``GALORE_ZERO`` of its norm before (a zero
+    column included) becomes zero.  Norms are fp64.  ``ratios`` (a list) receives every nonzero
+    column's norm ratio."""
+    Q = torch.zeros_like(Y)
+    for c in range(Y.shape[1]):
+        y = Y[:, c].clone()
+        n0 = float(y.double().norm())
+        y = y - Q[:, :c] @ (Q[:, :c].t() @ y)
+        n1 = float(y.double().norm())
+        if ratios is not None and n0 > 0:
+            ratios.append(n1 / n0)
+        if n1 <= GALORE_ZERO * n0:
+            continue
+        y = y - Q[:, :c] @ (Q[:, :c].t() @ y)
+        Q[:, c] = y / y.double().norm().to(Y.dtype)
+    return Q
+
+
+def galore_refresh(G, P, iters=2, ratios=None):
+    """``iters`` rounds of subspace iteration from ``P`` on the oriented gradient ``G`` [s, l]."""
+    for _ in range(iters):
+        P = galore_orth(G @ (G.t() @ P), ratios)
+    return P
+
+
+def galore_pow(b: float, t: int) -> float:
+    """``b^t`` in double by squaring: a fixed order of multiplications, the kernels' own, where
+    ``pow`` would be rounded differently on the host and on the device."""
+    r = 1.0
+    while t > 0:
+        if t & 1:
+            r = r * b
+        b = b * b
+        t >>= 1
+    return r
+
+
+def galore_scalars(lr, step, beta1, beta2, weight_decay, scale):
+    """``(b1, 1 - b1, b2, 1 - b2, 1 - b1^t, 1 - b2^t, 1 - lr wd, lr scale, lr)``, each formed in
+    double from the fp32 hyper-parameters and rounded to fp32."""
+    f32 = np.float32
+    lr, b1, b2, wd, sc = (float(f32(x)) for x in (lr, beta1, beta2, weight_decay, scale))
+    return tuple(float(f32(x)) for x in (
+        b1, 1.0 - b1, b2, 1.0 - b2, 1.0 - galore_pow(b1, step), 1.0 - galore_pow(b2, step),
+        1.0 - lr * wd, lr * sc, lr))
+
+
+def galore_apply(p, proj, m_lr, v_lr, m, v, g, tensors, lr, step, rank, update_gap=200,
+                 scale=0.25, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, iters=2):
+    """One GaLore step in place with the already scaled gradient ``g``."""
+    b1, c1, b2, c2, bc1, bc2, keep, step_lr, lr32 = galore_scalars(
+        lr, step, betas[0], betas[1], weight_decay, scale)
+    eps = float(np.float32(eps))
+    g = g.to(p.dtype)
+    for off, numel, n, p0, s0 in tensors:
+        pt, gt = p[off:off + numel], g[off:off + numel]
+        if not n:
+            M, V, R, a = m[s0:s0 + numel], v[s0:s0 + numel], gt, lr32
+        else:
+            mm = numel // n
+            s, l = min(n, mm), max(n, mm)
+            # the oriented views [s, l] of the tensor and [rank, l] of its moments
+            def orient(x, a, b, wide=n <= mm):
+                return x.view(a, b) if wide else x.view(b, a).t()
+
+            pt, G = orient(pt, s, l), orient(gt, s, l)
+            P = proj[p0:p0 + s * rank].view(s, rank)
+            if (step - 1) % update_gap == 0:
+                P.copy_(galore_refresh(G, P, iters))
+            M = orient(m_lr[s0:s0 + rank * l], rank, l)
+            V = orient(v_lr[s0:s0 + rank * l], rank, l)
+            R, a = P.t() @ G, step_lr
+        M.copy_(M * b1 + R * c1)
+        V.copy_(V * b2 + (R * R) * c2)
+        # the root through double: correctly rounded in fp32, which torch's own fp32 sqrt on the
+        # CPU is not for every input (the kernels' is)
+        N = (M / bc1) / ((V / bc2).double().sqrt().to(V.dtype) + eps)
+        pt.copy_(pt * keep - (P @ N if n else N) * a)

@@ -124,7 +124,8 @@ class Config:
     # ---- optimizer -------------------------------------------------------------------------------
     # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
     # onebit_lamb (1-bit LAMB) | adam8bit (8-bit Adam: block-wise quantised moments) |
-    # lion | muon | adafactor (factored second moments): optim/flat.py
+    # lion | muon | adafactor (factored second moments) | galore (low-rank projected Adam):
+    # optim/flat.py
     optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / adam8bit / onebit_adam
     # onebit_adam / onebit_lamb: dense steps before the variance is frozen and the sign-compressed
@@ -143,6 +144,12 @@ class Config:
     adafactor_beta1: Optional[float] = None
     adafactor_clip: Optional[float] = None
     adafactor_scale_parameter: bool = False
+    # galore (Adam in a rank-r subspace of every matrix whose short side exceeds r, decoupled weight
+    # decay): the rank, a multiple of 16 in 16..128 (None: 64), the steps between two refreshes of
+    # the subspace (None: 200) and the scale of the projected update (None: 0.25)
+    galore_rank: Optional[int] = None
+    galore_update_gap: Optional[int] = None
+    galore_scale: Optional[float] = None
     # lion: "B1,B2" (None: 0.9,0.99), each in [0, 1); resolved to a tuple of two floats
     lion_betas: Optional[str] = None
     # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
@@ -427,6 +434,22 @@ class Config:
                             ("--adafactor-scale-parameter", c.adafactor_scale_parameter or None)):
                 if v is not None:
                     raise ValueError(f"{flag} belongs to --optimizer adafactor")
+        if c.optimizer == "galore":
+            c.galore_rank = 64 if c.galore_rank is None else int(c.galore_rank)
+            c.galore_update_gap = 200 if c.galore_update_gap is None else int(c.galore_update_gap)
+            c.galore_scale = 0.25 if c.galore_scale is None else float(c.galore_scale)
+            if c.galore_rank % 16 or not 16 <= c.galore_rank <= 128:
+                raise ValueError("--galore-rank must be a multiple of 16 in 16..128")
+            if c.galore_update_gap < 1:
+                raise ValueError("--galore-update-gap must be >= 1")
+            if not c.galore_scale > 0:
+                raise ValueError("--galore-scale must be > 0")
+        else:
+            for flag, v in (("--galore-rank", c.galore_rank),
+                            ("--galore-update-gap", c.galore_update_gap),
+                            ("--galore-scale", c.galore_scale)):
+                if v is not None:
+                    raise ValueError(f"{flag} belongs to --optimizer galore")
         if c.clip_grad_norm is not None:
             # the clip scales every gradient of the rank once, after backward and before any
             # encode (parallel/clip.py); the exchanges below do not take a clipper
@@ -579,7 +602,10 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
       choices=["sgd", "adam", "amsgrad", "adam8bit", "onebit_adam", "lars", "lamb", "lion",
-               "onebit_lamb", "muon", "adafactor"])
+               "onebit_lamb", "muon", "adafactor", "galore"])
+    a("--galore-rank", type=int, default=None)
+    a("--galore-update-gap", type=int, default=None)
+    a("--galore-scale", type=float, default=None)
     a("--adafactor-beta1", type=float, default=None)
     a("--adafactor-clip", type=float, default=None)
     a("--adafactor-scale-parameter", action="store_true")

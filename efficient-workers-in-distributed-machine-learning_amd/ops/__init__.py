@@ -1756,6 +1756,159 @@ def adafactor_step(ap: AdafactorPlan, ws: AdafactorWorkspace, param, grad, row, 
     C.adafactor_apply(args)
 
 
+# GaLore (csrc/galore.hip): a work item is GALORE_W long-side columns (step, sketch) or short-side
+# rows (range) of a matrix; the range product's long dimension is cut into slabs of about
+# GALORE_SLAB_K columns (a multiple of GALORE_K), GALORE_MAX_SPLITS at the most
+GALORE_W, GALORE_K, GALORE_SLAB_K, GALORE_MAX_SPLITS = 64, 16, 512, 64
+
+
+def _galore_rt(rank: int) -> int:
+    """The rank rounded up to the kernels' register tiles."""
+    return next(x for x in (16, 32, 64, 128) if rank <= x)
+
+
+class GalorePlan:
+    """Tables of one flat range (a bucket or the whole model) for GaLore.  ``rows[t]`` is
+    ``shape[0]`` of a tensor with ``dim() >= 2`` (viewed as ``[n, m] = [rows, numel / rows]``) and
+    0 of a vector; a matrix whose short side exceeds ``rank`` is projected, every other tensor is
+    dense (``projected[t]``).  State offsets, counted in tensor order, so a bucket's offsets are
+    the whole model's minus those of its first tensor: ``p0`` (P [s, rank] in ``proj``), ``l0``
+    (the low-rank moments in ``m_lr`` / ``v_lr``), ``d0`` (the dense moments in ``m`` / ``v``,
+    padded to 4 floats); each list has one entry per tensor and the total at the end.  ``mats``,
+    ``items``, ``ritems`` and ``ditems`` are ``csrc/galore.hip``'s ``GlMat`` / ``GlItem`` /
+    ``GlChunk``; ``z_floats`` / ``y_floats`` / ``part_floats`` / ``num_tickets`` size the
+    workspaces.  Built without a device; :meth:`to` makes the device tables."""
+
+    def __init__(self, plan, rows, rank):
+        from ..compress.plan import CHUNK
+
+        if len(rows) != plan.num_tensors:
+            raise ValueError("one row count per tensor of the range")
+        if rank % 16 or not 16 <= rank <= 128:
+            raise ValueError(f"the GaLore rank is a multiple of 16 in 16..128, not {rank!r}")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        self.plan, self.rank = plan, rank
+        self.p0, self.l0, self.d0 = [0], [0], [0]
+        self.projected, self.mats, self.items, self.ritems, self.ditems = [], [], [], [], []
+        z = y = part = tick = 0
+        tile = GALORE_W * _galore_rt(rank)
+        for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
+            if numel < 1:
+                raise ValueError(f"tensor {t} has no elements")
+            if n < 0 or (n and numel % n):
+                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
+            m = numel // n if n else 0
+            s, l = min(n, m), max(n, m)
+            proj = s > rank
+            self.projected.append(proj)
+            self.p0.append(self.p0[-1] + (s * rank if proj else 0))
+            self.l0.append(self.l0[-1] + (rank * l if proj else 0))
+            self.d0.append(self.d0[-1] + (0 if proj else _up4(numel)))
+            if not proj:
+                self.ditems += [[off + CHUNK * j, min(CHUNK, numel - CHUNK * j),
+                                 self.d0[t] + CHUNK * j, 0] for j in range(-(-numel // CHUNK))]
+                continue
+            splits = min(GALORE_MAX_SPLITS, -(-l // GALORE_SLAB_K))
+            kper = -(-(-(-l // splits)) // GALORE_K) * GALORE_K
+            splits = -(-l // kper)
+            ntile = -(-s // GALORE_W)
+            wide = n <= m
+            k = len(self.mats)
+            # G(i, j), M(k, j): strides of the short / rank index and of the long index
+            self.mats.append([off, s, l, m if wide else 1, 1 if wide else m, self.p0[t],
+                              self.l0[t], l if wide else 1, 1 if wide else rank, z, y, part,
+                              tick, splits, kper, 0])
+            self.items += [[k, j, 0, 0] for j in range(-(-l // GALORE_W))]
+            self.ritems += [[k, i, b, i] for i in range(ntile) for b in range(splits)]
+            z, y, tick = z + l * rank, y + s * rank, tick + ntile
+            part += ntile * splits * tile if splits > 1 else 0
+        self.z_floats, self.y_floats, self.part_floats, self.num_tickets = z, y, part, tick
+        if max(z, part, plan.length, self.l0[-1], self.d0[-1]) >= 1 << 31:
+            raise ValueError("GaLore plan of 2^31 elements or more")
+        self.mats_t = self.items_t = self.ritems_t = self.ditems_t = None
+        self.on_device = False
+
+    def to(self, device):
+        def table(rows):
+            return torch.tensor(rows, dtype=torch.int32, device=device) if rows else None
+
+        self.mats_t, self.items_t = table(self.mats), table(self.items)
+        self.ritems_t, self.ditems_t = table(self.ritems), table(self.ditems)
+        self.on_device = True
+        return self
+
+
+class GaloreWorkspace:
+    """GaLore's device workspaces for the plan ``gp`` (the whole model's serves every bucket):
+    Z and Y of the refresh, the range product's slabs and their arrival counters (zero between
+    launches)."""
+
+    def __init__(self, gp: GalorePlan, device):
+        f32 = dict(dtype=torch.float32, device=device)
+        self.sizes = (gp.z_floats, gp.y_floats, gp.part_floats, gp.num_tickets)
+        self.z = torch.zeros(max(4, self.sizes[0]), **f32)
+        self.y = torch.zeros(max(4, self.sizes[1]), **f32)
+        self.parts = torch.zeros(max(4, self.sizes[2]), **f32)
+        self.tickets = torch.zeros(max(1, self.sizes[3]), dtype=torch.int32, device=device)
+
+    def fits(self, gp: GalorePlan) -> bool:
+        need = (gp.z_floats, gp.y_floats, gp.part_floats, gp.num_tickets)
+        return all(n <= s for n, s in zip(need, self.sizes))
+
+
+def galore_step(gp: GalorePlan, ws: GaloreWorkspace, param, grad, proj, m_lr, v_lr, m, v, *, lr,
+                t=1, update_gap=200, scale=0.25, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                grad_scale=1.0, iters=2, step=None, lr_tensor=None, shadow=None):
+    """One GaLore step of the flat range ``gp`` describes (``compress/oracle.py galore_apply``) in
+    ``3 iters + 2`` launches: ``iters`` times ``k_gl_sketch`` (Z = G^T P), ``k_gl_range`` (Y = G
+    Z) and ``k_gl_orth`` (P = orth(Y)), which exit at once unless this step refreshes, then
+    ``k_gl_step`` (project, Adam, back-project and the parameter step of the projected matrices)
+    and ``k_gl_dense`` (Adam of every other tensor).  ``proj`` / ``m_lr`` / ``v_lr`` / ``m`` /
+    ``v``: the range's views of the state (``gp.p0`` / ``l0`` / ``d0``).  ``step`` (int32 device
+    tensor, optional): the kernels read the 0-based step count from it (``t = step + 1``)
+    instead of the host's ``t``."""
+    C = require()
+    n = gp.plan.length
+    if not gp.on_device or not ws.fits(gp):
+        raise ValueError("the GaLore plan has no device tables or does not fit the workspace")
+    if update_gap < 1 or iters < 1:
+        raise ValueError("GaLore needs update_gap >= 1 and iters >= 1")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    for s, nm, need in ((proj, "proj", gp.p0[-1]), (m_lr, "m_lr", gp.l0[-1]),
+                        (v_lr, "v_lr", gp.l0[-1]), (m, "m", gp.d0[-1]), (v, "v", gp.d0[-1]),
+                        (param, "param", n), (grad, "grad", n)):
+        if need and nm not in ("param", "grad"):
+            _check(s, torch.float32, nm)
+        if s.numel() < need:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
+    _check_shadow(gp, shadow)
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    args = _args(
+        C.GaloreArgs, param=_ptr(param), grad=_ptr(grad), proj=_ptr(proj), m_lr=_ptr(m_lr),
+        v_lr=_ptr(v_lr), m=_ptr(m), v=_ptr(v), shadow=_ptr(shadow), mats=_ptr(gp.mats_t),
+        items=_ptr(gp.items_t), ritems=_ptr(gp.ritems_t), ditems=_ptr(gp.ditems_t), z=_ptr(ws.z),
+        y=_ptr(ws.y), parts=_ptr(ws.parts), tickets=_ptr(ws.tickets), num_items=len(gp.items),
+        num_ritems=len(gp.ritems), num_ditems=len(gp.ditems), num_mats=len(gp.mats),
+        rank=gp.rank, update_gap=int(update_gap), grad_dtype=_GDT[grad.dtype],
+        refresh=int((t - 1) % update_gap == 0), t=int(t), lr=float(lr), beta1=float(betas[0]),
+        beta2=float(betas[1]), eps=float(eps), weight_decay=float(weight_decay),
+        scale=float(scale), grad_scale=float(grad_scale), step=_ptr(step),
+        lr_ptr=_lrp(lr_tensor), stream=_stream())
+    for _ in range(iters):
+        C.galore_sketch(args)
+        C.galore_range(args)
+        C.galore_orth(args)
+    C.galore_step(args)
+    C.galore_dense(args)
+
+
 # Muon (csrc/muon.hip): output tile edge and k-step of its products; the gram's long dimension is
 # cut into slabs of about MUON_SLAB_K columns (a multiple of MUON_K), MUON_MAX_SPLITS at the most
 MUON_TILE, MUON_K = 64, 32

@@ -200,6 +200,11 @@ PYBIND11_MODULE(_C, m) {
           F(stream) F(rowpart) F(colpart) F(cfac) F(rsum) F(partials) F(num_items) F(num_tiles)
           F(num_fitems) F(grad_dtype) F(scale_parameter) F(lr) F(beta1) F(clip) F(weight_decay)
           F(grad_scale) F(beta2) F(omb2) F(decay) F(step) F(lr_ptr))
+  EW_ARGS(GaloreArgs,
+          F(param) F(grad) F(proj) F(m_lr) F(v_lr) F(m) F(v) F(shadow) F(mats) F(items) F(ritems)
+          F(ditems) F(stream) F(z) F(y) F(parts) F(tickets) F(num_items) F(num_ritems)
+          F(num_ditems) F(num_mats) F(rank) F(update_gap) F(grad_dtype) F(refresh) F(t) F(lr)
+          F(beta1) F(beta2) F(eps) F(weight_decay) F(scale) F(grad_scale) F(step) F(lr_ptr))
   EW_ARGS(MuonArgs,
           F(param) F(mom) F(grad) F(shadow) F(chunks) F(xoff) F(partials) F(stream) F(mats)
           F(items) F(x_in) F(x_out) F(a_buf) F(b_buf) F(slabs) F(tickets) F(num_chunks)
@@ -264,6 +269,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("adafactor_factor", &ew_adafactor_factor);
   m.def("adafactor_rms", &ew_adafactor_rms);
   m.def("adafactor_apply", &ew_adafactor_apply);
+  m.def("galore_sketch", &ew_galore_sketch);
+  m.def("galore_range", &ew_galore_range);
+  m.def("galore_orth", &ew_galore_orth);
+  m.def("galore_step", &ew_galore_step);
+  m.def("galore_dense", &ew_galore_dense);
   m.def("muon_momentum", &ew_muon_momentum);
   m.def("muon_gram", &ew_muon_gram);
   m.def("muon_poly", &ew_muon_poly);

@@ -479,6 +479,31 @@ void ew_adafactor_factor(const AdafactorArgs& a);
 void ew_adafactor_rms(const AdafactorArgs& a);
 void ew_adafactor_apply(const AdafactorArgs& a);
 
+// GaLore over a flat range (galore.hip; ops.GalorePlan builds the tables).  mats int32 [M, 16];
+// items int32 [num_items, 4]: (matrix, strip of EW_GL_W long-side columns) of the step and the
+// sketch; ritems int32 [num_ritems, 4]: (matrix, tile of EW_GL_W short-side rows, slab, tile index)
+// of the range product; ditems int32 [num_ditems, 4]: the dense tensors' chunk rows (start, len,
+// offset in m / v).  param, grad and shadow are the range's views; proj, m_lr, v_lr (projected
+// matrices) and m, v (dense tensors) the range's views of the state.  Workspaces: z, y, parts fp32,
+// tickets int32 (zero between launches).
+#define EW_GL_W 64
+struct GaloreArgs {
+  uintptr_t param, grad, proj, m_lr, v_lr, m, v, shadow, mats, items, ritems, ditems, stream;
+  uintptr_t z, y, parts, tickets;
+  int num_items, num_ritems, num_ditems, num_mats;
+  int rank, update_gap;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  int refresh, t;  // this step refreshes / its 1-based number (used when step is 0)
+  float lr, beta1, beta2, eps, weight_decay, scale, grad_scale;
+  uintptr_t step;    // nullable int32 device step counter: t = *step + 1
+  uintptr_t lr_ptr;  // nullable device fp32 lr (overrides lr)
+};
+void ew_galore_sketch(const GaloreArgs& a);
+void ew_galore_range(const GaloreArgs& a);
+void ew_galore_orth(const GaloreArgs& a);
+void ew_galore_step(const GaloreArgs& a);
+void ew_galore_dense(const GaloreArgs& a);
+
 // Muon over a flat range (muon.hip; ops.MuonPlan builds the tables).  The momentum launch walks
 // the range's chunk table (param, mom, grad, shadow: its views; xoff int32[T]: a matrix's offset in
 // the X workspace, -1 for a vector) and writes u into x_out and the chunk sums of u^2 into

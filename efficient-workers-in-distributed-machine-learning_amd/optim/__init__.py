@@ -1,6 +1,6 @@
 """Optimizers with explicit gradients over the flat parameter buffer (reference ``optim/``)."""
-from .flat import (FlatAdafactor, FlatAdam, FlatAdam8bit, FlatLAMB, FlatLARS, FlatMuon, FlatSGD,
-                   make_optimizer)
+from .flat import (FlatAdafactor, FlatAdam, FlatAdam8bit, FlatGalore, FlatLAMB, FlatLARS, FlatMuon,
+                   FlatSGD, make_optimizer)
 
-__all__ = ["FlatSGD", "FlatAdam", "FlatAdam8bit", "FlatAdafactor", "FlatLARS", "FlatLAMB",
-           "FlatMuon", "make_optimizer"]
+__all__ = ["FlatSGD", "FlatAdam", "FlatAdam8bit", "FlatAdafactor", "FlatGalore", "FlatLARS",
+           "FlatLAMB", "FlatMuon", "make_optimizer"]

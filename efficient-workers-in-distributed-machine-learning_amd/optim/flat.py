@@ -898,8 +898,145 @@ class FlatAdafactor(_LrMixin):
         self.lr = sd.get("lr", self.lr)
 
 
+class FlatGalore(_LrMixin):
+    """GaLore (Zhao et al., ICML 2024): Adam whose two moments live in a rank-``rank`` subspace
+    of each weight matrix (``compress/oracle.py galore_apply``).  A tensor with ``dim() >= 2``,
+    viewed as ``[n, m] = [shape[0], numel / shape[0]]`` like :class:`FlatMuon`'s, whose short side
+    ``s`` exceeds ``rank`` keeps a projector ``[s, rank]`` in the flat ``proj`` and the moments of
+    its projected gradient (``rank`` times the long side) in ``m_lr`` / ``v_lr``; every other
+    tensor keeps full moments in ``m`` / ``v``.  Every ``update_gap`` steps the projector is
+    refreshed from the gradient by two rounds of subspace iteration, warm-started from itself;
+    the first one is a Gaussian drawn on the CPU from ``seed``.  The projected update is scaled by
+    ``scale``.  The weight decay is decoupled (``p (1 - lr wd)``, as Muon's and Lion's), unlike
+    :class:`FlatAdam`'s L2 term.  A step covers one bucket or the whole model: a fixed number of
+    HIP launches on the GPU (``ops.galore_step``, which reads ``t`` from the device counter
+    ``step_t``), the torch oracle on the CPU."""
+    kind = "galore"
+    fusable = False
+    ITERS = 2
+
+    def __init__(self, flat, lr=1e-3, rank=64, update_gap=200, scale=0.25, betas=(0.9, 0.999),
+                 eps=1e-8, weight_decay=0.0, seed=0):
+        from ..compress.plan import BucketPlan
+
+        if rank % 16 or not 16 <= rank <= 128 or update_gap < 1 or not scale > 0:
+            raise ValueError(f"GaLore needs a rank that is a multiple of 16 in 16..128, "
+                             f"update_gap >= 1 and scale > 0, not {rank!r}, {update_gap!r}, "
+                             f"{scale!r}")
+        self.flat = flat
+        dev = flat.data.device
+        self._init_lr(lr, dev)
+        self.rank, self.update_gap, self.scale = int(rank), int(update_gap), float(scale)
+        self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        # the whole model's plan lays the state out; a bucket's plan sees views of it
+        self._whole = w = ops.GalorePlan(
+            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
+            self.rows, self.rank)
+        f32 = dict(dtype=torch.float32, device=dev)
+        gen = torch.Generator().manual_seed(seed)
+        self.proj = torch.randn(w.p0[-1], generator=gen).to(dev)
+        self.m_lr, self.v_lr = torch.zeros(w.l0[-1], **f32), torch.zeros(w.l0[-1], **f32)
+        self.m, self.v = torch.zeros(w.d0[-1], **f32), torch.zeros(w.d0[-1], **f32)
+        self._plans = {}
+        self._ws = ops.GaloreWorkspace(w, dev) if dev.type == "cuda" else None
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            raise ValueError(f"a GaLore step covers a bucket or the whole model (projectors are "
+                             f"per tensor), not the range [{start}, {start + length})") from None
+
+    def _plan(self, start, length):
+        """The range's device plan (built once)."""
+        gp = self._plans.get((start, length))
+        if gp is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            gp = ops.GalorePlan(plan, self.rows[t0:t0 + nt], self.rank).to(self.flat.data.device)
+            self._plans[(start, length)] = gp
+        return gp
+
+    def _state(self, t0, nt):
+        """The views of ``proj``, ``m_lr``, ``v_lr``, ``m``, ``v`` of tensors ``t0 .. t0 + nt``."""
+        w = self._whole
+        pj, lr, d = (slice(x[t0], x[t0 + nt]) for x in (w.p0, w.l0, w.d0))
+        return self.proj[pj], self.m_lr[lr], self.v_lr[lr], self.m[d], self.v[d]
+
+    def _tensors(self, start, length):
+        """The oracle's ``(offset, numel, rows, p0, s0)`` rows of a range, the state offsets
+        counted from the range's views."""
+        t0, nt = self._range(start, length)
+        w = self._whole
+        return [(self.flat.offsets[t] - start, self.flat.params[t].numel(),
+                 self.rows[t] if w.projected[t] else 0, w.p0[t] - w.p0[t0],
+                 (w.l0[t] - w.l0[t0]) if w.projected[t] else (w.d0[t] - w.d0[t0]))
+                for t in range(t0, t0 + nt)]
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state: the projectors and the low-rank and dense moments."""
+        return sum(t.numel() * t.element_size()
+                   for t in (self.proj, self.m_lr, self.v_lr, self.m, self.v))
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        t0, nt = self._range(start, length)
+        sl = slice(start, start + length)
+        p = self.flat.data[sl]
+        hp = dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale, betas=self.betas,
+                  eps=self.eps, weight_decay=self.weight_decay, iters=self.ITERS)
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.galore_step(self._plan(start, length), self._ws, p, grad, *self._state(t0, nt),
+                            t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
+                            lr_tensor=self.lr_t, shadow=sh, **hp)
+            return
+        oracle.galore_apply(p, *self._state(t0, nt), grad.to(torch.float32) * grad_scale,
+                            self._tensors(start, length), step=self.steps + 1, rank=self.rank,
+                            **hp)
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    _STATE = ("proj", "m_lr", "v_lr", "m", "v")
+
+    def state_dict(self):
+        return {"kind": "galore", **{k: getattr(self, k) for k in self._STATE},
+                "steps": self.steps, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        for k in self._STATE:
+            getattr(self, k).copy_(sd[k])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "galore":
+        return FlatGalore(flat, lr=kw.get("lr", 1e-3), rank=kw.get("galore_rank") or 64,
+                          update_gap=kw.get("galore_update_gap") or 200,
+                          scale=kw.get("galore_scale") or 0.25, eps=kw.get("eps", 1e-8),
+                          weight_decay=kw.get("weight_decay", 0.0))
     if name == "adafactor":
         return FlatAdafactor(flat, lr=kw.get("lr", 1e-3), beta1=kw.get("adafactor_beta1") or 0.0,
                              clip=kw.get("adafactor_clip") or 1.0,

@@ -241,7 +241,10 @@ class Trainer:
                                   ns_dtype=cfg.muon_ns_dtype, aux_lr=cfg.muon_aux_lr,
                                   adafactor_beta1=cfg.adafactor_beta1,
                                   adafactor_clip=cfg.adafactor_clip,
-                                  adafactor_scale_parameter=cfg.adafactor_scale_parameter)
+                                  adafactor_scale_parameter=cfg.adafactor_scale_parameter,
+                                  galore_rank=cfg.galore_rank,
+                                  galore_update_gap=cfg.galore_update_gap,
+                                  galore_scale=cfg.galore_scale)
 
         # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
         # Adam share it); it runs once per step, after backward and before the first encode
