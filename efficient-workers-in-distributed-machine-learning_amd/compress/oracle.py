@@ -1992,3 +1992,96 @@ def galore_apply(p, proj, m_lr, v_lr, m, v, g, tensors, lr, step, rank, update_g
         # CPU is not for every input (the kernels' is)
         N = (M / bc1) / ((V / bc2).double().sqrt().to(V.dtype) + eps)
         pt.copy_(pt * keep - (P @ N if n else N) * a)
+
+
+# ---------------------------------------------------------------------------------------------
+# APOLLO (Zhu et al., "APOLLO: SGD-like Memory, AdamW-level Performance", MLSys 2025): GaLore's
+# low-rank Adam moments, kept only to estimate a learning-rate scale per channel (or per tensor)
+# that is applied to the full-rank raw gradient.  The definition of ``ops/csrc/apollo.hip`` (up to
+# the order of the sums) and the CPU path of ``optim.FlatApollo``.
+#
+# ``p`` / ``g`` are views of one flat range, ``tensors`` its ``(offset, numel, rows, gidx, s0,
+# k)`` rows.  ``rows = shape[0]`` of a projected tensor, viewed as ``[n, m]`` and oriented as G
+# ``[s, l]`` like GaLore's; ``gidx`` is its index in the whole model, its moments ``[rank, l]``
+# are ``m_lr[s0:]`` / ``v_lr[s0:]`` and its stored update norm is ``norms[2 k + parity]``.
+# ``rows = 0``: a dense tensor, exactly GaLore's dense branch (``m[s0:]`` / ``v[s0:]``, step
+# ``lr``).  With t the 1-based step and e = (t - 1) // update_gap the projection epoch::
+#
+#     P[k, i] = +-1 / sqrt(r)    sign: bit i % 32 of mix32((4 k + i // 32) ^ stream_key(seed, e,
+#                                gidx)); P is never stored
+#     R = (S^T G) rs             S = sqrt(r) P, rs = fp32(1 / sqrt(r)) applied once
+#     M = b1 M + (1 - b1) R      V = b2 V + (1 - b2) R R
+#     Rn = (M / (1 - b1^t)) / (sqrt(V / (1 - b2^t)) + eps)
+#     num_j = sum_i Rn[i, j]^2   den_j = sum_i R[i, j]^2   c_j = sum_k G[k, j]^2
+#     channel: s_j = sqrt(num_j / den_j)                  (0 where den_j == 0)
+#     tensor:  s_j = s = sqrt(sum num_j / sum den_j)      (0 where the denominator is 0)
+#     u = sqrt(sum_j s_j^2 c_j)  lim = max(u / u_prev, 1.01) / 1.01 if u_prev > 0 else 1
+#     p = p (1 - lr wd) - (lr scale / lim) s_j g          the new stored norm is u / lim
+#
+# ``u_prev`` is read from slot (t - 1) & 1 of the matrix's pair of norms and the new norm is
+# written to slot t & 1, so that no block of the apply kernel reads what another one writes.  The
+# sums over the columns are in double; the scalars are formed in double and rounded to fp32 once.
+# ---------------------------------------------------------------------------------------------
+APOLLO_GAMMA = 1.01
+
+
+def apollo_signs(seed, gidx, epoch, s, rank):
+    """The signs of P ``[s, rank]`` as an int64 tensor of +-1."""
+    key = rng.stream_key(seed, epoch, gidx)
+    k = torch.arange(s, dtype=torch.int64)[:, None]
+    i = torch.arange(rank, dtype=torch.int64)[None, :]
+    return 1 - 2 * ((rng.mix32((4 * k + i // 32) ^ key) >> (i % 32)) & 1)
+
+
+def apollo_apply(p, m_lr, v_lr, m, v, norms, g, tensors, lr, step, rank, update_gap=200,
+                 scale=1.0, scale_type="channel", betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 seed=0):
+    """One APOLLO step in place with the already scaled gradient ``g``."""
+    import math
+
+    f32 = np.float32
+    b1, c1, b2, c2, bc1, bc2, keep, _, lr32 = galore_scalars(
+        lr, step, betas[0], betas[1], weight_decay, scale)
+    step_lr = float(f32(lr)) * float(f32(scale))  # divided by lim before it is rounded
+    eps, rs = float(f32(eps)), float(f32(1.0 / math.sqrt(float(rank))))
+    epoch, par = (step - 1) // update_gap, step & 1
+    g = g.to(p.dtype)
+
+    def root(x):  # through double: see galore_apply
+        return x.double().sqrt().to(x.dtype)
+
+    for off, numel, n, gidx, s0, k in tensors:
+        pt, gt = p[off:off + numel], g[off:off + numel]
+        if not n:
+            M, V = m[s0:s0 + numel], v[s0:s0 + numel]
+            M.copy_(M * b1 + gt * c1)
+            V.copy_(V * b2 + (gt * gt) * c2)
+            pt.copy_(pt * keep - ((M / bc1) / (root(V / bc2) + eps)) * lr32)
+            continue
+        mm = numel // n
+        s, l = min(n, mm), max(n, mm)
+
+        def orient(x, a, b, wide=n <= mm):
+            return x.view(a, b) if wide else x.view(b, a).t()
+
+        pt, G = orient(pt, s, l), orient(gt, s, l)
+        M = orient(m_lr[s0:s0 + rank * l], rank, l)
+        V = orient(v_lr[s0:s0 + rank * l], rank, l)
+        R = (apollo_signs(seed, gidx, epoch, s, rank).to(p.dtype).t() @ G) * rs
+        M.copy_(M * b1 + R * c1)
+        V.copy_(V * b2 + (R * R) * c2)
+        Rn = (M / bc1) / (root(V / bc2) + eps)
+        num, den, c = (Rn * Rn).sum(0), (R * R).sum(0), (G * G).sum(0)
+        if scale_type == "tensor":
+            sn, sd = float(num.double().sum()), float(den.double().sum())
+            st = float(torch.tensor(math.sqrt(sn / sd) if sd > 0 else 0.0, dtype=p.dtype))
+            sj = torch.full_like(c, st)
+            u = math.sqrt(st * st * float(c.double().sum()))
+        else:
+            sj = torch.where(den > 0, root(num / den), torch.zeros_like(den))
+            u = math.sqrt(float(((sj * sj) * c).double().sum()))
+        up = float(norms[2 * k + (par ^ 1)])
+        lim = max(u / up, APOLLO_GAMMA) / APOLLO_GAMMA if up > 0 else 1.0
+        norms[2 * k + par] = u / lim
+        coef = step_lr / lim if p.dtype == torch.float64 else float(f32(step_lr / lim))
+        pt.copy_(pt * keep - (sj * coef)[None, :] * G)

@@ -124,8 +124,8 @@ class Config:
     # ---- optimizer -------------------------------------------------------------------------------
     # sgd | adam | amsgrad | onebit_adam (1-bit Adam) | lars | lamb (layer-wise trust ratios) |
     # onebit_lamb (1-bit LAMB) | adam8bit (8-bit Adam: block-wise quantised moments) |
-    # lion | muon | adafactor (factored second moments) | galore (low-rank projected Adam):
-    # optim/flat.py
+    # lion | muon | adafactor (factored second moments) | galore (low-rank projected Adam) |
+    # apollo (low-rank moments as a channel-wise lr scale): optim/flat.py
     optimizer: str = "sgd"
     adam_eps: float = 1e-8  # epsilon of adam / amsgrad / adam8bit / onebit_adam
     # onebit_adam / onebit_lamb: dense steps before the variance is frozen and the sign-compressed
@@ -150,6 +150,15 @@ class Config:
     galore_rank: Optional[int] = None
     galore_update_gap: Optional[int] = None
     galore_scale: Optional[float] = None
+    # apollo (the Adam moments of a rank-r random projection of every matrix whose short side
+    # exceeds r, used as a learning-rate scale on the raw gradient, decoupled weight decay): the
+    # rank, 1 or a multiple of 16 in 16..128 (None: 64), the steps between two draws of the
+    # projection (None: 200), the scale of the update (None: 1.0) and one scale per channel |
+    # tensor (None: channel; rank 1 with tensor is APOLLO-Mini)
+    apollo_rank: Optional[int] = None
+    apollo_update_gap: Optional[int] = None
+    apollo_scale: Optional[float] = None
+    apollo_scale_type: Optional[str] = None
     # lion: "B1,B2" (None: 0.9,0.99), each in [0, 1); resolved to a tuple of two floats
     lion_betas: Optional[str] = None
     # --compress vote (Distributed Lion's 1-bit exchange): majority | average of the received
@@ -450,6 +459,26 @@ class Config:
                             ("--galore-scale", c.galore_scale)):
                 if v is not None:
                     raise ValueError(f"{flag} belongs to --optimizer galore")
+        if c.optimizer == "apollo":
+            c.apollo_rank = 64 if c.apollo_rank is None else int(c.apollo_rank)
+            c.apollo_update_gap = 200 if c.apollo_update_gap is None else int(c.apollo_update_gap)
+            c.apollo_scale = 1.0 if c.apollo_scale is None else float(c.apollo_scale)
+            c.apollo_scale_type = c.apollo_scale_type or "channel"
+            if c.apollo_rank != 1 and (c.apollo_rank % 16 or not 16 <= c.apollo_rank <= 128):
+                raise ValueError("--apollo-rank must be 1 or a multiple of 16 in 16..128")
+            if c.apollo_update_gap < 1:
+                raise ValueError("--apollo-update-gap must be >= 1")
+            if not c.apollo_scale > 0:
+                raise ValueError("--apollo-scale must be > 0")
+            if c.apollo_scale_type not in ("channel", "tensor"):
+                raise ValueError("--apollo-scale-type is channel or tensor")
+        else:
+            for flag, v in (("--apollo-rank", c.apollo_rank),
+                            ("--apollo-update-gap", c.apollo_update_gap),
+                            ("--apollo-scale", c.apollo_scale),
+                            ("--apollo-scale-type", c.apollo_scale_type)):
+                if v is not None:
+                    raise ValueError(f"{flag} belongs to --optimizer apollo")
         if c.clip_grad_norm is not None:
             # the clip scales every gradient of the rank once, after backward and before any
             # encode (parallel/clip.py); the exchanges below do not take a clipper
@@ -602,7 +631,11 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     # optimizer
     a("--optimizer", type=str, default=d.optimizer,
       choices=["sgd", "adam", "amsgrad", "adam8bit", "onebit_adam", "lars", "lamb", "lion",
-               "onebit_lamb", "muon", "adafactor", "galore"])
+               "onebit_lamb", "muon", "adafactor", "galore", "apollo"])
+    a("--apollo-rank", type=int, default=None)
+    a("--apollo-update-gap", type=int, default=None)
+    a("--apollo-scale", type=float, default=None)
+    a("--apollo-scale-type", type=str, default=None, choices=["channel", "tensor"])
     a("--galore-rank", type=int, default=None)
     a("--galore-update-gap", type=int, default=None)
     a("--galore-scale", type=float, default=None)

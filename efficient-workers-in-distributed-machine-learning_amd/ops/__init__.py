@@ -1909,6 +1909,148 @@ def galore_step(gp: GalorePlan, ws: GaloreWorkspace, param, grad, proj, m_lr, v_
     C.galore_dense(args)
 
 
+# APOLLO (csrc/apollo.hip): a stats item is APOLLO_W long-side columns of a matrix, an apply item a
+# chunk of its flat range
+APOLLO_W = 64
+APOLLO_SCALE_TYPES = {"channel": 0, "tensor": 1}
+
+
+class ApolloPlan:
+    """Tables of one flat range (a bucket or the whole model) for APOLLO, laid out as
+    :class:`GalorePlan`'s: ``rows[t]`` is ``shape[0]`` of a tensor with ``dim() >= 2`` and 0 of a
+    vector; a matrix whose short side exceeds ``rank`` is projected, every other tensor is dense.
+    ``tensor0`` is the index of the range's first tensor in the whole model: the key of a matrix's
+    projection is its global index, so a bucket's step and a whole-model step draw the same signs.
+    State offsets per tensor with the total at the end: ``l0`` (the low-rank moments), ``d0`` (the
+    dense moments, padded to 4 floats), ``k0`` (the matrix's pair of stored norms).  ``mats`` and
+    ``items`` / ``aitems`` are ``csrc/apollo.hip``'s ``ApMat`` / ``ApItem``, ``ditems`` is
+    ``csrc/galore.hip``'s ``GlChunk``; ``sj_floats`` sizes the per-column scale workspace.  Built
+    without a device; :meth:`to` makes the device tables."""
+
+    def __init__(self, plan, rows, rank, tensor0=0):
+        from ..compress.plan import CHUNK
+
+        if len(rows) != plan.num_tensors:
+            raise ValueError("one row count per tensor of the range")
+        if rank != 1 and (rank % 16 or not 16 <= rank <= 128):
+            raise ValueError(f"the APOLLO rank is 1 or a multiple of 16 in 16..128, not {rank!r}")
+        if any(o % 4 for o in plan.offsets):
+            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+            raise ValueError("a tensor reaches past the range")
+        self.plan, self.rank = plan, rank
+        self.l0, self.d0, self.k0 = [0], [0], [0]
+        self.projected, self.mats, self.items, self.aitems, self.ditems = [], [], [], [], []
+        w = 0
+        for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
+            if numel < 1:
+                raise ValueError(f"tensor {t} has no elements")
+            if n < 0 or (n and numel % n):
+                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
+            m = numel // n if n else 0
+            s, l = min(n, m), max(n, m)
+            proj = s > rank
+            self.projected.append(proj)
+            self.l0.append(self.l0[-1] + (rank * l if proj else 0))
+            self.d0.append(self.d0[-1] + (0 if proj else _up4(numel)))
+            self.k0.append(self.k0[-1] + int(proj))
+            if not proj:
+                self.ditems += [[off + CHUNK * j, min(CHUNK, numel - CHUNK * j),
+                                 self.d0[t] + CHUNK * j, 0] for j in range(-(-numel // CHUNK))]
+                continue
+            wide = n <= m
+            k, ns = len(self.mats), -(-l // APOLLO_W)
+            # G(i, j), M(k, j): strides of the short / rank index and of the long index
+            self.mats.append([off, s, l, m if wide else 1, 1 if wide else m, self.l0[t],
+                              l if wide else 1, 1 if wide else rank, tensor0 + t, w,
+                              len(self.items), ns, int(wide), 0, 0, 0])
+            self.items += [[k, j, 0, 0] for j in range(ns)]
+            self.aitems += [[k, j, 0, 0] for j in range(-(-numel // CHUNK))]
+            w += _up4(l)
+        self.sj_floats = w
+        if max(plan.length, self.l0[-1], self.d0[-1]) >= 1 << 31:
+            raise ValueError("APOLLO plan of 2^31 elements or more")
+        self.mats_t = self.items_t = self.aitems_t = self.ditems_t = None
+        self.on_device = False
+
+    def to(self, device):
+        def table(rows):
+            return torch.tensor(rows, dtype=torch.int32, device=device) if rows else None
+
+        self.mats_t, self.items_t = table(self.mats), table(self.items)
+        self.aitems_t, self.ditems_t = table(self.aitems), table(self.ditems)
+        self.on_device = True
+        return self
+
+
+class ApolloWorkspace:
+    """APOLLO's device workspaces for the plan ``ap`` (the whole model's serves every bucket): the
+    per-column scales of every matrix and one 4-float partial per strip."""
+
+    def __init__(self, ap: ApolloPlan, device):
+        self.sizes = (ap.sj_floats, 4 * len(ap.items))
+        self.sj = torch.zeros(max(4, self.sizes[0]), dtype=torch.float32, device=device)
+        self.parts = torch.zeros(max(4, self.sizes[1]), dtype=torch.float32, device=device)
+
+    def fits(self, ap: ApolloPlan) -> bool:
+        return ap.sj_floats <= self.sizes[0] and 4 * len(ap.items) <= self.sizes[1]
+
+
+def apollo_step(ap: ApolloPlan, ws: ApolloWorkspace, param, grad, m_lr, v_lr, m, v, norms, *, lr,
+                t=1, update_gap=200, scale=1.0, scale_type="channel", betas=(0.9, 0.999),
+                eps=1e-8, weight_decay=0.0, grad_scale=1.0, seed=0, step=None, lr_tensor=None,
+                shadow=None):
+    """One APOLLO step of the flat range ``ap`` describes (``compress/oracle.py apollo_apply``) in
+    three launches: ``k_ap_stats`` (the random projection from generated signs, Adam of the
+    low-rank moments, the per-column scales and the strips' partial sums), ``k_ap_apply`` (the
+    norm-growth limiter and the scaled-gradient step of the projected matrices) and GaLore's
+    ``k_gl_dense`` (Adam of every other tensor).  ``m_lr`` / ``v_lr`` / ``m`` / ``v`` / ``norms``:
+    the range's views of the state (``ap.l0`` / ``d0`` / ``k0``, two norms per matrix).  ``step``
+    (int32 device tensor, optional): the kernels read the 0-based step count from it (``t = step
+    + 1``; the projection epoch and the norms' parity follow) instead of the host's ``t``."""
+    C = require()
+    n = ap.plan.length
+    if not ap.on_device or not ws.fits(ap):
+        raise ValueError("the APOLLO plan has no device tables or does not fit the workspace")
+    if update_gap < 1 or scale_type not in APOLLO_SCALE_TYPES:
+        raise ValueError("APOLLO needs update_gap >= 1 and a scale type of channel or tensor")
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    for s, nm, need in ((m_lr, "m_lr", ap.l0[-1]), (v_lr, "v_lr", ap.l0[-1]), (m, "m", ap.d0[-1]),
+                        (v, "v", ap.d0[-1]), (norms, "norms", 2 * ap.k0[-1]), (param, "param", n),
+                        (grad, "grad", n)):
+        if need and nm not in ("param", "grad"):
+            # the low-rank state is read element by element: at rank 1 a bucket's view of it
+            # starts anywhere
+            _check(s, torch.float32, nm, align=16 if nm in ("m", "v") else 4)
+        if s.numel() < need:
+            raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
+    _check_shadow(ap, shadow)
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+    common = dict(param=_ptr(param), grad=_ptr(grad), shadow=_ptr(shadow),
+                  update_gap=int(update_gap), grad_dtype=_GDT[grad.dtype], t=int(t), lr=float(lr),
+                  beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
+                  weight_decay=float(weight_decay), grad_scale=float(grad_scale),
+                  step=_ptr(step), lr_ptr=_lrp(lr_tensor), stream=_stream())
+    if ap.mats:
+        args = _args(
+            C.ApolloArgs, m_lr=_ptr(m_lr), v_lr=_ptr(v_lr), norms=_ptr(norms),
+            mats=_ptr(ap.mats_t), items=_ptr(ap.items_t), aitems=_ptr(ap.aitems_t),
+            sj=_ptr(ws.sj), parts=_ptr(ws.parts), num_items=len(ap.items),
+            num_aitems=len(ap.aitems), num_mats=len(ap.mats), rank=ap.rank,
+            scale_type=APOLLO_SCALE_TYPES[scale_type], seed=int(seed) & 0xFFFFFFFF,
+            scale=float(scale), **common)
+        C.apollo_stats(args)
+        C.apollo_apply(args)
+    if ap.ditems:
+        # the dense tensors alone through GaLore's dense launch: no matrices, a rank it admits
+        C.galore_dense(_args(C.GaloreArgs, m=_ptr(m), v=_ptr(v), ditems=_ptr(ap.ditems_t),
+                             num_ditems=len(ap.ditems), rank=16, scale=1.0, **common))
+
+
 # Muon (csrc/muon.hip): output tile edge and k-step of its products; the gram's long dimension is
 # cut into slabs of about MUON_SLAB_K columns (a multiple of MUON_K), MUON_MAX_SPLITS at the most
 MUON_TILE, MUON_K = 64, 32

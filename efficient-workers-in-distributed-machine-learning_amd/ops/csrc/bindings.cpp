@@ -205,6 +205,11 @@ PYBIND11_MODULE(_C, m) {
           F(ditems) F(stream) F(z) F(y) F(parts) F(tickets) F(num_items) F(num_ritems)
           F(num_ditems) F(num_mats) F(rank) F(update_gap) F(grad_dtype) F(refresh) F(t) F(lr)
           F(beta1) F(beta2) F(eps) F(weight_decay) F(scale) F(grad_scale) F(step) F(lr_ptr))
+  EW_ARGS(ApolloArgs,
+          F(param) F(grad) F(m_lr) F(v_lr) F(norms) F(shadow) F(mats) F(items) F(aitems)
+          F(stream) F(sj) F(parts) F(num_items) F(num_aitems) F(num_mats) F(rank) F(update_gap)
+          F(grad_dtype) F(scale_type) F(t) F(seed) F(lr) F(beta1) F(beta2) F(eps)
+          F(weight_decay) F(scale) F(grad_scale) F(step) F(lr_ptr))
   EW_ARGS(MuonArgs,
           F(param) F(mom) F(grad) F(shadow) F(chunks) F(xoff) F(partials) F(stream) F(mats)
           F(items) F(x_in) F(x_out) F(a_buf) F(b_buf) F(slabs) F(tickets) F(num_chunks)
@@ -274,6 +279,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("galore_orth", &ew_galore_orth);
   m.def("galore_step", &ew_galore_step);
   m.def("galore_dense", &ew_galore_dense);
+  m.def("apollo_stats", &ew_apollo_stats);
+  m.def("apollo_apply", &ew_apollo_apply);
   m.def("muon_momentum", &ew_muon_momentum);
   m.def("muon_gram", &ew_muon_gram);
   m.def("muon_poly", &ew_muon_poly);

@@ -504,6 +504,30 @@ void ew_galore_orth(const GaloreArgs& a);
 void ew_galore_step(const GaloreArgs& a);
 void ew_galore_dense(const GaloreArgs& a);
 
+// APOLLO over a flat range (apollo.hip; ops.ApolloPlan builds the tables): the projected matrices
+// only, the range's other tensors go through ew_galore_dense.  mats int32 [M, 16]; items int32
+// [num_items, 4]: (matrix, strip of EW_GL_W long-side columns) of the stats launch; aitems int32
+// [num_aitems, 4]: (matrix, chunk of EW_CHUNK elements) of the apply launch.  param, grad and
+// shadow are the range's views; m_lr, v_lr and norms (fp32 [M, 2], indexed by the step's parity)
+// the range's views of the state.  Workspaces: sj fp32 (a matrix's per-column scales), parts fp32
+// [4 * num_items] (stats -> apply).  The projection's signs are a function of (seed, the tensor's
+// index in the whole model, (t - 1) / update_gap) and are never stored.
+struct ApolloArgs {
+  uintptr_t param, grad, m_lr, v_lr, norms, shadow, mats, items, aitems, stream;
+  uintptr_t sj, parts;
+  int num_items, num_aitems, num_mats;
+  int rank, update_gap;
+  int grad_dtype;  // 0 = fp32, 1 = bf16, 2 = fp16
+  int scale_type;  // 0 = one scale per long-side column, 1 = one per tensor
+  int t;           // the step's 1-based number (used when step is 0)
+  uint32_t seed;
+  float lr, beta1, beta2, eps, weight_decay, scale, grad_scale;
+  uintptr_t step;    // nullable int32 device step counter: t = *step + 1
+  uintptr_t lr_ptr;  // nullable device fp32 lr (overrides lr)
+};
+void ew_apollo_stats(const ApolloArgs& a);
+void ew_apollo_apply(const ApolloArgs& a);
+
 // Muon over a flat range (muon.hip; ops.MuonPlan builds the tables).  The momentum launch walks
 // the range's chunk table (param, mom, grad, shadow: its views; xoff int32[T]: a matrix's offset in
 // the X workspace, -1 for a vector) and writes u into x_out and the chunk sums of u^2 into

@@ -1030,8 +1030,151 @@ class FlatGalore(_LrMixin):
         self.lr = sd.get("lr", self.lr)
 
 
+class FlatApollo(_LrMixin):
+    """APOLLO (Zhu et al., MLSys 2025): the Adam moments of a rank-``rank`` random projection of
+    each weight matrix's gradient, kept only to estimate a learning-rate scale per long-side
+    column (``scale_type="channel"``) or per tensor (``"tensor"``; with ``rank=1`` the paper's
+    APOLLO-Mini), which multiplies the full-rank raw gradient (``compress/oracle.py
+    apollo_apply``).  The tensors are :class:`FlatGalore`'s: a matrix whose short side exceeds
+    ``rank`` keeps ``rank`` times its long side in ``m_lr`` / ``v_lr`` and a pair of update norms
+    for the norm-growth limiter; every other tensor keeps full moments in ``m`` / ``v``.  The
+    projection is +-1 / sqrt(rank) with signs hashed from (``seed``, the tensor's index, the
+    epoch ``(t - 1) // update_gap``): it is never stored and never refreshed by a launch.  The
+    weight decay is decoupled.  A step covers one bucket or the whole model: three HIP launches on
+    the GPU (``ops.apollo_step``, which reads ``t`` from the device counter ``step_t``), the torch
+    oracle on the CPU."""
+    kind = "apollo"
+    fusable = False
+
+    def __init__(self, flat, lr=1e-3, rank=64, update_gap=200, scale=1.0, scale_type="channel",
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, seed=0):
+        from ..compress.plan import BucketPlan
+
+        if ((rank != 1 and (rank % 16 or not 16 <= rank <= 128)) or update_gap < 1
+                or not scale > 0 or scale_type not in ops.APOLLO_SCALE_TYPES):
+            raise ValueError(f"APOLLO needs a rank of 1 or a multiple of 16 in 16..128, "
+                             f"update_gap >= 1, scale > 0 and a scale type of channel or tensor, "
+                             f"not {rank!r}, {update_gap!r}, {scale!r}, {scale_type!r}")
+        self.flat = flat
+        dev = flat.data.device
+        self._init_lr(lr, dev)
+        self.rank, self.update_gap, self.scale = int(rank), int(update_gap), float(scale)
+        self.scale_type, self.seed = scale_type, int(seed)
+        self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        # the whole model's plan lays the state out; a bucket's plan sees views of it
+        self._whole = w = ops.ApolloPlan(
+            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
+            self.rows, self.rank)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.m_lr, self.v_lr = torch.zeros(w.l0[-1], **f32), torch.zeros(w.l0[-1], **f32)
+        self.m, self.v = torch.zeros(w.d0[-1], **f32), torch.zeros(w.d0[-1], **f32)
+        self.norms = torch.zeros(2 * w.k0[-1], **f32)  # [matrix][parity of the step]
+        self._plans = {}
+        self._ws = ops.ApolloWorkspace(w, dev) if dev.type == "cuda" else None
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            raise ValueError(f"an APOLLO step covers a bucket or the whole model (scales and "
+                             f"norms are per tensor), not the range [{start}, {start + length})"
+                             ) from None
+
+    def _plan(self, start, length):
+        """The range's device plan (built once)."""
+        ap = self._plans.get((start, length))
+        if ap is None:
+            from ..compress.plan import BucketPlan
+
+            t0, nt = self._range(start, length)
+            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
+                              length)
+            ap = ops.ApolloPlan(plan, self.rows[t0:t0 + nt], self.rank, t0).to(
+                self.flat.data.device)
+            self._plans[(start, length)] = ap
+        return ap
+
+    def _state(self, t0, nt):
+        """The views of ``m_lr``, ``v_lr``, ``m``, ``v``, ``norms`` of tensors ``t0 .. t0 + nt``."""
+        w = self._whole
+        lr, d = (slice(x[t0], x[t0 + nt]) for x in (w.l0, w.d0))
+        return (self.m_lr[lr], self.v_lr[lr], self.m[d], self.v[d],
+                self.norms[2 * w.k0[t0]:2 * w.k0[t0 + nt]])
+
+    def _tensors(self, start, length):
+        """The oracle's ``(offset, numel, rows, gidx, s0, k)`` rows of a range, the state offsets
+        counted from the range's views."""
+        t0, nt = self._range(start, length)
+        w = self._whole
+        return [(self.flat.offsets[t] - start, self.flat.params[t].numel(),
+                 self.rows[t] if w.projected[t] else 0, t,
+                 (w.l0[t] - w.l0[t0]) if w.projected[t] else (w.d0[t] - w.d0[t0]),
+                 w.k0[t] - w.k0[t0]) for t in range(t0, t0 + nt)]
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state: the low-rank and dense moments and the stored norms."""
+        return sum(t.numel() * t.element_size() for t in (getattr(self, k) for k in self._STATE))
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        t0, nt = self._range(start, length)
+        sl = slice(start, start + length)
+        p = self.flat.data[sl]
+        hp = dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale,
+                  scale_type=self.scale_type, betas=self.betas, eps=self.eps,
+                  weight_decay=self.weight_decay, seed=self.seed)
+        if p.is_cuda:
+            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
+            ops.apollo_step(self._plan(start, length), self._ws, p, grad, *self._state(t0, nt),
+                            t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
+                            lr_tensor=self.lr_t, shadow=sh, **hp)
+            return
+        oracle.apollo_apply(p, *self._state(t0, nt), grad.to(torch.float32) * grad_scale,
+                            self._tensors(start, length), step=self.steps + 1, rank=self.rank,
+                            **hp)
+
+    def step(self, grad=None, grad_scale=1.0):
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    _STATE = ("m_lr", "v_lr", "m", "v", "norms")
+
+    def state_dict(self):
+        return {"kind": "apollo", **{k: getattr(self, k) for k in self._STATE},
+                "steps": self.steps, "lr": self.lr, "seed": self.seed}
+
+    def load_state_dict(self, sd):
+        for k in self._STATE:
+            getattr(self, k).copy_(sd[k])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+        self.seed = int(sd.get("seed", self.seed))
+
+
 def make_optimizer(name, flat, **kw):
     name = name.lower()
+    if name == "apollo":
+        return FlatApollo(flat, lr=kw.get("lr", 1e-3), rank=kw.get("apollo_rank") or 64,
+                          update_gap=kw.get("apollo_update_gap") or 200,
+                          scale=kw.get("apollo_scale") or 1.0,
+                          scale_type=kw.get("apollo_scale_type") or "channel",
+                          eps=kw.get("eps", 1e-8), weight_decay=kw.get("weight_decay", 0.0),
+                          seed=kw.get("seed") or 0)
     if name == "galore":
         return FlatGalore(flat, lr=kw.get("lr", 1e-3), rank=kw.get("galore_rank") or 64,
                           update_gap=kw.get("galore_update_gap") or 200,

@@ -244,7 +244,11 @@ class Trainer:
                                   adafactor_scale_parameter=cfg.adafactor_scale_parameter,
                                   galore_rank=cfg.galore_rank,
                                   galore_update_gap=cfg.galore_update_gap,
-                                  galore_scale=cfg.galore_scale)
+                                  galore_scale=cfg.galore_scale,
+                                  apollo_rank=cfg.apollo_rank,
+                                  apollo_update_gap=cfg.apollo_update_gap,
+                                  apollo_scale=cfg.apollo_scale,
+                                  apollo_scale_type=cfg.apollo_scale_type, seed=cfg.seed)
 
         # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
         # Adam share it); it runs once per step, after backward and before the first encode
