@@ -20,6 +20,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 from .compress import kinds
+from .optim import kinds as optimizers
 
 
 def _str2bool(v) -> bool:
@@ -408,77 +409,20 @@ class Config:
         elif c.onebit_warmup_steps is not None and c.optimizer != "onebit_lamb":
             raise ValueError("--onebit-warmup-steps belongs to --optimizer onebit_adam / "
                              "onebit_lamb")
-        if c.optimizer == "lars":
-            if c.lars_eta is None:
-                c.lars_eta = 0.001
-            if not c.lars_eta > 0:
-                raise ValueError("--lars-eta must be > 0")
-        elif c.lars_eta is not None:
-            raise ValueError("--lars-eta belongs to --optimizer lars")
-        if c.optimizer == "muon":
-            c.muon_ns_steps = 5 if c.muon_ns_steps is None else int(c.muon_ns_steps)
-            c.muon_ns_dtype = c.muon_ns_dtype or "fp32"
-            if not 1 <= c.muon_ns_steps <= 10:
-                raise ValueError("--muon-ns-steps must lie in 1..10")
-            if c.muon_ns_dtype not in ("fp32", "bf16"):
-                raise ValueError("--muon-ns-dtype is fp32 or bf16")
-            if c.muon_aux_lr is not None and not c.muon_aux_lr > 0:
-                raise ValueError("--muon-aux-lr must be > 0")
-        else:
-            for flag, v in (("--muon-ns-steps", c.muon_ns_steps),
-                            ("--muon-ns-dtype", c.muon_ns_dtype),
-                            ("--muon-aux-lr", c.muon_aux_lr)):
-                if v is not None:
-                    raise ValueError(f"{flag} belongs to --optimizer muon")
-        if c.optimizer == "adafactor":
-            c.adafactor_beta1 = 0.0 if c.adafactor_beta1 is None else float(c.adafactor_beta1)
-            c.adafactor_clip = 1.0 if c.adafactor_clip is None else float(c.adafactor_clip)
-            if not 0.0 <= c.adafactor_beta1 < 1.0:
-                raise ValueError("--adafactor-beta1 must lie in [0, 1)")
-            if not c.adafactor_clip > 0:
-                raise ValueError("--adafactor-clip must be > 0")
-        else:
-            for flag, v in (("--adafactor-beta1", c.adafactor_beta1),
-                            ("--adafactor-clip", c.adafactor_clip),
-                            ("--adafactor-scale-parameter", c.adafactor_scale_parameter or None)):
-                if v is not None:
-                    raise ValueError(f"{flag} belongs to --optimizer adafactor")
-        if c.optimizer == "galore":
-            c.galore_rank = 64 if c.galore_rank is None else int(c.galore_rank)
-            c.galore_update_gap = 200 if c.galore_update_gap is None else int(c.galore_update_gap)
-            c.galore_scale = 0.25 if c.galore_scale is None else float(c.galore_scale)
-            if c.galore_rank % 16 or not 16 <= c.galore_rank <= 128:
-                raise ValueError("--galore-rank must be a multiple of 16 in 16..128")
-            if c.galore_update_gap < 1:
-                raise ValueError("--galore-update-gap must be >= 1")
-            if not c.galore_scale > 0:
-                raise ValueError("--galore-scale must be > 0")
-        else:
-            for flag, v in (("--galore-rank", c.galore_rank),
-                            ("--galore-update-gap", c.galore_update_gap),
-                            ("--galore-scale", c.galore_scale)):
-                if v is not None:
-                    raise ValueError(f"{flag} belongs to --optimizer galore")
-        if c.optimizer == "apollo":
-            c.apollo_rank = 64 if c.apollo_rank is None else int(c.apollo_rank)
-            c.apollo_update_gap = 200 if c.apollo_update_gap is None else int(c.apollo_update_gap)
-            c.apollo_scale = 1.0 if c.apollo_scale is None else float(c.apollo_scale)
-            c.apollo_scale_type = c.apollo_scale_type or "channel"
-            if c.apollo_rank != 1 and (c.apollo_rank % 16 or not 16 <= c.apollo_rank <= 128):
-                raise ValueError("--apollo-rank must be 1 or a multiple of 16 in 16..128")
-            if c.apollo_update_gap < 1:
-                raise ValueError("--apollo-update-gap must be >= 1")
-            if not c.apollo_scale > 0:
-                raise ValueError("--apollo-scale must be > 0")
-            if c.apollo_scale_type not in ("channel", "tensor"):
-                raise ValueError("--apollo-scale-type is channel or tensor")
-        else:
-            for flag, v in (("--apollo-rank", c.apollo_rank),
-                            ("--apollo-update-gap", c.apollo_update_gap),
-                            ("--apollo-scale", c.apollo_scale),
-                            ("--apollo-scale-type", c.apollo_scale_type)):
-                if v is not None:
-                    raise ValueError(f"{flag} belongs to --optimizer apollo")
+        for k in optimizers.KINDS.values():
+            # the optimizers' own flags (optim/kinds.py): the chosen one's are filled with their
+            # defaults and checked in turn, every other one's are orphans
+            if c.optimizer == k.name:
+                for o in k.options:
+                    v = getattr(c, o.field)
+                    setattr(c, o.field, o.default if v is None else o.type(v))
+                for o in k.options:
+                    if o.refuses(getattr(c, o.field)):
+                        raise ValueError(f"{o.flag} {o.why}")
+            else:
+                for o in k.options:
+                    if getattr(c, o.field) != getattr(Config, o.field):
+                        raise ValueError(f"{o.flag} belongs to --optimizer {k.name}")
         if c.clip_grad_norm is not None:
             # the clip scales every gradient of the rank once, after backward and before any
             # encode (parallel/clip.py); the exchanges below do not take a clipper
@@ -629,26 +573,15 @@ def build_parser(prog="distributed_nn.py") -> argparse.ArgumentParser:
     a("--predivide", type=float, default=d.predivide)
     a("--sync-bn", "--sync-bn-buffers", dest="sync_bn", action="store_true", default=False)
     # optimizer
-    a("--optimizer", type=str, default=d.optimizer,
-      choices=["sgd", "adam", "amsgrad", "adam8bit", "onebit_adam", "lars", "lamb", "lion",
-               "onebit_lamb", "muon", "adafactor", "galore", "apollo"])
-    a("--apollo-rank", type=int, default=None)
-    a("--apollo-update-gap", type=int, default=None)
-    a("--apollo-scale", type=float, default=None)
-    a("--apollo-scale-type", type=str, default=None, choices=["channel", "tensor"])
-    a("--galore-rank", type=int, default=None)
-    a("--galore-update-gap", type=int, default=None)
-    a("--galore-scale", type=float, default=None)
-    a("--adafactor-beta1", type=float, default=None)
-    a("--adafactor-clip", type=float, default=None)
-    a("--adafactor-scale-parameter", action="store_true")
-    a("--muon-ns-steps", type=int, default=None)
-    a("--muon-ns-dtype", type=str, default=None, choices=["fp32", "bf16"])
-    a("--muon-aux-lr", type=float, default=None)
+    a("--optimizer", type=str, default=d.optimizer, choices=list(optimizers.KINDS))
+    for o in (o for k in optimizers.KINDS.values() for o in k.options):
+        if o.type is bool:
+            a(o.flag, action="store_true")
+        else:
+            a(o.flag, type=o.type, default=None, choices=o.choices and list(o.choices))
     a("--lion-betas", type=str, default=None)
     a("--adam-eps", type=float, default=d.adam_eps)
     a("--onebit-warmup-steps", type=int, default=None)
-    a("--lars-eta", type=float, default=None)
     a("--clip-grad-norm", type=float, default=None)
     a("--clip-scale-world", action="store_true", default=False)
     a("--weight-decay", type=float, default=d.weight_decay)

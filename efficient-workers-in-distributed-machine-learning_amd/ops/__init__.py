@@ -220,6 +220,21 @@ def _check_shadow(dp, shadow):
             raise ValueError("shadow too small for the bucket")
 
 
+def _check_param_grad(param, grad):
+    """A per-range step's fp32 ``param`` and its ``grad`` in one of the kernels' gradient dtypes
+    (the kernels load four values at once: 16 bytes of fp32, 8 of bf16 / fp16)."""
+    if grad.dtype not in _GDT:
+        raise TypeError(f"unsupported grad dtype {grad.dtype}")
+    _check(param, torch.float32, "param")
+    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+
+
+def _check_step(step):
+    """The optional device step counter (one int32)."""
+    if step is not None:
+        _check(step, torch.int32, "step", align=4)
+
+
 def _keyp(key_tensor):
     if key_tensor is None:
         return 0
@@ -912,8 +927,7 @@ def sign_decode_onebit(dp, recv, layout, param, exp_avg, exp_avg_sq, inv_n, lr_s
         _check_bucket(dp, t, nm)
     if int(freeze_step) < 1:
         raise ValueError("freeze_step must be >= 1")
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     _check_shadow(dp, shadow)
     C.sign_decode_onebit(_args(
         C.SignOnebitArgs, **src, param=_ptr(param), exp_avg=_ptr(exp_avg),
@@ -971,8 +985,7 @@ def onebit_lamb_step(lt: OnebitLambTables, recv, layout, param, exp_avg, exp_avg
         _check_bucket(dp, x, nm)
     if int(freeze_step) < 1 or (step is None and int(t) <= int(freeze_step)):
         raise ValueError("the compressed stage starts after freeze_step >= 1")
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     _check_shadow(dp, shadow)
     b1, b2 = betas
     args = _args(
@@ -1227,8 +1240,7 @@ def adam_flat(param, exp_avg, exp_avg_sq, max_exp_avg_sq, grad, lr_step, beta1, 
     reads t = step + 1 and derives ``lr_step = lr * sqrt(1 - beta2^t) / (1 - beta1^t)`` on the
     device, so a captured graph follows the step count (``lr_step`` is then ignored)."""
     C = require()
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     for t, nm in ((param, "param"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _check(t, torch.float32, nm)
     if amsgrad:
@@ -1434,6 +1446,25 @@ LAYERWISE_SUM_CHAIN = 41
 LAYERWISE_KINDS = {"lars": 0, "lamb": 1}
 
 
+def _check_range(plan, rows=None):
+    """What every per-range optimizer plan asks of its ``BucketPlan`` (and of ``rows``, one row
+    count per tensor, where it takes them): 16-byte loads from every tensor's start, and no
+    tensor past the end of the range the kernels index."""
+    if rows is not None and len(rows) != plan.num_tensors:
+        raise ValueError("one row count per tensor of the range")
+    if any(o % 4 for o in plan.offsets):
+        raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
+    if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
+        raise ValueError("a tensor reaches past the range")
+
+
+def _whole_rows(t, numel, n) -> int:
+    """The row length of tensor ``t`` viewed as ``n`` rows (0 for a vector, ``n`` = 0)."""
+    if n < 0 or (n and numel % n):
+        raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
+    return numel // n if n else 0
+
+
 class LayerwisePlan:
     """Device tables of one flat range (a bucket or the whole model) for the layer-wise
     optimizers: the range's ``BucketPlan`` tables and its views of the optimizer's per-tensor
@@ -1447,10 +1478,7 @@ class LayerwisePlan:
         if adapt.numel() != T or ratio.numel() != T or partials.numel() != 2 * C:
             raise ValueError(f"layer-wise plan of {T} tensors / {C} chunks: adapt, ratio must "
                              f"hold {T} entries and partials {2 * C}")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan)
         if plan.length >= 1 << 31:
             raise ValueError("flat range of 2^31 elements or more")
         self.plan = plan
@@ -1481,10 +1509,7 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
     if kind not in LAYERWISE_KINDS:
         raise ValueError(f"unknown layer-wise rule {kind!r}")
     n = lw.plan.length
-    if grad.dtype not in _GDT:
-        raise TypeError(f"unsupported grad dtype {grad.dtype}")
-    _check(param, torch.float32, "param")
-    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check_param_grad(param, grad)
     states = [(state1, "exp_avg"), (state2, "exp_avg_sq")] if kind == "lamb" else \
         [(state1, "mom")]
     for s, nm in states:
@@ -1495,8 +1520,7 @@ def layerwise_step(lw: LayerwisePlan, kind: str, param, grad, state1, state2=Non
         if s.numel() < n:
             raise ValueError(f"{nm} has {s.numel()} elements, the range needs {n}")
     _check_shadow(lw, shadow)
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     args = _layerwise_args(
         C, betas, t, kind=LAYERWISE_KINDS[kind], param=_ptr(param), grad=_ptr(grad),
         grad_dtype=_GDT[grad.dtype], state1=_ptr(state1),
@@ -1557,10 +1581,7 @@ class Adam8Plan:
         if absmax_m.numel() != ADAM8_SLOTS * C or absmax_v.numel() != ADAM8_SLOTS * C:
             raise ValueError(f"8-bit Adam plan of {C} chunks: absmax_m and absmax_v must hold "
                              f"{ADAM8_SLOTS * C} entries each")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan)
         if plan.length >= 1 << 31:
             raise ValueError("flat range of 2^31 elements or more")
         self.plan = plan
@@ -1579,18 +1600,14 @@ def adam8_step(plan: Adam8Plan, param, grad, code_m, code_v, *, lr_step=0.0, bet
     ``lr_step`` from ``lr`` / ``lr_tensor`` on the device, as :func:`adam_flat` does."""
     C = require()
     n = plan.plan.length
-    if grad.dtype not in _GDT:
-        raise TypeError(f"unsupported grad dtype {grad.dtype}")
-    _check(param, torch.float32, "param")
-    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check_param_grad(param, grad)
     _check(code_m, torch.uint8, "code_m", align=4)
     _check(code_v, torch.uint8, "code_v", align=4)
     for s, nm in ((param, "param"), (grad, "grad"), (code_m, "code_m"), (code_v, "code_v")):
         if s.numel() < n:
             raise ValueError(f"{nm} has {s.numel()} elements, the range needs {n}")
     _check_shadow(plan, shadow)
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     b1, b2 = betas
     C.adam8_step(_args(
         C.Adam8Args, param=_ptr(param), grad=_ptr(grad), code_m=_ptr(code_m),
@@ -1631,12 +1648,7 @@ class AdafactorPlan:
     def __init__(self, plan, rows):
         from ..compress.plan import CHUNK
 
-        if len(rows) != plan.num_tensors:
-            raise ValueError("one row count per tensor of the range")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan, rows)
         self.plan = plan
         self.r0, self.c0, self.v0 = [0], [0], [0]
         self.tens, tiles, chunks, self.fitems = [], [], [], []
@@ -1644,9 +1656,7 @@ class AdafactorPlan:
         for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
             if numel < 1:
                 raise ValueError(f"tensor {t} has no elements")
-            if n < 0 or (n and numel % n):
-                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
-            m = numel // n if n else 0
+            m = _whole_rows(t, numel, n)
             self.r0.append(self.r0[-1] + _up4(n))
             self.c0.append(self.c0[-1] + _up4(m))
             self.v0.append(self.v0[-1] + (0 if n else _up4(numel)))
@@ -1721,10 +1731,7 @@ def adafactor_step(ap: AdafactorPlan, ws: AdafactorWorkspace, param, grad, row, 
         raise ValueError("the Adafactor plan has no device tables or does not fit the workspace")
     if not clip > 0 or not 0.0 <= beta1 < 1.0:
         raise ValueError(f"Adafactor needs clip > 0 and beta1 in [0, 1), not {clip!r}, {beta1!r}")
-    if grad.dtype not in _GDT:
-        raise TypeError(f"unsupported grad dtype {grad.dtype}")
-    _check(param, torch.float32, "param")
-    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check_param_grad(param, grad)
     states = [(row, "row", ap.r0[-1]), (col, "col", ap.c0[-1]), (v, "v", ap.v0[-1])]
     if beta1 != 0.0:
         if mom is None:
@@ -1736,8 +1743,7 @@ def adafactor_step(ap: AdafactorPlan, ws: AdafactorWorkspace, param, grad, row, 
         if s.numel() < need:
             raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
     _check_shadow(ap, shadow)
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     b2, omb2 = oracle.adafactor_beta2(t, decay)
     args = _args(
         C.AdafactorArgs, param=_ptr(param), grad=_ptr(grad), row=_ptr(row), col=_ptr(col),
@@ -1786,10 +1792,7 @@ class GalorePlan:
             raise ValueError("one row count per tensor of the range")
         if rank % 16 or not 16 <= rank <= 128:
             raise ValueError(f"the GaLore rank is a multiple of 16 in 16..128, not {rank!r}")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan)
         self.plan, self.rank = plan, rank
         self.p0, self.l0, self.d0 = [0], [0], [0]
         self.projected, self.mats, self.items, self.ritems, self.ditems = [], [], [], [], []
@@ -1798,9 +1801,7 @@ class GalorePlan:
         for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
             if numel < 1:
                 raise ValueError(f"tensor {t} has no elements")
-            if n < 0 or (n and numel % n):
-                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
-            m = numel // n if n else 0
+            m = _whole_rows(t, numel, n)
             s, l = min(n, m), max(n, m)
             proj = s > rank
             self.projected.append(proj)
@@ -1876,10 +1877,7 @@ def galore_step(gp: GalorePlan, ws: GaloreWorkspace, param, grad, proj, m_lr, v_
         raise ValueError("the GaLore plan has no device tables or does not fit the workspace")
     if update_gap < 1 or iters < 1:
         raise ValueError("GaLore needs update_gap >= 1 and iters >= 1")
-    if grad.dtype not in _GDT:
-        raise TypeError(f"unsupported grad dtype {grad.dtype}")
-    _check(param, torch.float32, "param")
-    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check_param_grad(param, grad)
     for s, nm, need in ((proj, "proj", gp.p0[-1]), (m_lr, "m_lr", gp.l0[-1]),
                         (v_lr, "v_lr", gp.l0[-1]), (m, "m", gp.d0[-1]), (v, "v", gp.d0[-1]),
                         (param, "param", n), (grad, "grad", n)):
@@ -1888,8 +1886,7 @@ def galore_step(gp: GalorePlan, ws: GaloreWorkspace, param, grad, proj, m_lr, v_
         if s.numel() < need:
             raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
     _check_shadow(gp, shadow)
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     args = _args(
         C.GaloreArgs, param=_ptr(param), grad=_ptr(grad), proj=_ptr(proj), m_lr=_ptr(m_lr),
         v_lr=_ptr(v_lr), m=_ptr(m), v=_ptr(v), shadow=_ptr(shadow), mats=_ptr(gp.mats_t),
@@ -1934,10 +1931,7 @@ class ApolloPlan:
             raise ValueError("one row count per tensor of the range")
         if rank != 1 and (rank % 16 or not 16 <= rank <= 128):
             raise ValueError(f"the APOLLO rank is 1 or a multiple of 16 in 16..128, not {rank!r}")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan)
         self.plan, self.rank = plan, rank
         self.l0, self.d0, self.k0 = [0], [0], [0]
         self.projected, self.mats, self.items, self.aitems, self.ditems = [], [], [], [], []
@@ -1945,9 +1939,7 @@ class ApolloPlan:
         for t, (off, numel, n) in enumerate(zip(plan.offsets, plan.numels, rows)):
             if numel < 1:
                 raise ValueError(f"tensor {t} has no elements")
-            if n < 0 or (n and numel % n):
-                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
-            m = numel // n if n else 0
+            m = _whole_rows(t, numel, n)
             s, l = min(n, m), max(n, m)
             proj = s > rank
             self.projected.append(proj)
@@ -2014,10 +2006,7 @@ def apollo_step(ap: ApolloPlan, ws: ApolloWorkspace, param, grad, m_lr, v_lr, m,
         raise ValueError("the APOLLO plan has no device tables or does not fit the workspace")
     if update_gap < 1 or scale_type not in APOLLO_SCALE_TYPES:
         raise ValueError("APOLLO needs update_gap >= 1 and a scale type of channel or tensor")
-    if grad.dtype not in _GDT:
-        raise TypeError(f"unsupported grad dtype {grad.dtype}")
-    _check(param, torch.float32, "param")
-    _check(grad, grad.dtype, "grad", align=16 if grad.dtype == torch.float32 else 8)
+    _check_param_grad(param, grad)
     for s, nm, need in ((m_lr, "m_lr", ap.l0[-1]), (v_lr, "v_lr", ap.l0[-1]), (m, "m", ap.d0[-1]),
                         (v, "v", ap.d0[-1]), (norms, "norms", 2 * ap.k0[-1]), (param, "param", n),
                         (grad, "grad", n)):
@@ -2028,8 +2017,7 @@ def apollo_step(ap: ApolloPlan, ws: ApolloWorkspace, param, grad, m_lr, v_lr, m,
         if s.numel() < need:
             raise ValueError(f"{nm} has {s.numel()} elements, the range needs {need}")
     _check_shadow(ap, shadow)
-    if step is not None:
-        _check(step, torch.int32, "step", align=4)
+    _check_step(step)
     common = dict(param=_ptr(param), grad=_ptr(grad), shadow=_ptr(shadow),
                   update_gap=int(update_gap), grad_dtype=_GDT[grad.dtype], t=int(t), lr=float(lr),
                   beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
@@ -2066,12 +2054,7 @@ class MuonPlan:
     workspace sizes) are built without a device; :meth:`to` makes the device tables."""
 
     def __init__(self, plan, rows):
-        if len(rows) != plan.num_tensors:
-            raise ValueError("one row count per tensor of the range")
-        if any(o % 4 for o in plan.offsets):
-            raise ValueError("tensor offsets must be multiples of 4 elements (16-byte loads)")
-        if max(o + n for o, n in zip(plan.offsets, plan.numels)) > plan.length:
-            raise ValueError("a tensor reaches past the range")
+        _check_range(plan, rows)
         self.plan = plan
         self.mats, self.xoff = [], []
         self.gram, self.poly, self.update = [], [], []
@@ -2080,9 +2063,7 @@ class MuonPlan:
             if not n:
                 self.xoff.append(-1)
                 continue
-            if n < 0 or numel % n:
-                raise ValueError(f"tensor {t}: {numel} elements are not {n} whole rows")
-            m = numel // n
+            m = _whole_rows(t, numel, n)
             r, c = min(n, m), max(n, m)
             rs, cs = (m, 1) if n <= m else (1, m)
             tr, tc = -(-r // MUON_TILE), -(-c // MUON_TILE)

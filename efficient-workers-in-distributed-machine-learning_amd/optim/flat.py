@@ -6,6 +6,11 @@ decay) and ``optim/adam.py:12-94`` (Adam/AMSGrad with explicit gradients).  The 
 over parameter tensors; these run one HIP kernel over a flat range (``ops.sgd_flat`` /
 ``ops.adam_flat``), and the top-k / QSGD exchanges fuse the SGD update into their decode kernel
 (``Codec.decode_apply_sgd``) so the averaged gradient never round-trips through HBM.
+
+Every class derives from :class:`_Flat` (the learning rate, the step counters, the whole-model
+step, the checkpoint); the ones whose step covers whole tensors from :class:`_PerTensor`; the
+three whose state the whole model's plan lays out from :class:`_Factored`.  ``optim/kinds.py``
+names the classes and their options for the command line, the trainer and ``make_optimizer``.
 """
 import math
 
@@ -37,8 +42,35 @@ class DeviceScalar:
         self._slot = (self._slot + 1) % len(self._ring)
 
 
-class _LrMixin:
-    """``lr`` as a host value mirrored into ``lr_t`` (device) on the GPU."""
+# how a saved hyper-parameter is read back from a checkpoint (every other one as it is)
+_READ = {"freeze_step": int, "seed": int, "coeff_beta": float, "factor_min": float,
+         "factor_max": float, "factor_threshold": float}
+
+
+class _Flat:
+    """What every optimizer here shares.  ``lr`` is a host value mirrored into ``lr_t`` (device)
+    on the GPU; ``steps`` counts the finished steps, and ``step_t`` is its device copy: the
+    kernels derive the bias correction (the dither, the refresh) from it, so a captured HIP graph
+    replays the current step's values, not the capture step's.  A subclass gives
+    :meth:`step_range` and names its checkpoint: ``_KIND``, the state tensors ``_STATE`` (one
+    that is ``None`` is not loaded; one in ``_OPTIONAL`` may be missing from the checkpoint) and
+    the saved hyper-parameters ``_HPARAMS`` (each loaded when the checkpoint has it)."""
+    fusable = False
+    _KIND = None
+    _STATE = ()
+    _OPTIONAL = ()
+    _HPARAMS = ()
+    _COUNTER = True  # keeps the device step counter
+
+    def _init(self, flat, lr):
+        self.flat = flat
+        dev = flat.data.device
+        self._lr_dev = DeviceScalar(lr, dev) if dev.type == "cuda" else None
+        self._lr = float(lr)
+        self.steps = 0
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) \
+            if self._COUNTER and dev.type == "cuda" else None
+        return dev
 
     @property
     def lr(self) -> float:
@@ -47,33 +79,121 @@ class _LrMixin:
     @lr.setter
     def lr(self, value: float):
         self._lr = float(value)
-        dev = getattr(self, "_lr_dev", None)
-        if dev is not None:
-            dev.set(self._lr)
+        if self._lr_dev is not None:
+            self._lr_dev.set(self._lr)
 
     @property
     def lr_t(self):
-        dev = getattr(self, "_lr_dev", None)
-        return None if dev is None else dev.t
+        return None if self._lr_dev is None else self._lr_dev.t
 
-    def _init_lr(self, lr, device):
-        self._lr_dev = DeviceScalar(lr, device) if device.type == "cuda" else None
-        self._lr = float(lr)
+    def _shadow(self, start, length):
+        """The range's view of the bf16 shadow parameters (None without them)."""
+        sh = self.flat.shadow
+        return None if sh is None else sh[start:start + length]
+
+    def step(self, grad: torch.Tensor = None, grad_scale: float = 1.0):
+        """Whole-model step (``grad`` defaults to the flat gradient buffer)."""
+        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
+        self.end_step()
+
+    def end_step(self):
+        self.steps += 1
+        if self.step_t is not None:
+            self.step_t.add_(1)  # on the stream: captured into the step graph
+
+    def state_dict(self):
+        return {"kind": self._KIND, **{k: getattr(self, k) for k in self._STATE},
+                "steps": self.steps, "lr": self.lr,
+                **{k: getattr(self, k) for k in self._HPARAMS}}
+
+    def load_state_dict(self, sd):
+        for k in self._STATE:
+            t = getattr(self, k)
+            if t is not None and not (k in self._OPTIONAL and sd.get(k) is None):
+                t.copy_(sd[k])
+        self.steps = int(sd["steps"])
+        if self.step_t is not None:
+            self.step_t.fill_(self.steps)
+        self.lr = sd.get("lr", self.lr)
+        for k in self._HPARAMS:
+            if k in sd:
+                setattr(self, k, _READ[k](sd[k]) if k in _READ else sd[k])
 
 
-class FlatSGD(_LrMixin):
+class _StateBytes:
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state (the tensors of ``_STATE`` that exist)."""
+        return sum(t.numel() * t.element_size()
+                   for t in (getattr(self, k) for k in self._STATE) if t is not None)
+
+
+class _PerTensor(_Flat):
+    """An optimizer with per-tensor quantities (norms, blocks, factors): a step covers one bucket
+    or the whole model, never another range.  ``_COVERS`` words the refusal; :meth:`_plan` caches
+    what :meth:`_make_plan` builds for a range from its ``BucketPlan``."""
+    _COVERS = None  # ("a layer-wise", "norms are")
+
+    def _init(self, flat, lr):
+        dev = super()._init(flat, lr)
+        # flat ranges a step may cover -> (first tensor, tensors): the whole model and each bucket
+        self._ranges = {(0, flat.numel): (0, len(flat.params))}
+        t0 = 0
+        for b in flat.buckets:
+            self._ranges[(b.start, b.length)] = (t0, len(b.params))
+            t0 += len(b.params)
+        self._plans = {}
+        return dev
+
+    def _range(self, start, length):
+        try:
+            return self._ranges[(start, length)]
+        except KeyError:
+            step, per = self._COVERS
+            raise ValueError(f"{step} step covers a bucket or the whole model ({per} per "
+                             f"tensor), not the range [{start}, {start + length})") from None
+
+    def _chunk_starts(self):
+        """The first chunk of every tensor when each starts a chunk of its own, and the total."""
+        from ..compress.plan import CHUNK
+
+        c0 = [0]
+        for p in self.flat.params:
+            c0.append(c0[-1] + (p.numel() + CHUNK - 1) // CHUNK)
+        return c0
+
+    def _bucket_plan(self, start, length):
+        """The ``BucketPlan`` of a range, its tensors' offsets counted from ``start``."""
+        from ..compress.plan import BucketPlan
+
+        t0, nt = self._range(start, length)
+        return BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
+                          [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start, length)
+
+    def _plan(self, start, length):
+        """The range's device plan (built once)."""
+        got = self._plans.get((start, length))
+        if got is None:
+            t0, nt = self._range(start, length)
+            got = self._plans[(start, length)] = self._make_plan(
+                self._bucket_plan(start, length), t0, nt)
+        return got
+
+
+class FlatSGD(_Flat):
     fusable = True
+    _KIND = "sgd"
+    _STATE = ("mom",)
+    _HPARAMS = ("momentum", "dampening", "weight_decay", "nesterov")
+    _COUNTER = False
 
     def __init__(self, flat, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        self.flat = flat
-        self._init_lr(lr, flat.data.device)
+        self._init(flat, lr)
         self.momentum, self.dampening = momentum, dampening
         self.weight_decay, self.nesterov = weight_decay, nesterov
         self.mom = torch.zeros_like(flat.data)
-        self.steps = 0
 
     @property
     def first(self) -> bool:
@@ -88,20 +208,15 @@ class FlatSGD(_LrMixin):
         p = self.flat.data[start:start + length]
         m = self.mom[start:start + length]
         if p.is_cuda:
-            sh = self.flat.shadow[start:start + length] if self.flat.shadow is not None else None
             ops.sgd_flat(p, m, grad, self.lr, self.momentum, self.dampening, self.weight_decay,
-                         grad_scale, self.nesterov, self.first, shadow=sh, lr_tensor=self.lr_t)
+                         grad_scale, self.nesterov, self.first,
+                         shadow=self._shadow(start, length), lr_tensor=self.lr_t)
             return
         g = grad.to(torch.float32)
         if grad_scale != 1.0:
             g = g * grad_scale
         oracle.sgd_apply(p, m, g, self.lr, self.momentum, self.dampening, self.weight_decay,
                          self.nesterov, self.first)
-
-    def step(self, grad: torch.Tensor = None, grad_scale: float = 1.0):
-        """Whole-model step (``grad`` defaults to the flat gradient buffer)."""
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
 
     def step_bucket_ptrs(self, b, dp, grads, grad_scale: float = 1.0):
         """SGD of bucket ``b`` from its per-tensor gradients ``grads`` (pointer mode), one
@@ -112,38 +227,20 @@ class FlatSGD(_LrMixin):
                      grad_scale, self.nesterov, self.first, shadow=self.flat.shadow_view(b),
                      lr_tensor=self.lr_t)
 
-    def end_step(self):
-        self.steps += 1
 
-    def state_dict(self):
-        hp = {k: v for k, v in self.hparams().items() if k != "lr_t"}
-        return {"kind": "sgd", "mom": self.mom, "steps": self.steps, **hp}
-
-    def load_state_dict(self, sd):
-        self.mom.copy_(sd["mom"])
-        self.steps = int(sd["steps"])
-        for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"):
-            if k in sd:
-                setattr(self, k, sd[k])
-
-
-class FlatAdam(_LrMixin):
-    fusable = False
+class FlatAdam(_Flat):
+    _KIND = "adam"
+    _STATE = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+    _OPTIONAL = ("max_exp_avg_sq",)
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False):
-        self.flat = flat
-        self._init_lr(lr, flat.data.device)
+        self._init(flat, lr)
         self.betas, self.eps = betas, eps
         self.weight_decay, self.amsgrad = weight_decay, amsgrad
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.max_exp_avg_sq = torch.zeros_like(flat.data) if amsgrad else None
-        self.steps = 0
-        # device copy of the step count: the kernel derives the bias correction from it, so a
-        # captured HIP graph replays the current step's correction (not the capture step's)
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=flat.data.device) \
-            if flat.data.is_cuda else None
 
     def step_range(self, start, length, grad, grad_scale=1.0):
         t = self.steps + 1
@@ -153,41 +250,18 @@ class FlatAdam(_LrMixin):
         vmax = self.max_exp_avg_sq[sl] if self.amsgrad else None
         if p.is_cuda:
             lr_step = self.lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
             ops.adam_flat(p, self.exp_avg[sl], self.exp_avg_sq[sl], vmax, grad, lr_step, b1, b2,
-                          self.eps, self.weight_decay, grad_scale, self.amsgrad, shadow=sh,
-                          step=self.step_t, lr=self.lr, lr_tensor=self.lr_t)
+                          self.eps, self.weight_decay, grad_scale, self.amsgrad,
+                          shadow=self._shadow(start, length), step=self.step_t, lr=self.lr,
+                          lr_tensor=self.lr_t)
             return
         g = grad.to(torch.float32) * grad_scale
         oracle.adam_apply(p, self.exp_avg[sl], self.exp_avg_sq[sl],
                           vmax if vmax is not None else torch.empty(0), g, self.lr, b1, b2,
                           self.eps, self.weight_decay, t, self.amsgrad)
 
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
 
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    def state_dict(self):
-        return {"kind": "adam", "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "max_exp_avg_sq": self.max_exp_avg_sq, "steps": self.steps, "lr": self.lr}
-
-    def load_state_dict(self, sd):
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        if self.amsgrad and sd.get("max_exp_avg_sq") is not None:
-            self.max_exp_avg_sq.copy_(sd["max_exp_avg_sq"])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
-
-
-class FlatAdam8bit(_LrMixin):
+class FlatAdam8bit(_PerTensor, _StateBytes):
     """8-bit Adam (Dettmers et al., ICLR 2022): :class:`FlatAdam`'s rule with both moments kept
     as one byte per element (``code_m`` / ``code_v``, indexed like ``flat.data``) plus one fp32
     absmax per 256-element block of a tensor (``absmax_m`` / ``absmax_v``, 32 slots per global
@@ -195,96 +269,38 @@ class FlatAdam8bit(_LrMixin):
     (``compress/oracle.py adam8_apply`` defines the format).  A step covers one bucket or the
     whole model, as blocks are counted per tensor: one HIP kernel on the GPU
     (``ops.adam8_step``), the torch oracle on the CPU.  No AMSGrad."""
-    fusable = False
+    _KIND = "adam8bit"
+    _STATE = ("code_m", "code_v", "absmax_m", "absmax_v")
+    _COVERS = ("an 8-bit Adam", "blocks are")
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        from ..compress.plan import CHUNK
-
-        self.flat = flat
-        dev = flat.data.device
-        self._init_lr(lr, dev)
+        dev = self._init(flat, lr)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        self._chunk0 = [0]
-        for p in flat.params:
-            self._chunk0.append(self._chunk0[-1] + (p.numel() + CHUNK - 1) // CHUNK)
+        self._chunk0 = self._chunk_starts()
         self.code_m, self.code_v, self.absmax_m, self.absmax_v = oracle.adam8_state(
             flat.data.numel(), self._chunk0[-1], dev)
-        # flat ranges a step may cover -> (first tensor, tensors): the whole model and each bucket
-        self._ranges = {(0, flat.numel): (0, len(flat.params))}
-        t0 = 0
-        for b in flat.buckets:
-            self._ranges[(b.start, b.length)] = (t0, len(b.params))
-            t0 += len(b.params)
-        self._plans = {}
 
-    def _range(self, start, length):
-        try:
-            return self._ranges[(start, length)]
-        except KeyError:
-            raise ValueError(f"an 8-bit Adam step covers a bucket or the whole model (blocks are "
-                             f"per tensor), not the range [{start}, {start + length})") from None
-
-    def _plan(self, start, length):
-        """The range's device plan (built once): its chunk table and absmax views."""
-        ap = self._plans.get((start, length))
-        if ap is None:
-            from ..compress.plan import BucketPlan
-
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            s0, s1 = (oracle.ADAM8_SLOTS * self._chunk0[t] for t in (t0, t0 + nt))
-            ap = ops.Adam8Plan(plan, self.absmax_m[s0:s1], self.absmax_v[s0:s1])
-            self._plans[(start, length)] = ap
-        return ap
-
-    def state_bytes(self) -> int:
-        """Bytes of optimizer state (the codes and the absmax arrays)."""
-        return sum(t.numel() * t.element_size()
-                   for t in (self.code_m, self.code_v, self.absmax_m, self.absmax_v))
+    def _make_plan(self, plan, t0, nt):
+        """The range's chunk table and absmax views."""
+        s0, s1 = (oracle.ADAM8_SLOTS * self._chunk0[t] for t in (t0, t0 + nt))
+        return ops.Adam8Plan(plan, self.absmax_m[s0:s1], self.absmax_v[s0:s1])
 
     def step_range(self, start, length, grad, grad_scale=1.0):
         t0, nt = self._range(start, length)
         sl = slice(start, start + length)
         p, cm, cv = self.flat.data[sl], self.code_m[sl], self.code_v[sl]
         if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
             ops.adam8_step(self._plan(start, length), p, grad, cm, cv,
                            lr_step=oracle.adam8_lr_step(self.lr, *self.betas, self.steps + 1),
                            betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                           grad_scale=grad_scale, shadow=sh, step=self.step_t, lr=self.lr,
-                           lr_tensor=self.lr_t)
+                           grad_scale=grad_scale, shadow=self._shadow(start, length),
+                           step=self.step_t, lr=self.lr, lr_tensor=self.lr_t)
             return
         blocks = [(self.flat.offsets[t] - start, self.flat.params[t].numel(),
                    oracle.ADAM8_SLOTS * self._chunk0[t]) for t in range(t0, t0 + nt)]
         g = grad.to(torch.float32) * grad_scale
         oracle.adam8_apply(p, cm, cv, self.absmax_m, self.absmax_v, g, blocks, self.lr,
                            *self.betas, self.eps, self.weight_decay, self.steps + 1)
-
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
-
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    def state_dict(self):
-        return {"kind": "adam8bit", "code_m": self.code_m, "code_v": self.code_v,
-                "absmax_m": self.absmax_m, "absmax_v": self.absmax_v, "steps": self.steps,
-                "lr": self.lr}
-
-    def load_state_dict(self, sd):
-        for k in ("code_m", "code_v", "absmax_m", "absmax_v"):
-            getattr(self, k).copy_(sd[k])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
 
 
 class FlatOnebitAdam(FlatAdam):
@@ -296,6 +312,8 @@ class FlatOnebitAdam(FlatAdam):
     (``Codec.encode_momentum`` / ``decode_apply_onebit``).  The error-feedback residual is per-rank
     state and lives in the exchange; this optimizer's state is the same on every rank."""
     onebit = True
+    _KIND = "onebit_adam"
+    _HPARAMS = ("freeze_step",)
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, freeze_step=None):
@@ -328,15 +346,8 @@ class FlatOnebitAdam(FlatAdam):
                                "step (a dense step would write exp_avg_sq)")
         super().step_range(start, length, grad, grad_scale)
 
-    def state_dict(self):
-        return dict(super().state_dict(), kind="onebit_adam", freeze_step=self.freeze_step)
 
-    def load_state_dict(self, sd):
-        super().load_state_dict(sd)
-        self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
-
-
-class FlatLion(_LrMixin):
+class FlatLion(_Flat):
     """Lion (Chen et al., "Symbolic Discovery of Optimization Algorithms", 2023): the update is
     the sign of an interpolation of the momentum and the gradient, ``p -= lr * (sign(m * beta1 +
     (1 - beta1) * g) + wd * p)``, then ``m = m * beta2 + (1 - beta2) * g``; one state buffer, half
@@ -346,20 +357,17 @@ class FlatLion(_LrMixin):
     element and applies the vote (``Codec.encode_vote`` / ``decode_apply_vote``).  ``step_t`` is
     the device copy of the step count: the vote's exact-zero dither reads it, so a captured step
     dithers with the current step."""
-    fusable = False
     lion = True
+    _KIND = "lion"
+    _STATE = ("exp_avg",)
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0):
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
             raise ValueError(f"Lion's betas must lie in [0, 1), not {betas!r}")
-        self.flat = flat
-        self._init_lr(lr, flat.data.device)
+        self._init(flat, lr)
         self.betas, self.weight_decay = (b1, b2), weight_decay
         self.exp_avg = torch.zeros_like(flat.data)
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=flat.data.device) \
-            if flat.data.is_cuda else None
 
     def hparams(self) -> dict:
         return dict(lr=self.lr, betas=self.betas, weight_decay=self.weight_decay,
@@ -370,36 +378,16 @@ class FlatLion(_LrMixin):
         sl = slice(start, start + length)
         p, m = self.flat.data[sl], self.exp_avg[sl]
         if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
-            ops.lion_flat(p, m, grad, self.lr, b1, b2, self.weight_decay, grad_scale, shadow=sh,
-                          lr_tensor=self.lr_t)
+            ops.lion_flat(p, m, grad, self.lr, b1, b2, self.weight_decay, grad_scale,
+                          shadow=self._shadow(start, length), lr_tensor=self.lr_t)
             return
         g = grad.to(torch.float32)
         if grad_scale != 1.0:
             g = g * grad_scale
         oracle.lion_apply(p, m, g, self.lr, b1, b2, self.weight_decay)
 
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
 
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    def state_dict(self):
-        return {"kind": "lion", "exp_avg": self.exp_avg, "steps": self.steps, "lr": self.lr}
-
-    def load_state_dict(self, sd):
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
-
-
-class _Layerwise(_LrMixin):
+class _Layerwise(_PerTensor):
     """Shared part of the layer-wise trust-ratio optimizers :class:`FlatLARS` / :class:`FlatLAMB`.
 
     A tensor *adapts* (takes a trust ratio) when it has two or more dimensions; biases and
@@ -408,57 +396,26 @@ class _Layerwise(_LrMixin):
     (:meth:`step_range` with that range): on the GPU two launches (``ops.layerwise_step``), on the
     CPU the torch oracle.  The 1-based step ``t`` is read from the device counter ``step_t``, so a
     captured step replays the current step's values."""
-    fusable = False
     kind = None
+    _OPTIONAL = ("ratio",)
+    _COVERS = ("a layer-wise", "norms are")
 
     def __init__(self, flat, lr, weight_decay):
-        self.flat = flat
-        dev = flat.data.device
-        self._init_lr(lr, dev)
+        dev = self._init(flat, lr)
         self.weight_decay = weight_decay
-        self.steps = 0
         self.adapts = [p.dim() >= 2 for p in flat.params]
         self.ratio = torch.ones(len(flat.params), dtype=torch.float32, device=dev)
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        # flat ranges a step may cover -> (first tensor, tensors): the whole model and each bucket
-        self._ranges = {(0, flat.numel): (0, len(flat.params))}
-        t0 = 0
-        for b in flat.buckets:
-            self._ranges[(b.start, b.length)] = (t0, len(b.params))
-            t0 += len(b.params)
-        self._plans = {}
         if dev.type == "cuda":
-            from ..compress.plan import CHUNK
-
             self._adapt_t = torch.tensor(self.adapts, dtype=torch.int32, device=dev)
-            self._chunk0 = [0]
-            for p in flat.params:
-                self._chunk0.append(self._chunk0[-1] + (p.numel() + CHUNK - 1) // CHUNK)
+            self._chunk0 = self._chunk_starts()
             self._partials = torch.zeros(2 * self._chunk0[-1], dtype=torch.float32, device=dev)
 
-    def _range(self, start, length):
-        try:
-            return self._ranges[(start, length)]
-        except KeyError:
-            raise ValueError(f"a layer-wise step covers a bucket or the whole model (norms are "
-                             f"per tensor), not the range [{start}, {start + length})") from None
-
-    def _plan(self, start, length):
-        """The range's device plan (built once): its tables and its views of ``adapt`` /
-        ``ratio`` / the per-chunk partial sums."""
-        lw = self._plans.get((start, length))
-        if lw is None:
-            from ..compress.plan import BucketPlan
-
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            c0, c1 = self._chunk0[t0], self._chunk0[t0 + nt]
-            lw = ops.LayerwisePlan(plan, self._adapt_t[t0:t0 + nt], self.ratio[t0:t0 + nt],
-                                   self._partials[2 * c0:2 * c1])
-            self._plans[(start, length)] = lw
-        return lw
+    def _make_plan(self, plan, t0, nt):
+        """The range's tables and its views of ``adapt`` / ``ratio`` / the per-chunk partial
+        sums."""
+        c0, c1 = self._chunk0[t0], self._chunk0[t0 + nt]
+        return ops.LayerwisePlan(plan, self._adapt_t[t0:t0 + nt], self.ratio[t0:t0 + nt],
+                                 self._partials[2 * c0:2 * c1])
 
     def _tensors(self, start, length):
         t0, nt = self._range(start, length)
@@ -471,30 +428,14 @@ class _Layerwise(_LrMixin):
         r = self.ratio[torch.tensor(self.adapts, dtype=torch.bool, device=self.ratio.device)]
         return (float(r.min()), float(r.max())) if r.numel() else None
 
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
-
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    def _load_common(self, sd):
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        if "ratio" in sd and sd["ratio"] is not None:
-            self.ratio.copy_(sd["ratio"])
-        self.lr = sd.get("lr", self.lr)
-        self.weight_decay = sd.get("weight_decay", self.weight_decay)
-
 
 class FlatLARS(_Layerwise):
     """LARS (You et al., 2017): per adapting tensor ``r = eta |p| / (|g| + wd |p|)`` (1 when a
     norm is zero), then :class:`FlatSGD`'s rule on ``r (g + wd p)`` with its own weight decay off
     (momentum buffer = the first such gradient, dampening, Nesterov)."""
-    kind = "lars"
+    kind = _KIND = "lars"
+    _STATE = ("mom", "ratio")
+    _HPARAMS = ("momentum", "dampening", "weight_decay", "nesterov", "eta")
 
     def __init__(self, flat, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0,
                  nesterov=False, eta=0.001):
@@ -512,12 +453,11 @@ class FlatLARS(_Layerwise):
         sl = slice(start, start + length)
         p, m = self.flat.data[sl], self.mom[sl]
         if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
             ops.layerwise_step(self._plan(start, length), "lars", p, grad, m, lr=self.lr,
                                weight_decay=self.weight_decay, grad_scale=grad_scale,
                                eta=self.eta, momentum=self.momentum, dampening=self.dampening,
                                nesterov=self.nesterov, first=self.first, step=self.step_t,
-                               lr_tensor=self.lr_t, shadow=sh)
+                               lr_tensor=self.lr_t, shadow=self._shadow(start, length))
             return
         t0, tensors = self._tensors(start, length)
         g = grad.to(torch.float32) * grad_scale
@@ -525,24 +465,14 @@ class FlatLARS(_Layerwise):
             p, m, g, tensors, self.lr, self.momentum, self.dampening, self.weight_decay,
             self.nesterov, self.first, self.eta)
 
-    def state_dict(self):
-        return {"kind": "lars", "mom": self.mom, "steps": self.steps, "ratio": self.ratio,
-                "lr": self.lr, "momentum": self.momentum, "dampening": self.dampening,
-                "weight_decay": self.weight_decay, "nesterov": self.nesterov, "eta": self.eta}
-
-    def load_state_dict(self, sd):
-        self.mom.copy_(sd["mom"])
-        self._load_common(sd)
-        for k in ("momentum", "dampening", "nesterov", "eta"):
-            if k in sd:
-                setattr(self, k, sd[k])
-
 
 class FlatLAMB(_Layerwise):
     """LAMB (You et al., ICLR 2020): Adam's moments with bias correction, ``u = m^ / (sqrt(v^) +
     eps) + wd p``, per adapting tensor ``r = |p| / |u|`` (1 when a norm is zero), ``p -= lr r u``.
     No clamp on ``|p|`` and no gradient clipping."""
-    kind = "lamb"
+    kind = _KIND = "lamb"
+    _STATE = ("exp_avg", "exp_avg_sq", "ratio")
+    _HPARAMS = ("weight_decay",)
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(flat, lr, weight_decay)
@@ -554,27 +484,17 @@ class FlatLAMB(_Layerwise):
         sl = slice(start, start + length)
         p, m, v = self.flat.data[sl], self.exp_avg[sl], self.exp_avg_sq[sl]
         if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
             ops.layerwise_step(self._plan(start, length), "lamb", p, grad, m, v, lr=self.lr,
                                weight_decay=self.weight_decay, grad_scale=grad_scale,
                                betas=self.betas, eps=self.eps, t=self.steps + 1,
-                               step=self.step_t, lr_tensor=self.lr_t, shadow=sh)
+                               step=self.step_t, lr_tensor=self.lr_t,
+                               shadow=self._shadow(start, length))
             return
         t0, tensors = self._tensors(start, length)
         g = grad.to(torch.float32) * grad_scale
         b1, b2 = self.betas
         self.ratio[t0:t0 + len(tensors)] = oracle.lamb_apply(
             p, m, v, g, tensors, self.lr, b1, b2, self.eps, self.weight_decay, self.steps + 1)
-
-    def state_dict(self):
-        return {"kind": "lamb", "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                "steps": self.steps, "ratio": self.ratio, "lr": self.lr,
-                "weight_decay": self.weight_decay}
-
-    def load_state_dict(self, sd):
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self._load_common(sd)
 
 
 class FlatOnebitLamb(FlatLAMB):
@@ -596,6 +516,10 @@ class FlatOnebitLamb(FlatLAMB):
     rank; the error-feedback residual lives in the exchange."""
     onebit = True
     onebit_kind = "lamb"
+    _KIND = "onebit_lamb"
+    _STATE = FlatLAMB._STATE + ("exp_avg_sq_fresh", "coeff_ema", "r_frozen")
+    _HPARAMS = FlatLAMB._HPARAMS + ("freeze_step", "coeff_beta", "factor_min", "factor_max",
+                                    "factor_threshold")
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  freeze_step=None, coeff_beta=0.9, factor_min=0.5, factor_max=4.0,
@@ -670,22 +594,11 @@ class FlatOnebitLamb(FlatLAMB):
         super().end_step()
 
     def state_dict(self):
-        return dict(super().state_dict(), kind="onebit_lamb", freeze_step=self.freeze_step,
-                    exp_avg_sq_fresh=self.exp_avg_sq_fresh, coeff_ema=self.coeff_ema,
-                    r_frozen=self.r_frozen, last_factor=self._factors,
-                    coeff_beta=self.coeff_beta, factor_min=self.factor_min,
-                    factor_max=self.factor_max, factor_threshold=self.factor_threshold)
+        return dict(super().state_dict(), last_factor=self._factors)  # both rows
 
     def load_state_dict(self, sd):
         super().load_state_dict(sd)
-        self.exp_avg_sq_fresh.copy_(sd["exp_avg_sq_fresh"])
-        self.coeff_ema.copy_(sd["coeff_ema"])
-        self.r_frozen.copy_(sd["r_frozen"])
         self._factors.copy_(sd["last_factor"])
-        self.freeze_step = int(sd.get("freeze_step", self.freeze_step))
-        for k in ("coeff_beta", "factor_min", "factor_max", "factor_threshold"):
-            if k in sd:
-                setattr(self, k, float(sd[k]))
 
 
 class FlatMuon(_Layerwise):
@@ -696,7 +609,9 @@ class FlatMuon(_Layerwise):
     p (1 - lr wd) - lr sqrt(max(1, n / m)) O``; the others take momentum SGD at ``lr_aux = lr *
     aux_lr / (the lr at construction)``, so a schedule moves both rates together.  On the GPU a
     step is ``ops.muon_step`` (``csrc/muon.hip``), on the CPU the torch oracle."""
-    kind = "muon"
+    kind = _KIND = "muon"
+    _STATE = ("mom",)
+    _HPARAMS = ("momentum", "weight_decay", "nesterov", "ns_steps", "ns_dtype", "aux_ratio")
 
     def __init__(self, flat, lr=0.02, momentum=0.95, weight_decay=0.0, nesterov=False,
                  ns_steps=5, ns_dtype="fp32", aux_lr=None):
@@ -722,24 +637,15 @@ class FlatMuon(_Layerwise):
     def trust_ratio_range(self):
         return None  # no trust ratios
 
-    def _plan(self, start, length):
-        """The range's device plan and workspace (built once).  The whole model steps in the
-        buckets' workspace when it fits and in one of its own otherwise."""
-        got = self._plans.get((start, length))
-        if got is None:
-            from ..compress.plan import BucketPlan
-
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            dev = self.flat.data.device
-            mp = ops.MuonPlan(plan, self.rows[t0:t0 + nt]).to(dev)
-            ws = self._ws
-            if ws is not None and not ws.fits(mp):
-                ws = ops.MuonWorkspace([mp], dev)
-            got = self._plans[(start, length)] = (mp, ws)
-        return got
+    def _make_plan(self, plan, t0, nt):
+        """The range's device plan and workspace.  The whole model steps in the buckets'
+        workspace when it fits and in one of its own otherwise."""
+        dev = self.flat.data.device
+        mp = ops.MuonPlan(plan, self.rows[t0:t0 + nt]).to(dev)
+        ws = self._ws
+        if ws is not None and not ws.fits(mp):
+            ws = ops.MuonWorkspace([mp], dev)
+        return mp, ws
 
     def step_range(self, start, length, grad, grad_scale=1.0):
         sl = slice(start, start + length)
@@ -748,31 +654,70 @@ class FlatMuon(_Layerwise):
                   weight_decay=self.weight_decay, nesterov=self.nesterov,
                   ns_steps=self.ns_steps, ns_dtype=self.ns_dtype)
         if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
             mp, ws = self._plan(start, length)
             c0 = self._chunk0[self._range(start, length)[0]]
             ops.muon_step(mp, ws, p, grad, m, self._partials[c0:c0 + mp.plan.num_chunks],
-                          grad_scale=grad_scale, lr_tensor=self.lr_t, shadow=sh, **hp)
+                          grad_scale=grad_scale, lr_tensor=self.lr_t,
+                          shadow=self._shadow(start, length), **hp)
             return
         t0, tensors = self._tensors(start, length)
         rows = [(off, n, self.rows[t0 + i]) for i, (off, n, _) in enumerate(tensors)]
         oracle.muon_apply(p, m, grad.to(torch.float32) * grad_scale, rows, **hp)
 
-    def state_dict(self):
-        return {"kind": "muon", "mom": self.mom, "steps": self.steps, "lr": self.lr,
-                "momentum": self.momentum, "weight_decay": self.weight_decay,
-                "nesterov": self.nesterov, "ns_steps": self.ns_steps, "ns_dtype": self.ns_dtype,
-                "aux_ratio": self.aux_ratio}
 
-    def load_state_dict(self, sd):
-        self.mom.copy_(sd["mom"])
-        self._load_common(sd)
-        for k in ("momentum", "nesterov", "ns_steps", "ns_dtype", "aux_ratio"):
-            if k in sd:
-                setattr(self, k, sd[k])
+class _Factored(_PerTensor, _StateBytes):
+    """Shared part of :class:`FlatAdafactor`, :class:`FlatGalore` and :class:`FlatApollo`, whose
+    state per tensor depends on the tensor's shape.  ``rows[t]`` is ``shape[0]`` of a tensor with
+    ``dim() >= 2`` and 0 of a vector.  The whole model's plan (``_whole``) lays the state out; a
+    bucket's plan sees views of it: ``_LAYOUT`` names, per state tensor of that kind, the plan's
+    list of per-tensor offsets (with the total at its end) and the floats per unit of it.  A
+    subclass gives ``_LAYOUT``, :meth:`_new_plan`, :meth:`_hp` and :meth:`_tensors`; its kernels
+    and oracle are ``ops.<kind>_step`` / ``ops.<Kind>Workspace`` and ``oracle.<kind>_apply``."""
+    _LAYOUT = ()
+    _ORACLE_ONLY = ()  # attributes the oracle takes on top of _hp() (the kernels read the plan's)
+
+    def _init(self, flat, lr):
+        dev = super()._init(flat, lr)
+        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
+        self._whole = self._new_plan(self._bucket_plan(0, flat.numel), 0, len(flat.params))
+        for name, offsets, per in self._LAYOUT:
+            setattr(self, name, torch.zeros(per * getattr(self._whole, offsets)[-1],
+                                            dtype=torch.float32, device=dev))
+        self._ws = getattr(ops, self._KIND.capitalize() + "Workspace")(self._whole, dev) \
+            if dev.type == "cuda" else None
+        return dev
+
+    def _make_plan(self, plan, t0, nt):
+        return self._new_plan(plan, t0, nt).to(self.flat.data.device)
+
+    def _state(self, t0, nt):
+        """The views of the ``_LAYOUT`` tensors that belong to tensors ``t0 .. t0 + nt``."""
+        w = self._whole
+        return tuple(getattr(self, name)[per * getattr(w, offsets)[t0]:
+                                         per * getattr(w, offsets)[t0 + nt]]
+                     for name, offsets, per in self._LAYOUT)
+
+    def _operands(self, start, length, t0, nt):
+        """The state a step of the range takes, in the order of the kernels' and the oracle's
+        arguments."""
+        return self._state(t0, nt)
+
+    def step_range(self, start, length, grad, grad_scale=1.0):
+        t0, nt = self._range(start, length)
+        p = self.flat.data[start:start + length]
+        state, hp = self._operands(start, length, t0, nt), self._hp()
+        if p.is_cuda:
+            getattr(ops, self._KIND + "_step")(
+                self._plan(start, length), self._ws, p, grad, *state, t=self.steps + 1,
+                grad_scale=grad_scale, step=self.step_t, lr_tensor=self.lr_t,
+                shadow=self._shadow(start, length), **hp)
+            return
+        getattr(oracle, self._KIND + "_apply")(
+            p, *state, grad.to(torch.float32) * grad_scale, self._tensors(start, length),
+            step=self.steps + 1, **{k: getattr(self, k) for k in self._ORACLE_ONLY}, **hp)
 
 
-class FlatAdafactor(_LrMixin):
+class FlatAdafactor(_Factored):
     """Adafactor (Shazeer and Stern, ICML 2018) with an external learning rate
     (``compress/oracle.py adafactor_apply``).  A tensor with ``dim() >= 2``, viewed as ``[n, m] =
     [shape[0], numel / shape[0]]`` like :class:`FlatMuon`'s, keeps ``n + m`` floats of
@@ -782,66 +727,31 @@ class FlatAdafactor(_LrMixin):
     ``scale_parameter``, scaled by ``max(1e-3, RMS(p))``.  A step covers one bucket or the whole
     model: four HIP launches on the GPU (``ops.adafactor_step``, which reads ``t`` from the
     device counter ``step_t``), the torch oracle on the CPU."""
-    fusable = False
+    _KIND = "adafactor"
+    _STATE = ("row", "col", "v", "m")
+    _LAYOUT = (("row", "r0", 1), ("col", "c0", 1), ("v", "v0", 1))
+    _COVERS = ("an Adafactor", "statistics are")
 
     def __init__(self, flat, lr=1e-3, beta1=0.0, clip=1.0, scale_parameter=False,
                  weight_decay=0.0, decay=0.8):
-        from ..compress.plan import BucketPlan
-
         if not 0.0 <= beta1 < 1.0 or not clip > 0 or not decay > 0:
             raise ValueError(f"Adafactor needs beta1 in [0, 1), clip > 0 and decay > 0, not "
                              f"{beta1!r}, {clip!r}, {decay!r}")
-        self.flat = flat
-        dev = flat.data.device
-        self._init_lr(lr, dev)
         self.beta1, self.clip, self.decay = float(beta1), float(clip), float(decay)
         self.scale_parameter, self.weight_decay = bool(scale_parameter), weight_decay
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
-        self._ranges = {(0, flat.numel): (0, len(flat.params))}
-        t0 = 0
-        for b in flat.buckets:
-            self._ranges[(b.start, b.length)] = (t0, len(b.params))
-            t0 += len(b.params)
-        # the whole model's plan lays the state out; a bucket's plan sees views of it
-        self._whole = ops.AdafactorPlan(
-            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
-            self.rows)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.row = torch.zeros(self._whole.r0[-1], **f32)
-        self.col = torch.zeros(self._whole.c0[-1], **f32)
-        self.v = torch.zeros(self._whole.v0[-1], **f32)
+        self._init(flat, lr)
         self.m = torch.zeros_like(flat.data) if self.beta1 > 0 else None
-        self._plans = {}
-        self._ws = ops.AdafactorWorkspace(self._whole, dev) if dev.type == "cuda" else None
 
-    def _range(self, start, length):
-        try:
-            return self._ranges[(start, length)]
-        except KeyError:
-            raise ValueError(f"an Adafactor step covers a bucket or the whole model (statistics "
-                             f"are per tensor), not the range [{start}, {start + length})") from None
+    def _new_plan(self, plan, t0, nt):
+        return ops.AdafactorPlan(plan, self.rows[t0:t0 + nt])
 
-    def _plan(self, start, length):
-        """The range's device plan (built once)."""
-        ap = self._plans.get((start, length))
-        if ap is None:
-            from ..compress.plan import BucketPlan
+    def _operands(self, start, length, t0, nt):
+        m = self.m[start:start + length] if self.m is not None else None
+        return self._state(t0, nt) + (m,)
 
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            ap = ops.AdafactorPlan(plan, self.rows[t0:t0 + nt]).to(self.flat.data.device)
-            self._plans[(start, length)] = ap
-        return ap
-
-    def _state(self, t0, nt):
-        """The views of ``row`` / ``col`` / ``v`` that belong to tensors ``t0 .. t0 + nt``."""
-        w = self._whole
-        return (self.row[w.r0[t0]:w.r0[t0 + nt]], self.col[w.c0[t0]:w.c0[t0 + nt]],
-                self.v[w.v0[t0]:w.v0[t0 + nt]])
+    def _hp(self):
+        return dict(lr=self.lr, beta1=self.beta1, clip=self.clip, decay=self.decay,
+                    scale_parameter=self.scale_parameter, weight_decay=self.weight_decay)
 
     def _tensors(self, start, length):
         """The oracle's ``(offset, numel, rows, s0, s1)`` rows of a range, the state offsets
@@ -852,53 +762,8 @@ class FlatAdafactor(_LrMixin):
                  (w.r0[t] - w.r0[t0]) if self.rows[t] else (w.v0[t] - w.v0[t0]),
                  w.c0[t] - w.c0[t0]) for t in range(t0, t0 + nt)]
 
-    def state_bytes(self) -> int:
-        """Bytes of optimizer state: ``row``, ``col``, ``v`` and, with ``beta1 > 0``, ``m``."""
-        return sum(t.numel() * t.element_size()
-                   for t in (self.row, self.col, self.v, self.m) if t is not None)
 
-    def step_range(self, start, length, grad, grad_scale=1.0):
-        t0, nt = self._range(start, length)
-        sl = slice(start, start + length)
-        p = self.flat.data[sl]
-        m = self.m[sl] if self.m is not None else None
-        row, col, v = self._state(t0, nt)
-        hp = dict(lr=self.lr, beta1=self.beta1, clip=self.clip, decay=self.decay,
-                  scale_parameter=self.scale_parameter, weight_decay=self.weight_decay)
-        if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
-            ops.adafactor_step(self._plan(start, length), self._ws, p, grad, row, col, v, m,
-                               t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
-                               lr_tensor=self.lr_t, shadow=sh, **hp)
-            return
-        oracle.adafactor_apply(p, row, col, v, m, grad.to(torch.float32) * grad_scale,
-                               self._tensors(start, length), step=self.steps + 1, **hp)
-
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
-
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    def state_dict(self):
-        return {"kind": "adafactor", "row": self.row, "col": self.col, "v": self.v, "m": self.m,
-                "steps": self.steps, "lr": self.lr}
-
-    def load_state_dict(self, sd):
-        for k in ("row", "col", "v"):
-            getattr(self, k).copy_(sd[k])
-        if self.m is not None:
-            self.m.copy_(sd["m"])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
-
-
-class FlatGalore(_LrMixin):
+class FlatGalore(_Factored):
     """GaLore (Zhao et al., ICML 2024): Adam whose two moments live in a rank-``rank`` subspace
     of each weight matrix (``compress/oracle.py galore_apply``).  A tensor with ``dim() >= 2``,
     viewed as ``[n, m] = [shape[0], numel / shape[0]]`` like :class:`FlatMuon`'s, whose short side
@@ -911,69 +776,32 @@ class FlatGalore(_LrMixin):
     :class:`FlatAdam`'s L2 term.  A step covers one bucket or the whole model: a fixed number of
     HIP launches on the GPU (``ops.galore_step``, which reads ``t`` from the device counter
     ``step_t``), the torch oracle on the CPU."""
-    kind = "galore"
-    fusable = False
+    kind = _KIND = "galore"
     ITERS = 2
+    _STATE = ("proj", "m_lr", "v_lr", "m", "v")
+    _LAYOUT = (("proj", "p0", 1), ("m_lr", "l0", 1), ("v_lr", "l0", 1), ("m", "d0", 1),
+               ("v", "d0", 1))
+    _ORACLE_ONLY = ("rank",)
+    _COVERS = ("a GaLore", "projectors are")
 
     def __init__(self, flat, lr=1e-3, rank=64, update_gap=200, scale=0.25, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=0.0, seed=0):
-        from ..compress.plan import BucketPlan
-
         if rank % 16 or not 16 <= rank <= 128 or update_gap < 1 or not scale > 0:
             raise ValueError(f"GaLore needs a rank that is a multiple of 16 in 16..128, "
                              f"update_gap >= 1 and scale > 0, not {rank!r}, {update_gap!r}, "
                              f"{scale!r}")
-        self.flat = flat
-        dev = flat.data.device
-        self._init_lr(lr, dev)
         self.rank, self.update_gap, self.scale = int(rank), int(update_gap), float(scale)
         self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
-        self._ranges = {(0, flat.numel): (0, len(flat.params))}
-        t0 = 0
-        for b in flat.buckets:
-            self._ranges[(b.start, b.length)] = (t0, len(b.params))
-            t0 += len(b.params)
-        # the whole model's plan lays the state out; a bucket's plan sees views of it
-        self._whole = w = ops.GalorePlan(
-            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
-            self.rows, self.rank)
-        f32 = dict(dtype=torch.float32, device=dev)
+        dev = self._init(flat, lr)
         gen = torch.Generator().manual_seed(seed)
-        self.proj = torch.randn(w.p0[-1], generator=gen).to(dev)
-        self.m_lr, self.v_lr = torch.zeros(w.l0[-1], **f32), torch.zeros(w.l0[-1], **f32)
-        self.m, self.v = torch.zeros(w.d0[-1], **f32), torch.zeros(w.d0[-1], **f32)
-        self._plans = {}
-        self._ws = ops.GaloreWorkspace(w, dev) if dev.type == "cuda" else None
+        self.proj = torch.randn(self._whole.p0[-1], generator=gen).to(dev)
 
-    def _range(self, start, length):
-        try:
-            return self._ranges[(start, length)]
-        except KeyError:
-            raise ValueError(f"a GaLore step covers a bucket or the whole model (projectors are "
-                             f"per tensor), not the range [{start}, {start + length})") from None
+    def _new_plan(self, plan, t0, nt):
+        return ops.GalorePlan(plan, self.rows[t0:t0 + nt], self.rank)
 
-    def _plan(self, start, length):
-        """The range's device plan (built once)."""
-        gp = self._plans.get((start, length))
-        if gp is None:
-            from ..compress.plan import BucketPlan
-
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            gp = ops.GalorePlan(plan, self.rows[t0:t0 + nt], self.rank).to(self.flat.data.device)
-            self._plans[(start, length)] = gp
-        return gp
-
-    def _state(self, t0, nt):
-        """The views of ``proj``, ``m_lr``, ``v_lr``, ``m``, ``v`` of tensors ``t0 .. t0 + nt``."""
-        w = self._whole
-        pj, lr, d = (slice(x[t0], x[t0 + nt]) for x in (w.p0, w.l0, w.d0))
-        return self.proj[pj], self.m_lr[lr], self.v_lr[lr], self.m[d], self.v[d]
+    def _hp(self):
+        return dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale, betas=self.betas,
+                    eps=self.eps, weight_decay=self.weight_decay, iters=self.ITERS)
 
     def _tensors(self, start, length):
         """The oracle's ``(offset, numel, rows, p0, s0)`` rows of a range, the state offsets
@@ -985,52 +813,8 @@ class FlatGalore(_LrMixin):
                  (w.l0[t] - w.l0[t0]) if w.projected[t] else (w.d0[t] - w.d0[t0]))
                 for t in range(t0, t0 + nt)]
 
-    def state_bytes(self) -> int:
-        """Bytes of optimizer state: the projectors and the low-rank and dense moments."""
-        return sum(t.numel() * t.element_size()
-                   for t in (self.proj, self.m_lr, self.v_lr, self.m, self.v))
 
-    def step_range(self, start, length, grad, grad_scale=1.0):
-        t0, nt = self._range(start, length)
-        sl = slice(start, start + length)
-        p = self.flat.data[sl]
-        hp = dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale, betas=self.betas,
-                  eps=self.eps, weight_decay=self.weight_decay, iters=self.ITERS)
-        if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
-            ops.galore_step(self._plan(start, length), self._ws, p, grad, *self._state(t0, nt),
-                            t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
-                            lr_tensor=self.lr_t, shadow=sh, **hp)
-            return
-        oracle.galore_apply(p, *self._state(t0, nt), grad.to(torch.float32) * grad_scale,
-                            self._tensors(start, length), step=self.steps + 1, rank=self.rank,
-                            **hp)
-
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
-
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    _STATE = ("proj", "m_lr", "v_lr", "m", "v")
-
-    def state_dict(self):
-        return {"kind": "galore", **{k: getattr(self, k) for k in self._STATE},
-                "steps": self.steps, "lr": self.lr}
-
-    def load_state_dict(self, sd):
-        for k in self._STATE:
-            getattr(self, k).copy_(sd[k])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
-
-
-class FlatApollo(_LrMixin):
+class FlatApollo(_Factored):
     """APOLLO (Zhu et al., MLSys 2025): the Adam moments of a rank-``rank`` random projection of
     each weight matrix's gradient, kept only to estimate a learning-rate scale per long-side
     column (``scale_type="channel"``) or per tensor (``"tensor"``; with ``rank=1`` the paper's
@@ -1043,72 +827,34 @@ class FlatApollo(_LrMixin):
     weight decay is decoupled.  A step covers one bucket or the whole model: three HIP launches on
     the GPU (``ops.apollo_step``, which reads ``t`` from the device counter ``step_t``), the torch
     oracle on the CPU."""
-    kind = "apollo"
-    fusable = False
+    kind = _KIND = "apollo"
+    _STATE = ("m_lr", "v_lr", "m", "v", "norms")
+    _HPARAMS = ("seed",)
+    # norms: [matrix][parity of the step]
+    _LAYOUT = (("m_lr", "l0", 1), ("v_lr", "l0", 1), ("m", "d0", 1), ("v", "d0", 1),
+               ("norms", "k0", 2))
+    _ORACLE_ONLY = ("rank",)
+    _COVERS = ("an APOLLO", "scales and norms are")
 
     def __init__(self, flat, lr=1e-3, rank=64, update_gap=200, scale=1.0, scale_type="channel",
                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, seed=0):
-        from ..compress.plan import BucketPlan
-
         if ((rank != 1 and (rank % 16 or not 16 <= rank <= 128)) or update_gap < 1
                 or not scale > 0 or scale_type not in ops.APOLLO_SCALE_TYPES):
             raise ValueError(f"APOLLO needs a rank of 1 or a multiple of 16 in 16..128, "
                              f"update_gap >= 1, scale > 0 and a scale type of channel or tensor, "
                              f"not {rank!r}, {update_gap!r}, {scale!r}, {scale_type!r}")
-        self.flat = flat
-        dev = flat.data.device
-        self._init_lr(lr, dev)
         self.rank, self.update_gap, self.scale = int(rank), int(update_gap), float(scale)
         self.scale_type, self.seed = scale_type, int(seed)
         self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
-        self.steps = 0
-        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
-        self.rows = [p.shape[0] if p.dim() >= 2 else 0 for p in flat.params]
-        self._ranges = {(0, flat.numel): (0, len(flat.params))}
-        t0 = 0
-        for b in flat.buckets:
-            self._ranges[(b.start, b.length)] = (t0, len(b.params))
-            t0 += len(b.params)
-        # the whole model's plan lays the state out; a bucket's plan sees views of it
-        self._whole = w = ops.ApolloPlan(
-            BucketPlan([p.numel() for p in flat.params], list(flat.offsets), 1.0, 0, flat.numel),
-            self.rows, self.rank)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.m_lr, self.v_lr = torch.zeros(w.l0[-1], **f32), torch.zeros(w.l0[-1], **f32)
-        self.m, self.v = torch.zeros(w.d0[-1], **f32), torch.zeros(w.d0[-1], **f32)
-        self.norms = torch.zeros(2 * w.k0[-1], **f32)  # [matrix][parity of the step]
-        self._plans = {}
-        self._ws = ops.ApolloWorkspace(w, dev) if dev.type == "cuda" else None
+        self._init(flat, lr)
 
-    def _range(self, start, length):
-        try:
-            return self._ranges[(start, length)]
-        except KeyError:
-            raise ValueError(f"an APOLLO step covers a bucket or the whole model (scales and "
-                             f"norms are per tensor), not the range [{start}, {start + length})"
-                             ) from None
+    def _new_plan(self, plan, t0, nt):
+        return ops.ApolloPlan(plan, self.rows[t0:t0 + nt], self.rank, t0)
 
-    def _plan(self, start, length):
-        """The range's device plan (built once)."""
-        ap = self._plans.get((start, length))
-        if ap is None:
-            from ..compress.plan import BucketPlan
-
-            t0, nt = self._range(start, length)
-            plan = BucketPlan([p.numel() for p in self.flat.params[t0:t0 + nt]],
-                              [o - start for o in self.flat.offsets[t0:t0 + nt]], 1.0, start,
-                              length)
-            ap = ops.ApolloPlan(plan, self.rows[t0:t0 + nt], self.rank, t0).to(
-                self.flat.data.device)
-            self._plans[(start, length)] = ap
-        return ap
-
-    def _state(self, t0, nt):
-        """The views of ``m_lr``, ``v_lr``, ``m``, ``v``, ``norms`` of tensors ``t0 .. t0 + nt``."""
-        w = self._whole
-        lr, d = (slice(x[t0], x[t0 + nt]) for x in (w.l0, w.d0))
-        return (self.m_lr[lr], self.v_lr[lr], self.m[d], self.v[d],
-                self.norms[2 * w.k0[t0]:2 * w.k0[t0 + nt]])
+    def _hp(self):
+        return dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale,
+                    scale_type=self.scale_type, betas=self.betas, eps=self.eps,
+                    weight_decay=self.weight_decay, seed=self.seed)
 
     def _tensors(self, start, length):
         """The oracle's ``(offset, numel, rows, gidx, s0, k)`` rows of a range, the state offsets
@@ -1120,107 +866,15 @@ class FlatApollo(_LrMixin):
                  (w.l0[t] - w.l0[t0]) if w.projected[t] else (w.d0[t] - w.d0[t0]),
                  w.k0[t] - w.k0[t0]) for t in range(t0, t0 + nt)]
 
-    def state_bytes(self) -> int:
-        """Bytes of optimizer state: the low-rank and dense moments and the stored norms."""
-        return sum(t.numel() * t.element_size() for t in (getattr(self, k) for k in self._STATE))
-
-    def step_range(self, start, length, grad, grad_scale=1.0):
-        t0, nt = self._range(start, length)
-        sl = slice(start, start + length)
-        p = self.flat.data[sl]
-        hp = dict(lr=self.lr, update_gap=self.update_gap, scale=self.scale,
-                  scale_type=self.scale_type, betas=self.betas, eps=self.eps,
-                  weight_decay=self.weight_decay, seed=self.seed)
-        if p.is_cuda:
-            sh = self.flat.shadow[sl] if self.flat.shadow is not None else None
-            ops.apollo_step(self._plan(start, length), self._ws, p, grad, *self._state(t0, nt),
-                            t=self.steps + 1, grad_scale=grad_scale, step=self.step_t,
-                            lr_tensor=self.lr_t, shadow=sh, **hp)
-            return
-        oracle.apollo_apply(p, *self._state(t0, nt), grad.to(torch.float32) * grad_scale,
-                            self._tensors(start, length), step=self.steps + 1, rank=self.rank,
-                            **hp)
-
-    def step(self, grad=None, grad_scale=1.0):
-        self.step_range(0, self.flat.numel, self.flat.grad if grad is None else grad, grad_scale)
-        self.end_step()
-
-    def end_step(self):
-        self.steps += 1
-        if self.step_t is not None:
-            self.step_t.add_(1)  # on the stream: captured into the step graph
-
-    _STATE = ("m_lr", "v_lr", "m", "v", "norms")
-
-    def state_dict(self):
-        return {"kind": "apollo", **{k: getattr(self, k) for k in self._STATE},
-                "steps": self.steps, "lr": self.lr, "seed": self.seed}
-
-    def load_state_dict(self, sd):
-        for k in self._STATE:
-            getattr(self, k).copy_(sd[k])
-        self.steps = int(sd["steps"])
-        if self.step_t is not None:
-            self.step_t.fill_(self.steps)
-        self.lr = sd.get("lr", self.lr)
-        self.seed = int(sd.get("seed", self.seed))
-
 
 def make_optimizer(name, flat, **kw):
+    """The optimizer ``optim/kinds.py`` lists under ``name`` (any letter case), built from the
+    keywords it takes: the common ones under their own names and its options under theirs
+    (``galore_rank=``, ``ns_steps=``, ...).  A keyword it does not take is ignored, and one that
+    is ``None`` means the default."""
+    from .kinds import KINDS  # the table names the classes above
+
     name = name.lower()
-    if name == "apollo":
-        return FlatApollo(flat, lr=kw.get("lr", 1e-3), rank=kw.get("apollo_rank") or 64,
-                          update_gap=kw.get("apollo_update_gap") or 200,
-                          scale=kw.get("apollo_scale") or 1.0,
-                          scale_type=kw.get("apollo_scale_type") or "channel",
-                          eps=kw.get("eps", 1e-8), weight_decay=kw.get("weight_decay", 0.0),
-                          seed=kw.get("seed") or 0)
-    if name == "galore":
-        return FlatGalore(flat, lr=kw.get("lr", 1e-3), rank=kw.get("galore_rank") or 64,
-                          update_gap=kw.get("galore_update_gap") or 200,
-                          scale=kw.get("galore_scale") or 0.25, eps=kw.get("eps", 1e-8),
-                          weight_decay=kw.get("weight_decay", 0.0))
-    if name == "adafactor":
-        return FlatAdafactor(flat, lr=kw.get("lr", 1e-3), beta1=kw.get("adafactor_beta1") or 0.0,
-                             clip=kw.get("adafactor_clip") or 1.0,
-                             scale_parameter=bool(kw.get("adafactor_scale_parameter")),
-                             weight_decay=kw.get("weight_decay", 0.0))
-    if name == "muon":
-        return FlatMuon(flat, aux_lr=kw.get("aux_lr"), ns_steps=kw.get("ns_steps") or 5,
-                        ns_dtype=kw.get("ns_dtype") or "fp32",
-                        **{k: v for k, v in kw.items()
-                           if k in ("lr", "momentum", "weight_decay", "nesterov")})
-    if name == "onebit_lamb":
-        return FlatOnebitLamb(flat, lr=kw.get("lr", 1e-3),
-                              weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),
-                              freeze_step=kw.get("freeze_step"))
-    if name == "lars":
-        return FlatLARS(flat, eta=kw.get("eta", 0.001),
-                        **{k: v for k, v in kw.items()
-                           if k in ("lr", "momentum", "dampening", "weight_decay", "nesterov")})
-    if name == "lamb":
-        return FlatLAMB(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
-                        eps=kw.get("eps", 1e-8))
-    if name == "sgd":
-        return FlatSGD(flat, **{k: v for k, v in kw.items()
-                                if k in ("lr", "momentum", "dampening", "weight_decay",
-                                         "nesterov")})
-    if name in ("adam", "amsgrad"):
-        return FlatAdam(flat, lr=kw.get("lr", 1e-3), weight_decay=kw.get("weight_decay", 0.0),
-                        eps=kw.get("eps", 1e-8),
-                        amsgrad=(name == "amsgrad") or kw.get("amsgrad", False))
-    if name == "adam8bit":
-        if kw.get("amsgrad", False):
-            raise ValueError("8-bit Adam has no AMSGrad: a running maximum of the second moment "
-                             "would be a third quantised state")
-        return FlatAdam8bit(flat, lr=kw.get("lr", 1e-3),
-                            weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8))
-    if name == "lion":
-        return FlatLion(flat, lr=kw.get("lr", 1e-4), betas=kw.get("betas") or (0.9, 0.99),
-                        weight_decay=kw.get("weight_decay", 0.0))
-    if name == "onebit_adam":
-        return FlatOnebitAdam(flat, lr=kw.get("lr", 1e-3),
-                              weight_decay=kw.get("weight_decay", 0.0), eps=kw.get("eps", 1e-8),
-                              amsgrad=kw.get("amsgrad", False),
-                              freeze_step=kw.get("freeze_step"))
-    raise ValueError(f"unknown optimizer {name!r}")
+    if name not in KINDS:
+        raise ValueError(f"unknown optimizer {name!r}")
+    return KINDS[name].build(flat, kw)

@@ -23,6 +23,7 @@ from ..config import Config
 from ..data import DeviceLoader, load_dataset
 from ..models import build_model, canonical_name, input_shape
 from ..models.fused import set_enabled as set_fused_nn
+from ..optim import kinds as optimizers
 from ..optim.flat import make_optimizer
 from ..parallel.comm import Comm, init_distributed
 from ..parallel.engine import (GradientExchange, SegmentedCapture, StepStats, Stopwatch,
@@ -233,22 +234,11 @@ class Trainer:
         lr = cfg.lr * (n_workers if cfg.lr_scale_world else 1)
         self.base_lr = lr
         self.n_workers = n_workers
-        self.opt = make_optimizer(cfg.optimizer, self.flat, lr=lr, momentum=cfg.momentum,
-                                  dampening=cfg.dampening, weight_decay=cfg.weight_decay,
-                                  nesterov=cfg.nesterov, eps=cfg.adam_eps,
-                                  freeze_step=cfg.onebit_warmup_steps, eta=cfg.lars_eta,
-                                  betas=cfg.lion_betas, ns_steps=cfg.muon_ns_steps,
-                                  ns_dtype=cfg.muon_ns_dtype, aux_lr=cfg.muon_aux_lr,
-                                  adafactor_beta1=cfg.adafactor_beta1,
-                                  adafactor_clip=cfg.adafactor_clip,
-                                  adafactor_scale_parameter=cfg.adafactor_scale_parameter,
-                                  galore_rank=cfg.galore_rank,
-                                  galore_update_gap=cfg.galore_update_gap,
-                                  galore_scale=cfg.galore_scale,
-                                  apollo_rank=cfg.apollo_rank,
-                                  apollo_update_gap=cfg.apollo_update_gap,
-                                  apollo_scale=cfg.apollo_scale,
-                                  apollo_scale_type=cfg.apollo_scale_type, seed=cfg.seed)
+        # every keyword of optim/kinds.py from its Config field; the optimizer takes its own
+        opt_kw = {kw: getattr(cfg, f) for kw, f in optimizers.COMMON.items()}
+        opt_kw.update((o.kw, getattr(cfg, o.field))
+                      for k in optimizers.KINDS.values() for o in k.options)
+        self.opt = make_optimizer(cfg.optimizer, self.flat, lr=lr, **opt_kw)
 
         # --clip-grad-norm: one clipper for every exchange of this trainer (both stages of 1-bit
         # Adam share it); it runs once per step, after backward and before the first encode
